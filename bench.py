@@ -1,6 +1,10 @@
 """Benchmark: batched 64 KiB-block snappy compress + uncompress on MI355X (BASELINE.json).
 
-`python bench.py --gpus N --steps K --warmup W`.  With N > 1 and no WORLD_SIZE in the
+`python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]`.  A plain run sets
+up the headline workload, warms up, times its K steps, checks its round trip and prints the
+result line; `--dump-outputs DIR` also writes what the last timed step computed (dump_outputs).
+Everything else below -- configs 4 and 5, reference mode, per-kernel rooflines, the CPU baseline
+-- takes runs of its own and is measured only with `--full`.  With N > 1 and no WORLD_SIZE in the
 environment the script starts N ranks itself (torch.distributed.run, before any GPU call) and
 exits with their status; under torchrun it checks WORLD_SIZE == N and that the node has N GPUs,
 and exits non-zero otherwise.  One process per GPU, RCCL for the collectives.
@@ -281,6 +285,42 @@ def load_package_cached():
     return _SM
 
 
+DUMP_SAMPLE = 64  # blocks whose bytes --dump-outputs writes: 64 x (76,496 + 65,536) float32 = 36 MB
+
+
+def dump_outputs(batch, out_dir, chunk=500):
+    """--dump-outputs: what the last step left for its caller, as <name>.npy under out_dir.
+    Of every block (float64, exact): comp_len, dec_len and status, and a position-weighted byte
+    sum of its compressed stream (comp_checksum) and of its decoded bytes (dec_checksum).  Of a
+    fixed seeded sample of blocks (sample_blocks), the bytes themselves as float32: comp_sample
+    (each stream zero-padded to its slot, whose tail the compressor leaves unwritten) and
+    dec_sample."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    dev, nblk = batch.d_comp.device, batch.nblk
+    comp = batch.d_comp.view(nblk, SLOT)
+    dec = batch.d_dec.view(nblk, BLOCK)
+    pos = torch.arange(SLOT, dtype=torch.int32, device=dev)
+    weight = pos % 251 + 1
+
+    def streams(rows):  # the compressed bytes of rows as int32, zero beyond each stream's length
+        return comp[rows].to(torch.int32) * (pos < batch.comp_len[rows, None])
+
+    csum = torch.empty(nblk, dtype=torch.int64, device=dev)
+    dsum = torch.empty(nblk, dtype=torch.int64, device=dev)
+    for lo in range(0, nblk, chunk):
+        rows = slice(lo, min(lo + chunk, nblk))
+        csum[rows] = (streams(rows) * weight).sum(1, dtype=torch.int64)
+        dsum[rows] = (dec[rows].to(torch.int32) * weight[:BLOCK]).sum(1, dtype=torch.int64)
+    sample = np.sort(np.random.default_rng(0x5EED).choice(nblk, min(DUMP_SAMPLE, nblk), replace=False))
+    rows = torch.from_numpy(sample).to(dev)
+    arrays = {"comp_len": batch.comp_len.double(), "dec_len": batch.dec_len.double(),
+              "status": batch.status.double(), "comp_checksum": csum.double(), "dec_checksum": dsum.double(),
+              "sample_blocks": rows.double(), "comp_sample": streams(rows).float(), "dec_sample": dec[rows].float()}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def timed_steps(step, steps, warmup, world, dist, dev):
     # dist is None unless a process group is up (world > 1, or SM_BENCH_DIST=1)
     """W untimed steps, then K steps between barrier + synchronize on both sides; max over ranks."""
@@ -536,12 +576,19 @@ def main():
     ap.add_argument("--steps", type=int, default=100)  # ~0.6 s timed on the headline: long enough for a busy sampler
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--blocks", type=int, default=10000)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed headline step computed as "
+                                                          "DIR/<name>.npy (rank 0; see dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: per-kernel "
+                                                        "rooflines, reference mode, configs 4 and 5, the CPU baseline")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-large", action="store_true", help="skip the config-5 (644 MiB stream) workload")
     ap.add_argument("--no-random", action="store_true", help="skip the config-4 (random blocks) workload")
-    ap.add_argument("--extras", action="store_true", help="also time dense/reference modes, validation and the "
-                                                          "PCIe-inclusive single-stream entry points")
+    ap.add_argument("--extras", action="store_true", help="--full, and also time dense/reference modes, validation "
+                                                          "and the PCIe-inclusive single-stream entry points")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    args.full |= args.extras
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))
@@ -595,51 +642,61 @@ def main():
         batch.uncompress(sm)
 
     elapsed = timed_steps(step, args.steps, args.warmup, world, dist, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(batch, args.dump_outputs)
     headline_sizes = batch.comp_len.clone()
     comp_bytes = batch.comp_bytes()
-    DECODE_STREAM_BYTES["uncompress"] = comp_bytes
     in_bytes = batch.in_bytes
-    t_c = kernel_ms(lambda: batch.compress(sm), reps)
-    t_d = kernel_ms(lambda: batch.uncompress(sm), reps)
+    value = 2.0 * in_bytes * args.steps * world / elapsed / 1e9
     ok = batch.verify()
     ok_all &= ok
-    c_bytes = in_bytes + comp_bytes + 4 * args.blocks
-    d_bytes = comp_bytes + in_bytes
-    kern = {"compress_fast": (t_c, c_bytes), "uncompress": (t_d, d_bytes)}
-    dom = max(kern, key=lambda k: kern[k][0])
-    value = 2.0 * in_bytes * args.steps * world / elapsed / 1e9
-
-    # byte-identical (reference) mode on the same batch: Snappy.jl's own bytes (tests/ check
-    # them against the oracle block for block); reported beside the headline, not in it
-    t_ref = kernel_ms(lambda: batch.compress(sm, "reference"), 3)
-    ref_comp = batch.comp_bytes()
-    DECODE_STREAM_BYTES["uncompress_reference_streams"] = ref_comp
-    # config 3's other half: the decode of the reference-mode (Snappy.jl's own)
-    # streams of the same blocks, with its own roofline
-    t_rd = kernel_ms(lambda: batch.uncompress(sm), reps)
-    ref_mode = {"workload": "the headline's %d text blocks, byte-identical (reference) mode compress, and the "
-                            "uncompress of those streams (config 3's reference-mode inputs)" % args.blocks,
-                "compress_GBps": round(in_bytes / (t_ref * 1e-3) / 1e9, 3),
-                "ratio": round(ref_comp / in_bytes, 5),
-                "roundtrip_bit_exact": batch.verify()}
-    ok_all &= ref_mode["roundtrip_bit_exact"]
-    ref_streams = {"workload": "config 3: uncompress of the %d reference-mode (Snappy.jl byte-identical) streams of "
-                               "the headline blocks, the stream set the oracle produces" % args.blocks,
-                   "reference_streams_uncompress_GBps": round(in_bytes / (t_rd * 1e-3) / 1e9, 3),
-                   "ratio": round(ref_comp / in_bytes, 5),
-                   "roundtrip_bit_exact": ref_mode["roundtrip_bit_exact"],
-                   "roofline": roofline("uncompress_reference_streams", ref_comp + in_bytes, t_rd)}
-    batch.compress(sm, "fast")
-
+    full = {}
     extras = {}
-    if args.extras:
-        extras.update(extra_modes(sm, batch, in_bytes))
+    if args.full:
+        DECODE_STREAM_BYTES["uncompress"] = comp_bytes
+        t_c = kernel_ms(lambda: batch.compress(sm), reps)
+        t_d = kernel_ms(lambda: batch.uncompress(sm), reps)
+        c_bytes = in_bytes + comp_bytes + 4 * args.blocks
+        d_bytes = comp_bytes + in_bytes
+        kern = {"compress_fast": (t_c, c_bytes), "uncompress": (t_d, d_bytes)}
+        dom = max(kern, key=lambda k: kern[k][0])
+
+        # byte-identical (reference) mode on the same batch: Snappy.jl's own bytes (tests/ check
+        # them against the oracle block for block); reported beside the headline, not in it
+        t_ref = kernel_ms(lambda: batch.compress(sm, "reference"), 3)
+        ref_comp = batch.comp_bytes()
+        DECODE_STREAM_BYTES["uncompress_reference_streams"] = ref_comp
+        # config 3's other half: the decode of the reference-mode (Snappy.jl's own)
+        # streams of the same blocks, with its own roofline
+        t_rd = kernel_ms(lambda: batch.uncompress(sm), reps)
+        ref_mode = {"workload": "the headline's %d text blocks, byte-identical (reference) mode compress, and the "
+                                "uncompress of those streams (config 3's reference-mode inputs)" % args.blocks,
+                    "compress_GBps": round(in_bytes / (t_ref * 1e-3) / 1e9, 3),
+                    "ratio": round(ref_comp / in_bytes, 5),
+                    "roundtrip_bit_exact": batch.verify()}
+        ok_all &= ref_mode["roundtrip_bit_exact"]
+        ref_streams = {"workload": "config 3: uncompress of the %d reference-mode (Snappy.jl byte-identical) streams "
+                                   "of the headline blocks, the stream set the oracle produces" % args.blocks,
+                       "reference_streams_uncompress_GBps": round(in_bytes / (t_rd * 1e-3) / 1e9, 3),
+                       "ratio": round(ref_comp / in_bytes, 5),
+                       "roundtrip_bit_exact": ref_mode["roundtrip_bit_exact"],
+                       "roofline": roofline("uncompress_reference_streams", ref_comp + in_bytes, t_rd)}
+        batch.compress(sm, "fast")
+        full = {"compress_GBps": round(in_bytes / (t_c * 1e-3) / 1e9, 3),
+                "uncompress_GBps": round(in_bytes / (t_d * 1e-3) / 1e9, 3),
+                "roofline": roofline(dom, kern[dom][1], kern[dom][0]),
+                "roofline_other": roofline(*[(k, v[1], v[0]) for k, v in kern.items() if k != dom][0]),
+                "reference_mode": ref_mode,
+                "reference_streams_uncompress_GBps": ref_streams["reference_streams_uncompress_GBps"],
+                "reference_streams": ref_streams}
+        if args.extras:
+            extras.update(extra_modes(sm, batch, in_bytes))
     del batch
     torch.cuda.empty_cache()
 
     # ---- config 4: incompressible blocks ------------------------------------------------
     rnd = None
-    if not args.no_random:
+    if args.full and not args.no_random:
         rb = Batch(random_blocks(args.blocks, 0x5EED + 1 + rank), dev)
 
         def rstep():
@@ -670,7 +727,7 @@ def main():
     # ---- config 5: one 644 MiB stream, strong scaling --------------------------------------
     large = None
     big = None
-    if not args.no_large:
+    if args.full and not args.no_large:
         big = large_corpus()
         nfrag = (big.size + BLOCK - 1) // BLOCK
         lo, hi = dmod.shard_range(nfrag, rank, world)
@@ -750,7 +807,7 @@ def main():
         ok_all &= rccl["own_slice_matches"]
 
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         cpu = cpu_baseline(blocks_np)
 
     if rank == 0:
@@ -774,21 +831,13 @@ def main():
                 "block_bytes": BLOCK,
                 "parallelism": "dp%d (blocks sharded per rank, RCCL size all-gather)" % world,
             },
-            "compress_GBps": round(in_bytes / (t_c * 1e-3) / 1e9, 3),
-            "uncompress_GBps": round(in_bytes / (t_d * 1e-3) / 1e9, 3),
             "ratio": round(comp_bytes / in_bytes, 5),
             "roundtrip_bit_exact": ok,
             "all_roundtrips_bit_exact": ok_all,
-            "roofline": roofline(dom, kern[dom][1], kern[dom][0]),
-            "roofline_other": roofline(*[(k, v[1], v[0]) for k, v in kern.items() if k != dom][0]),
             "rccl": rccl,
-            "random": rnd,
-            "large": large,
-            "reference_mode": ref_mode,
-            "reference_streams_uncompress_GBps": ref_streams["reference_streams_uncompress_GBps"],
-            "reference_streams": ref_streams,
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            line.update(full, random=rnd, large=large, cpu_baseline=cpu)
         line.update(extras)
         sys.stdout.flush()
         os.write(out_fd, (json.dumps(line) + "\n").encode())

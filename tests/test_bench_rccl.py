@@ -21,7 +21,7 @@ def test_bench_rccl_one_rank(gpu_available):
     env["SM_BENCH_DIST"] = "1"
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-           "--no-cpu", "--no-random", "--blocks", "2000"]
+           "--full", "--no-cpu", "--no-random", "--blocks", "2000"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -10,5 +10,5 @@ for op in compress_fast uncompress; do
 done
 timeout -k 10 120 python3 tools/kbench.py --op compress_fragments --reps 10 >> $O/t.log 2>&1 || { echo kbench failed; tail $O/t.log; exit 1; }
 grep -v amdgpu.ids $O/t.log
-timeout -k 10 300 python3 bench.py > $O/bench.json 2> $O/bench.err || { echo bench failed; tail $O/bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { echo bench failed; tail $O/bench.err; exit 1; }
 cat $O/bench.json | head -c 3000
