@@ -148,9 +148,13 @@ sm_status sm_compress_fragments_device(sm_ctx* ctx, const uint8_t* d_in, const u
  *                      starting at its first fragment.
  * d_dst has room for dst_capacity bytes.  d_local_off (optional, nfrag u64) receives
  * d_dst_off[b] - base (the fragments' offsets in d_dst, for sm_uncompress_fragments_device).
- * A length that is an error mark (>= SM_OUT_LEN_ERROR), or a fragment that would end past
- * dst_capacity, copies nothing and sets *d_status = SM_ERR_DEVICE (optional; never cleared: zero
- * it first).  Asynchronous on `stream`. */
+ * A length that is an error mark (>= SM_OUT_LEN_ERROR), a fragment that would end past
+ * dst_capacity, or with write_header a fragment that would start inside the header
+ * (d_dst_off[b] < the length of varint(total_len)), copies nothing and sets
+ * *d_status = SM_ERR_DEVICE (optional; never cleared: zero it first); the other fragments and the
+ * header are written as usual.  d_src may have any alignment (16-byte-aligned fragments copy
+ * faster), and reads stay inside the 16-byte-aligned granules that hold fragment bytes: no byte
+ * of a granule lying wholly before or behind a fragment is read.  Asynchronous on `stream`. */
 sm_status sm_place_fragments_device(sm_ctx* ctx, const uint8_t* d_src, const uint64_t* d_src_off,
                                     const uint32_t* d_len, uint32_t nfrag, const uint64_t* d_dst_off,
                                     uint64_t total_len, int write_header, uint8_t* d_dst, uint64_t dst_capacity,

@@ -485,7 +485,9 @@ def place_fragments_device(d_src, d_src_off, d_len, d_dst_off, d_dst, total_len,
     write_header (d_dst is the stream from byte 0; varint(total_len) is written there) or
     d_dst_off[0] (d_dst is this shard's byte range).  d_local_off (int64, optional) receives the
     fragments' offsets in d_dst; d_status (int32[1], optional, zeroed by the caller) turns
-    SM_ERR_DEVICE on an error-mark length or a fragment past d_dst's end."""
+    SM_ERR_DEVICE on an error-mark length, a fragment past d_dst's end or, with write_header, a
+    fragment that would start inside the header (d_dst_off[b] < len(varint(total_len))); such a
+    fragment is not copied, the others and the header are."""
     dev = d_dst.device.index if device is None else device
     nfrag = d_len.numel()
     nul = ctypes.c_void_p(0)

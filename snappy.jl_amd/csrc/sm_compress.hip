@@ -432,7 +432,9 @@ __device__ __attribute__((always_inline)) inline void gather_unit(const uint8_t*
   const uint32_t stride = blockDim.x * ny;
   for (uint32_t u = u0 + y * blockDim.x + threadIdx.x; u < u1; u += stride) {
     const uint32_t j = 16 * u - ad;
-    const uint4 A = s16[j >> 4], B = s16[(j >> 4) + 1];
+    // the second granule only when the unit straddles two (sb != 0: it then holds source byte 16u < n);
+    // for an aligned g it would lie wholly past the piece on its last unit
+    const uint4 A = s16[j >> 4], B = sb ? s16[(j >> 4) + 1] : make_uint4(0, 0, 0, 0);
     const uint32_t x[8] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w};
     uint32_t r5[5];
 #pragma unroll
@@ -548,8 +550,10 @@ __global__ __launch_bounds__(256) void k_gather_parts(const uint8_t* __restrict_
 // header), base = 0 with the header (dst is the stream from its first byte and varint(total) is
 // written there) or dst_off[0] without it (dst is the caller's byte range from its first
 // fragment).  loc_off[b] (optional) receives dst_off[b] - base.  A length that is an error mark,
-// or a fragment that would end past cap, copies nothing and sets *status = SM_ERR_DEVICE
-// (optional; never cleared here).  blockIdx.y strides the fragment's 16-byte units.
+// a fragment that would end past cap, or with the header a fragment that would start inside it
+// (dst_off[b] < varint_len(total): its bytes would race the header's), copies nothing and sets
+// *status = SM_ERR_DEVICE (optional; never cleared here).  blockIdx.y strides the fragment's
+// 16-byte units.
 __global__ __launch_bounds__(256) void k_place(const uint8_t* __restrict__ src, const uint64_t* src_off,
                                                const uint32_t* len, const uint64_t* dst_off, uint32_t nfrag,
                                                uint64_t total, int header, uint64_t cap, uint8_t* __restrict__ dst,
@@ -564,7 +568,7 @@ __global__ __launch_bounds__(256) void k_place(const uint8_t* __restrict__ src, 
   const uint64_t base = header ? 0ull : dst_off[0];
   const uint32_t n = len[b];
   const uint64_t at = dst_off[b] - base;  // (a mark earlier in the scan wraps this past cap)
-  const bool bad = n >= kOutLenError || at > cap || cap - at < n;
+  const bool bad = n >= kOutLenError || at > cap || cap - at < n || (header && at < varint_len((uint32_t)total));
   if (blockIdx.y == 0 && threadIdx.x == 0) {
     if (loc_off) loc_off[b] = at;
     if (bad && status) *status = kErrDevice;
