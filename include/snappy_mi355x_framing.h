@@ -1,0 +1,167 @@
+/*
+ * snappy_mi355x_framing.h -- C ABI of the Snappy framing format on the MI355X (gfx950),
+ * libsnappy_mi355x_framing.so: a companion of libsnappy_mi355x.so (snappy_mi355x.h), which it
+ * links by name and whose public batched device entry points it calls for the raw codec.
+ *
+ * The framing format (framing_format.txt of google/snappy; what .sz files, snzip and Go's
+ * snappy.Writer produce) is a sequence of chunks: one type byte, a 3-byte little-endian length
+ * of the data that follows, then the data.
+ *   0xff  stream identifier: length 6, data "sNaPpY".  The stream starts with it; it may occur
+ *         again (concatenated streams) and is then checked and skipped.
+ *   0x00  compressed data: a 4-byte LE masked CRC-32C of the UNCOMPRESSED bytes, then one raw
+ *         Snappy stream (varint + body) of at most 65536 uncompressed bytes.
+ *   0x01  uncompressed data: the same CRC field, then at most 65536 bytes.
+ *   0xfe  padding, 0x80..0xfd reserved skippable: the data is skipped.
+ *   0x02..0x7f reserved unskippable: an error.
+ * CRC-32C: reflected polynomial 0x82F63B78, init and final xor 0xffffffff; the stored value is
+ * masked: ((crc >> 15) | (crc << 17)) + 0xa282ead8 mod 2^32.
+ *
+ * Encoder rule (fixed, so the output is deterministic): the input is cut into 64 KiB blocks; a
+ * block becomes a 0x00 chunk if and only if its Snappy stream is strictly shorter than the
+ * block, else a 0x01 chunk; the empty input is the identifier alone.
+ *
+ * Statuses: the codes of snappy_mi355x.h plus SMF_ERR_* (48..53).  A corrupt Snappy payload
+ * keeps the raw decoder's SM_ERR_* code.  A decode's overall status is the first failing
+ * chunk's in stream order; the other chunks still decode and report SM_OK.
+ *
+ * Threading: an smf_ctx owns one sm_ctx (device, stream) and scratch.  The host-buffer entry
+ * points lock the ctx.  The *_device entry points launch on the caller's stream and use the
+ * ctx's scratch without a lock: one caller per ctx at a time, and calls on one ctx go to one
+ * stream (or are ordered by the caller), since consecutive calls reuse the scratch.
+ */
+#ifndef SNAPPY_MI355X_FRAMING_H_
+#define SNAPPY_MI355X_FRAMING_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "snappy_mi355x.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+enum {
+  SMF_ERR_NO_IDENTIFIER = 48,   /* the stream does not start with a 0xff chunk (or is empty) */
+  SMF_ERR_BAD_IDENTIFIER = 49,  /* a 0xff chunk whose length is not 6 or whose data is not "sNaPpY" */
+  SMF_ERR_RESERVED_CHUNK = 50,  /* an unskippable reserved chunk type, 0x02..0x7f */
+  SMF_ERR_TRUNCATED = 51,       /* a chunk header or its data runs past the end of the stream, or a
+                                   data chunk has no room for its CRC (length < 4) */
+  SMF_ERR_CHUNK_TOO_LARGE = 52, /* a data chunk of more than 65536 uncompressed bytes */
+  SMF_ERR_CRC = 53              /* the chunk's bytes do not have the stored CRC-32C */
+};
+
+#define SMF_CHUNK_COMPRESSED 0x00u
+#define SMF_CHUNK_UNCOMPRESSED 0x01u
+#define SMF_IDENTIFIER_LENGTH 10u
+
+typedef struct smf_ctx smf_ctx;
+
+/* The index of a framed stream: one entry per DATA chunk (0x00 / 0x01), in stream order.  Five
+ * parallel arrays of at least max_chunks entries, all in host memory (smf_index) or all in device
+ * memory (the *_device calls). */
+typedef struct smf_chunks {
+  uint8_t* type;      /* SMF_CHUNK_COMPRESSED or SMF_CHUNK_UNCOMPRESSED */
+  uint64_t* pay_off;  /* offset in the stream of the payload (the bytes behind the CRC field) */
+  uint32_t* pay_len;  /* its length: the chunk length - 4 */
+  uint32_t* crc;      /* the stored (masked) CRC */
+  uint32_t* ulen;     /* declared uncompressed length: the payload's varint (0x00), pay_len (0x01) */
+} smf_chunks;
+
+/* What a walk found.  status: SM_OK, the first structural error (the walk stops there; nchunks
+ * and total_length then cover the data chunks before it), or SM_BUFFER_TOO_SMALL when the stream
+ * is well formed but has more than max_chunks data chunks (nchunks = the count needed; the first
+ * max_chunks entries are filled). */
+typedef struct smf_summary {
+  uint64_t total_length; /* the sum of the declared uncompressed lengths */
+  uint32_t nchunks;      /* data chunks */
+  int32_t status;
+} smf_summary;
+
+/* Message for a status code: the SMF_ERR_* texts, else the companion library's message. */
+const char* smf_status_message(sm_status st);
+/* library build identification ("snappy_mi355x_framing gfx950 <source hash>") */
+const char* smf_version(void);
+
+/* ---- format helpers (host, no device needed) ------------------------------------ */
+/* The largest framed stream of an n-byte input under the encoder rule:
+ * 10 + 8 * ceil(n / 65536) + n. */
+size_t smf_max_framed_length(size_t n);
+/* CRC-32C of a host buffer (unmasked), and the mask. */
+uint32_t smf_crc32c(const void* buf, size_t n);
+uint32_t smf_crc32c_mask(uint32_t crc);
+/* Walks a framed stream in HOST memory.  chunks may be NULL (max_chunks is then ignored: count
+ * and total only).  Returns summary->status (SM_ERR_ARGUMENT for a NULL summary or buffer). */
+sm_status smf_index(const uint8_t* buf, size_t n, const smf_chunks* chunks, uint32_t max_chunks,
+                    smf_summary* summary);
+/* The stream's total uncompressed length, from its chunk headers alone (no CRC or payload check). */
+sm_status smf_uncompressed_length(const uint8_t* buf, size_t n, size_t* result);
+
+/* ---- context ---------------------------------------------------------------------- */
+/* NULL without a usable device. */
+smf_ctx* smf_ctx_create(int device);
+void smf_ctx_destroy(smf_ctx* ctx);
+
+/* ---- device memory (the GPU hot path) ------------------------------------------------ */
+/* Block b: d_crc[b] = CRC-32C of d_in[d_off[b] .. +d_len[b]), masked when masked != 0.  Any
+ * length (0 gives 0, masked 0xa282ead8) and any source alignment; reads stay inside the 16-byte-
+ * aligned granules that hold the block's bytes, and of a granule the block only partly covers only
+ * the block's own bytes are read.  Asynchronous on `stream`. */
+sm_status smf_crc32c_batch_device(smf_ctx* ctx, const uint8_t* d_in, const uint64_t* d_off, const uint32_t* d_len,
+                                  uint32_t nblk, uint32_t* d_crc, int masked, void* stream);
+
+/* Frames d_in[0, n) into d_out: the identifier, then one chunk per 64 KiB block (encoder rule
+ * above).  *d_out_len (device, u64) = the stream's length; *d_status (device) = SM_OK, or
+ * SM_ERR_DEVICE when the compressor returned an error mark for a block (nothing is packed for that
+ * block; never expected).  out_capacity < smf_max_framed_length(n) returns SM_BUFFER_TOO_SMALL
+ * and launches nothing.  mode: SM_MODE_*.  Asynchronous on `stream`, except when the ctx's
+ * scratch has to grow (first call, or a larger n than any before: hipMalloc). */
+sm_status smf_compress_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t out_capacity,
+                              uint64_t* d_out_len, int32_t* d_status, int mode, void* stream);
+
+/* smf_index for a stream that lives in DEVICE memory: one wave walks the chunk chain (serial: a
+ * chunk's position is known only from its predecessor's length).  d_chunks points to a HOST
+ * struct of DEVICE arrays (NULL: count only); *d_summary is in device memory.  Asynchronous. */
+sm_status smf_index_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, const smf_chunks* d_chunks,
+                           uint32_t max_chunks, smf_summary* d_summary, void* stream);
+/* *d_len (device, u64) = the total uncompressed length, *d_status (device) = the walk's status. */
+sm_status smf_uncompressed_length_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, uint64_t* d_len,
+                                         int32_t* d_status, void* stream);
+
+/* Decodes the nchunks data chunks of an indexed stream (d_chunks: a HOST struct of DEVICE arrays,
+ * as smf_index_device fills them) into d_out, chunk c at the sum of the declared lengths before
+ * it: 0x00 chunks by the raw batched decoder with capacity = the declared length, 0x01 chunks by a
+ * copy kernel; then the CRC of every chunk's output is recomputed and compared.
+ * d_chunk_status[c] (device, nchunks) = SM_OK, the raw decoder's SM_ERR_* code, SMF_ERR_CRC,
+ * SMF_ERR_CHUNK_TOO_LARGE (a declared length over 65536, or a 0x01 chunk whose lengths differ), or
+ * SM_BUFFER_TOO_SMALL (the chunk would end past out_capacity; it is not decoded).
+ * *d_status (device) = the first failing chunk's status in stream order, else SM_OK;
+ * *d_out_len (device, u64) = the sum of the declared lengths (the size needed).
+ * Asynchronous on `stream`, except when the ctx's scratch has to grow. */
+sm_status smf_uncompress_chunks_device(smf_ctx* ctx, const uint8_t* d_in, const smf_chunks* d_chunks,
+                                       uint32_t nchunks, uint8_t* d_out, uint64_t out_capacity,
+                                       int32_t* d_chunk_status, uint64_t* d_out_len, int32_t* d_status, void* stream);
+
+/* Index plus decode of a stream in device memory.  ONE host synchronisation of `stream`, between
+ * the index walk and the decode (the host needs the chunk count to size the launches); a second
+ * one when the stream has more chunks than the ctx's index scratch held (it grows, and the walk
+ * runs again).  Returns, and stores in *d_status, the walk's structural error, or
+ * SM_BUFFER_TOO_SMALL when out_capacity is less than the total length (*d_out_len = the size
+ * needed; nothing is decoded); otherwise returns SM_OK with the decode queued on `stream`, and
+ * *d_status / *d_out_len are those of smf_uncompress_chunks_device. */
+sm_status smf_uncompress_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t out_capacity,
+                                uint64_t* d_out_len, int32_t* d_status, void* stream);
+
+/* ---- host memory (H2D + the device path + D2H, synchronous) ------------------------- */
+/* *framed_length: in = capacity (>= smf_max_framed_length(n)), out = bytes written. */
+sm_status smf_compress(smf_ctx* ctx, const uint8_t* input, size_t n, uint8_t* framed, size_t* framed_length, int mode);
+/* The stream is indexed on the host, decoded and CRC-checked on the device.
+ * *length: in = capacity, out = bytes written (with SM_BUFFER_TOO_SMALL: the size needed). */
+sm_status smf_uncompress(smf_ctx* ctx, const uint8_t* framed, size_t n, uint8_t* output, size_t* length);
+/* The status smf_uncompress would return with enough room (decodes into device scratch). */
+sm_status smf_validate(smf_ctx* ctx, const uint8_t* framed, size_t n);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* SNAPPY_MI355X_FRAMING_H_ */

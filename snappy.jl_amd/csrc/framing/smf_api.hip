@@ -1,0 +1,366 @@
+// smf_api.hip -- C ABI of the framing format (include/snappy_mi355x_framing.h) over the raw
+// codec's public batched device calls (libsnappy_mi355x.so, linked by name) and the kernels of
+// smf_kernels.hip.  The host-only entry points live in smf_host.cpp.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "smf_format.h"
+#include "smf_internal.h"
+
+#ifndef SMF_VERSION_STR
+#define SMF_VERSION_STR "dev"
+#endif
+
+namespace {
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  hipError_t ensure(size_t n) {  // (growing frees the old buffer: hipFree waits for the device)
+    if (n <= cap) return hipSuccess;
+    release();
+    const size_t want = n < 4096 ? 4096 : n;
+    const hipError_t e = hipMalloc(&p, want);
+    if (e == hipSuccess) cap = want;
+    else p = nullptr;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    (void)hipSetDevice(dev);
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+// consecutive arrays of one scratch buffer, the widest element types first
+struct Carve {
+  uint8_t* p;
+  template <typename T>
+  T* take(size_t n) {
+    T* r = reinterpret_cast<T*>(p);
+    p += (n * sizeof(T) + 15) / 16 * 16;
+    return r;
+  }
+};
+
+constexpr uint64_t kSlotPitch = 76496;  // sm_max_compressed_length(65536) = 76490, 16-byte aligned
+constexpr size_t kCompressMeta = 8 + 8 + 8 + 4 + 4 + 4 + 1;      // scratch bytes per block (+ padding)
+constexpr size_t kDecodeMeta = 8 + 4 + 4 + 4 + 4 + 4 + 4;        // per chunk
+constexpr size_t kIndexMeta = 8 + 4 + 4 + 4 + 4 + 1;             // per index entry (+ chunk status)
+inline size_t meta_bytes(size_t per, size_t n) { return per * n + 16 * 8; }
+
+}  // namespace
+
+struct smf_ctx {
+  sm_ctx* sm = nullptr;
+  int device = 0;
+  hipStream_t stream = nullptr;  // the sm_ctx's: the host-buffer calls run on it
+  DevBuf lut;                    // smf::CrcLut
+  DevBuf cmeta, slots;           // compress: per-block arrays, the raw compressor's output slots
+  DevBuf dmeta;                  // decode: per-chunk arrays
+  DevBuf idx;                    // a stream's index (smf_uncompress_device, smf_uncompress)
+  DevBuf io_in, io_out, res;     // the host-buffer calls' staging; small results
+  std::mutex mu;                 // serialises the host-buffer entry points
+};
+
+#define SMF_CHECK(x)                               \
+  do {                                             \
+    if ((x) != hipSuccess) return SM_ERR_DEVICE;   \
+  } while (0)
+#define SMF_PASS(x)                \
+  do {                             \
+    const sm_status st_ = (x);     \
+    if (st_ != SM_OK) return st_;  \
+  } while (0)
+
+namespace {
+
+// the index arrays of up to n chunks in ctx->idx, and the per-chunk status behind them
+sm_status index_scratch(smf_ctx* ctx, size_t n, smf_chunks& ch, int32_t*& chunk_status) {
+  SMF_CHECK(ctx->idx.ensure(meta_bytes(kIndexMeta, n)));
+  Carve c{(uint8_t*)ctx->idx.p};
+  ch.pay_off = c.take<uint64_t>(n);
+  ch.pay_len = c.take<uint32_t>(n);
+  ch.crc = c.take<uint32_t>(n);
+  ch.ulen = c.take<uint32_t>(n);
+  chunk_status = c.take<int32_t>(n);
+  ch.type = c.take<uint8_t>(n);
+  return SM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* smf_status_message(sm_status st) {
+  const char* m = smf::host_message(st);
+  return m ? m : sm_status_message(st);
+}
+
+const char* smf_version(void) { return "snappy_mi355x_framing gfx950 " SMF_VERSION_STR; }
+
+smf_ctx* smf_ctx_create(int device) {
+  sm_ctx* sm = sm_ctx_create(device);
+  if (!sm) return nullptr;
+  smf_ctx* ctx = new (std::nothrow) smf_ctx();
+  smf::CrcLut* lut = new (std::nothrow) smf::CrcLut();
+  if (!ctx || !lut) {
+    delete ctx;
+    delete lut;
+    sm_ctx_destroy(sm);
+    return nullptr;
+  }
+  ctx->sm = sm;
+  ctx->device = device;
+  ctx->stream = (hipStream_t)sm_ctx_stream(sm);
+  smf::build_crc_lut(lut);
+  bool ok;
+  {
+    DeviceGuard g(device);
+    ok = ctx->lut.ensure(sizeof(smf::CrcLut)) == hipSuccess && ctx->res.ensure(4096) == hipSuccess &&
+         hipMemcpy(ctx->lut.p, lut, sizeof(smf::CrcLut), hipMemcpyHostToDevice) == hipSuccess;
+  }
+  delete lut;
+  if (!ok) {
+    smf_ctx_destroy(ctx);
+    return nullptr;
+  }
+  return ctx;
+}
+
+void smf_ctx_destroy(smf_ctx* ctx) {
+  if (!ctx) return;
+  {
+    DeviceGuard g(ctx->device);
+    (void)hipDeviceSynchronize();  // (the *_device calls ran on the callers' streams)
+    for (DevBuf* b : {&ctx->lut, &ctx->cmeta, &ctx->slots, &ctx->dmeta, &ctx->idx, &ctx->io_in, &ctx->io_out, &ctx->res})
+      b->release();
+  }
+  sm_ctx_destroy(ctx->sm);
+  delete ctx;
+}
+
+sm_status smf_crc32c_batch_device(smf_ctx* ctx, const uint8_t* d_in, const uint64_t* d_off, const uint32_t* d_len,
+                                  uint32_t nblk, uint32_t* d_crc, int masked, void* stream) {
+  if (!ctx) return SM_ERR_ARGUMENT;
+  if (nblk == 0) return SM_OK;
+  if (!d_in || !d_off || !d_len || !d_crc) return SM_ERR_ARGUMENT;
+  DeviceGuard g(ctx->device);
+  SMF_CHECK(smf::launch_crc32c(d_in, d_off, d_len, nblk, d_crc, masked ? 1 : 0, (const smf::CrcLut*)ctx->lut.p,
+                               (hipStream_t)stream));
+  return SM_OK;
+}
+
+sm_status smf_compress_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t out_capacity,
+                              uint64_t* d_out_len, int32_t* d_status, int mode, void* stream) {
+  if (!ctx || !d_out || !d_out_len || !d_status || (n && !d_in)) return SM_ERR_ARGUMENT;
+  if (mode != SM_MODE_REFERENCE && mode != SM_MODE_FAST && mode != SM_MODE_FAST_DENSE) return SM_ERR_ARGUMENT;
+  const uint64_t nblk64 = (n + smf::kBlock - 1) / smf::kBlock;
+  if (nblk64 > 0x7fffffffull) return SM_ERR_INPUT_TOO_LARGE;
+  if (out_capacity < smf_max_framed_length(n)) return SM_BUFFER_TOO_SMALL;
+  const uint32_t nblk = (uint32_t)nblk64;
+  hipStream_t s = (hipStream_t)stream;
+  DeviceGuard g(ctx->device);
+  SMF_CHECK(ctx->cmeta.ensure(meta_bytes(kCompressMeta, nblk)));
+  SMF_CHECK(ctx->slots.ensure((size_t)nblk * kSlotPitch));
+  Carve c{(uint8_t*)ctx->cmeta.p};
+  uint64_t* in_off = c.take<uint64_t>(nblk);
+  uint64_t* slot_off = c.take<uint64_t>(nblk);
+  uint64_t* dst_off = c.take<uint64_t>(nblk);
+  uint32_t* in_len = c.take<uint32_t>(nblk);
+  uint32_t* comp_len = c.take<uint32_t>(nblk);
+  uint32_t* crc = c.take<uint32_t>(nblk);
+  uint8_t* type = c.take<uint8_t>(nblk);
+  uint8_t* slots = (uint8_t*)ctx->slots.p;
+  SMF_CHECK(smf::launch_frame_compress_plan(n, nblk, kSlotPitch, in_off, in_len, slot_off, s));
+  SMF_PASS(sm_compress_batch_device(ctx->sm, d_in, in_off, in_len, nblk, slots, slot_off, comp_len, mode, stream));
+  SMF_CHECK(smf::launch_crc32c(d_in, in_off, in_len, nblk, crc, 1, (const smf::CrcLut*)ctx->lut.p, s));
+  const smf::PackArgs a{d_in, in_off, in_len, slots, slot_off, comp_len, crc, type, dst_off, nblk, d_out};
+  SMF_CHECK(smf::launch_frame_pack(a, d_out_len, d_status, s));
+  return SM_OK;
+}
+
+sm_status smf_index_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, const smf_chunks* d_chunks,
+                           uint32_t max_chunks, smf_summary* d_summary, void* stream) {
+  if (!ctx || !d_summary || (n && !d_in)) return SM_ERR_ARGUMENT;
+  smf_chunks none{nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (d_chunks && max_chunks == 0) d_chunks = &none;  // (nothing is stored; more than 0 chunks is still too small)
+  if (d_chunks && max_chunks &&
+      (!d_chunks->type || !d_chunks->pay_off || !d_chunks->pay_len || !d_chunks->crc || !d_chunks->ulen))
+    return SM_ERR_ARGUMENT;
+  DeviceGuard g(ctx->device);
+  SMF_CHECK(smf::launch_frame_index(d_in, n, d_chunks, max_chunks, d_summary, (hipStream_t)stream));
+  return SM_OK;
+}
+
+sm_status smf_uncompressed_length_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, uint64_t* d_len,
+                                         int32_t* d_status, void* stream) {
+  if (!ctx || !d_len || !d_status || (n && !d_in)) return SM_ERR_ARGUMENT;
+  DeviceGuard g(ctx->device);
+  smf_summary* sum = (smf_summary*)ctx->res.p;
+  SMF_CHECK(smf::launch_frame_index(d_in, n, nullptr, 0, sum, (hipStream_t)stream));
+  SMF_CHECK(smf::launch_frame_result(d_len, 0, sum, d_status, 0, (hipStream_t)stream));
+  return SM_OK;
+}
+
+sm_status smf_uncompress_chunks_device(smf_ctx* ctx, const uint8_t* d_in, const smf_chunks* d_chunks,
+                                       uint32_t nchunks, uint8_t* d_out, uint64_t out_capacity,
+                                       int32_t* d_chunk_status, uint64_t* d_out_len, int32_t* d_status, void* stream) {
+  if (!ctx || !d_out_len || !d_status) return SM_ERR_ARGUMENT;
+  smf_chunks ch{nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (nchunks) {
+    if (!d_in || !d_out || !d_chunk_status || !d_chunks) return SM_ERR_ARGUMENT;
+    ch = *d_chunks;
+    if (!ch.type || !ch.pay_off || !ch.pay_len || !ch.crc || !ch.ulen) return SM_ERR_ARGUMENT;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  DeviceGuard g(ctx->device);
+  SMF_CHECK(ctx->dmeta.ensure(meta_bytes(kDecodeMeta, nchunks)));
+  Carve c{(uint8_t*)ctx->dmeta.p};
+  uint64_t* out_off = c.take<uint64_t>(nchunks);
+  uint32_t* cap = c.take<uint32_t>(nchunks);
+  uint32_t* dec_len = c.take<uint32_t>(nchunks);
+  int32_t* pre = c.take<int32_t>(nchunks);
+  uint32_t* dec_out_len = c.take<uint32_t>(nchunks);
+  int32_t* dec_status = c.take<int32_t>(nchunks);
+  uint32_t* crc_out = c.take<uint32_t>(nchunks);
+  SMF_CHECK(smf::launch_frame_plan(ch, nchunks, out_capacity, out_off, cap, dec_len, pre, d_out_len, s));
+  SMF_PASS(sm_uncompress_batch_device(ctx->sm, d_in, ch.pay_off, dec_len, nchunks, d_out, out_off, cap, dec_out_len,
+                                      dec_status, stream));
+  SMF_CHECK(smf::launch_frame_copy(d_in, ch, nchunks, out_off, cap, d_out, s));
+  SMF_CHECK(smf::launch_crc32c(d_out, out_off, cap, nchunks, crc_out, 1, (const smf::CrcLut*)ctx->lut.p, s));
+  SMF_CHECK(smf::launch_frame_verify(ch, nchunks, pre, dec_status, crc_out, d_chunk_status, d_status, s));
+  return SM_OK;
+}
+
+sm_status smf_uncompress_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t out_capacity,
+                                uint64_t* d_out_len, int32_t* d_status, void* stream) {
+  if (!ctx || !d_out_len || !d_status || (n && !d_in)) return SM_ERR_ARGUMENT;
+  hipStream_t s = (hipStream_t)stream;
+  DeviceGuard g(ctx->device);
+  smf_summary* d_sum = (smf_summary*)ctx->res.p;
+  smf_summary sum;
+  smf_chunks ch;
+  int32_t* chunk_status = nullptr;
+  // entries for a stream whose chunks average 1 KiB or more; a stream of smaller chunks walks twice
+  size_t entries = std::max<size_t>(ctx->idx.cap / (kIndexMeta + 1), n / 1024 + 64);
+  entries = std::min<size_t>(entries, 0xffffffffu);
+  for (int pass = 0;; ++pass) {
+    SMF_PASS(index_scratch(ctx, entries, ch, chunk_status));
+    SMF_CHECK(smf::launch_frame_index(d_in, n, &ch, (uint32_t)entries, d_sum, s));
+    SMF_CHECK(hipMemcpyAsync(&sum, d_sum, sizeof(sum), hipMemcpyDeviceToHost, s));
+    SMF_CHECK(hipStreamSynchronize(s));  // the documented synchronisation
+    if (sum.status != SM_BUFFER_TOO_SMALL || pass) break;
+    entries = sum.nchunks;
+  }
+  sm_status st = sum.status;
+  if (st == SM_OK && sum.total_length > out_capacity) st = SM_BUFFER_TOO_SMALL;
+  if (st != SM_OK) {
+    SMF_CHECK(smf::launch_frame_result(d_out_len, sum.total_length, nullptr, d_status, st, s));
+    return st;
+  }
+  if (sum.nchunks && !d_out) return SM_ERR_ARGUMENT;
+  return smf_uncompress_chunks_device(ctx, d_in, &ch, sum.nchunks, d_out, out_capacity, chunk_status, d_out_len, d_status,
+                                      stream);
+}
+
+sm_status smf_compress(smf_ctx* ctx, const uint8_t* input, size_t n, uint8_t* framed, size_t* framed_length, int mode) {
+  if (!ctx || !framed || !framed_length || (n && !input)) return SM_ERR_ARGUMENT;
+  const size_t need = smf_max_framed_length(n);
+  if (*framed_length < need) return SM_BUFFER_TOO_SMALL;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  SMF_CHECK(ctx->io_in.ensure(n));
+  SMF_CHECK(ctx->io_out.ensure(need));
+  if (n) SMF_CHECK(hipMemcpyAsync(ctx->io_in.p, input, n, hipMemcpyHostToDevice, s));
+  uint64_t* d_len = (uint64_t*)((uint8_t*)ctx->res.p + 64);
+  int32_t* d_st = (int32_t*)((uint8_t*)ctx->res.p + 72);
+  SMF_PASS(smf_compress_device(ctx, (const uint8_t*)ctx->io_in.p, n, (uint8_t*)ctx->io_out.p, need, d_len, d_st, mode, s));
+  struct {
+    uint64_t len;
+    int32_t st, pad;
+  } r;
+  SMF_CHECK(hipMemcpyAsync(&r, d_len, 16, hipMemcpyDeviceToHost, s));
+  SMF_CHECK(hipStreamSynchronize(s));
+  if (r.st != SM_OK) return r.st;
+  if (r.len > need) return SM_ERR_DEVICE;
+  SMF_CHECK(hipMemcpy(framed, ctx->io_out.p, r.len, hipMemcpyDeviceToHost));
+  *framed_length = (size_t)r.len;
+  return SM_OK;
+}
+
+// host index, upload, decode; output == null validates only (the decode goes to scratch)
+static sm_status uncompress_host(smf_ctx* ctx, const uint8_t* framed, size_t n, uint8_t* output, size_t* length) {
+  smf_summary sum;
+  SMF_PASS(smf_index(framed, n, nullptr, 0, &sum));
+  if (length && sum.total_length > *length) {
+    *length = (size_t)sum.total_length;
+    return SM_BUFFER_TOO_SMALL;
+  }
+  const uint32_t nc = sum.nchunks;
+  std::vector<uint8_t> type(nc);
+  std::vector<uint64_t> pay_off(nc);
+  std::vector<uint32_t> pay_len(nc), crc(nc), ulen(nc);
+  const smf_chunks h{type.data(), pay_off.data(), pay_len.data(), crc.data(), ulen.data()};
+  SMF_PASS(smf_index(framed, n, &h, nc, &sum));
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  smf_chunks d;
+  int32_t* chunk_status = nullptr;
+  SMF_PASS(index_scratch(ctx, nc, d, chunk_status));
+  SMF_CHECK(ctx->io_in.ensure(n));
+  SMF_CHECK(ctx->io_out.ensure((size_t)sum.total_length));
+  SMF_CHECK(hipMemcpyAsync(ctx->io_in.p, framed, n, hipMemcpyHostToDevice, s));
+  if (nc) {
+    SMF_CHECK(hipMemcpyAsync(d.type, h.type, nc, hipMemcpyHostToDevice, s));
+    SMF_CHECK(hipMemcpyAsync(d.pay_off, h.pay_off, 8 * (size_t)nc, hipMemcpyHostToDevice, s));
+    SMF_CHECK(hipMemcpyAsync(d.pay_len, h.pay_len, 4 * (size_t)nc, hipMemcpyHostToDevice, s));
+    SMF_CHECK(hipMemcpyAsync(d.crc, h.crc, 4 * (size_t)nc, hipMemcpyHostToDevice, s));
+    SMF_CHECK(hipMemcpyAsync(d.ulen, h.ulen, 4 * (size_t)nc, hipMemcpyHostToDevice, s));
+  }
+  uint64_t* d_len = (uint64_t*)((uint8_t*)ctx->res.p + 64);
+  int32_t* d_st = (int32_t*)((uint8_t*)ctx->res.p + 72);
+  SMF_PASS(smf_uncompress_chunks_device(ctx, (const uint8_t*)ctx->io_in.p, &d, nc, (uint8_t*)ctx->io_out.p,
+                                        sum.total_length, chunk_status, d_len, d_st, s));
+  struct {
+    uint64_t len;
+    int32_t st, pad;
+  } r;
+  SMF_CHECK(hipMemcpyAsync(&r, d_len, 16, hipMemcpyDeviceToHost, s));
+  SMF_CHECK(hipStreamSynchronize(s));
+  if (r.st != SM_OK) return r.st;
+  if (output && r.len) SMF_CHECK(hipMemcpy(output, ctx->io_out.p, r.len, hipMemcpyDeviceToHost));
+  if (length) *length = (size_t)r.len;
+  return SM_OK;
+}
+
+sm_status smf_uncompress(smf_ctx* ctx, const uint8_t* framed, size_t n, uint8_t* output, size_t* length) {
+  if (!ctx || !length || (n && !framed) || (*length && !output)) return SM_ERR_ARGUMENT;
+  return uncompress_host(ctx, framed, n, output, length);
+}
+
+sm_status smf_validate(smf_ctx* ctx, const uint8_t* framed, size_t n) {
+  if (!ctx || (n && !framed)) return SM_ERR_ARGUMENT;
+  return uncompress_host(ctx, framed, n, nullptr, nullptr);
+}
+
+}  // extern "C"

@@ -1,0 +1,119 @@
+// smf_host.cpp -- the host-only part of the framing library (include/snappy_mi355x_framing.h):
+// the chunk walker over a host buffer, the bytewise CRC-32C and the size helpers.  No HIP and no
+// call into the raw codec, so this file also builds alone (the sanitizer driver, smf_host_check.cpp).
+#include "smf_format.h"
+
+namespace {
+
+struct CrcTable {
+  uint32_t t[256];
+  CrcTable() {
+    for (uint32_t b = 0; b < 256; ++b) {
+      uint32_t c = b;
+      for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1) ? smf::kPoly : 0u);
+      t[b] = c;
+    }
+  }
+};
+
+const CrcTable& crc_table() {
+  static const CrcTable tab;
+  return tab;
+}
+
+}  // namespace
+
+namespace smf {
+
+// T_k[b]: byte b followed by k zero bytes (the slicing tables; T_0 is the bytewise table).
+// tab[i] = T_(15-i): a granule's byte i has 15-i bytes behind it.  tab[16+j] = T_(N-1-j), N =
+// 16 kCrcThreads: a register's byte j stands in for byte j of the N bytes that follow it.
+void build_crc_lut(CrcLut* T) {
+  const uint32_t* t0 = crc_table().t;
+  const uint32_t N = 16 * kCrcThreads;
+  uint32_t cur[256];
+  for (uint32_t b = 0; b < 256; ++b) cur[b] = t0[b];
+  for (uint32_t k = 0; k < N; ++k) {
+    if (k < 16)
+      for (uint32_t b = 0; b < 256; ++b) T->tab[15 - k][b] = cur[b];
+    if (k >= N - 4)
+      for (uint32_t b = 0; b < 256; ++b) T->tab[16 + (N - 1 - k)][b] = cur[b];
+    for (uint32_t b = 0; b < 256; ++b) cur[b] = (cur[b] >> 8) ^ t0[cur[b] & 0xff];
+  }
+  uint32_t x128 = 0x40000000u;  // x
+  for (int i = 0; i < 7; ++i) x128 = gf_mul(x128, x128);
+  T->xpow[0] = 0x80000000u;  // 1
+  for (uint32_t g = 0; g < kCrcPow; ++g) T->xpow[g + 1] = gf_mul(T->xpow[g], x128);
+  T->xpow2[0] = x128;
+  for (uint32_t k = 0; k + 1 < 32; ++k) T->xpow2[k + 1] = gf_mul(T->xpow2[k], T->xpow2[k]);
+}
+
+const char* host_message(sm_status st) {
+  switch (st) {
+    case SMF_ERR_NO_IDENTIFIER: return "Framed stream does not start with a stream identifier.";
+    case SMF_ERR_BAD_IDENTIFIER: return "Framed stream: corrupt stream identifier.";
+    case SMF_ERR_RESERVED_CHUNK: return "Framed stream: unskippable reserved chunk type.";
+    case SMF_ERR_TRUNCATED: return "Framed stream: truncated chunk.";
+    case SMF_ERR_CHUNK_TOO_LARGE: return "Framed stream: chunk of more than 65536 uncompressed bytes.";
+    case SMF_ERR_CRC: return "Framed stream: CRC-32C mismatch.";
+    default: return nullptr;
+  }
+}
+
+}  // namespace smf
+
+extern "C" {
+
+size_t smf_max_framed_length(size_t n) { return 10 + 8 * ((n + 65535) / 65536) + n; }
+
+uint32_t smf_crc32c(const void* buf, size_t n) {
+  const uint32_t* t = crc_table().t;
+  const uint8_t* p = (const uint8_t*)buf;
+  uint32_t c = 0xffffffffu;
+  for (size_t i = 0; i < n; ++i) c = t[(c ^ p[i]) & 0xff] ^ (c >> 8);
+  return c ^ 0xffffffffu;
+}
+
+uint32_t smf_crc32c_mask(uint32_t crc) { return smf::mask(crc); }
+
+sm_status smf_index(const uint8_t* buf, size_t n, const smf_chunks* chunks, uint32_t max_chunks,
+                    smf_summary* summary) {
+  if (!summary || (!buf && n)) return SM_ERR_ARGUMENT;
+  if (chunks && max_chunks && (!chunks->type || !chunks->pay_off || !chunks->pay_len || !chunks->crc || !chunks->ulen))
+    return SM_ERR_ARGUMENT;
+  smf::Walk w;
+  uint64_t pos = 0;
+  for (;;) {
+    uint8_t head[smf::kHeadBytes];
+    const uint32_t have = (uint32_t)(n - pos < smf::kHeadBytes ? n - pos : smf::kHeadBytes);
+    for (uint32_t i = 0; i < have; ++i) head[i] = buf[pos + i];
+    smf::Chunk c;
+    if (!smf::walk_step(w, head, have, pos, n, c)) break;
+    if (c.data) {
+      if (chunks && w.nchunks < max_chunks) {
+        const uint32_t k = w.nchunks;
+        chunks->type[k] = c.type;
+        chunks->pay_off[k] = c.pay_off;
+        chunks->pay_len[k] = c.pay_len;
+        chunks->crc[k] = c.crc;
+        chunks->ulen[k] = c.ulen;
+      }
+      ++w.nchunks;
+      w.total += c.ulen;
+    }
+    pos = c.next;
+  }
+  summary->total_length = w.total;
+  summary->nchunks = w.nchunks;
+  summary->status = smf::walk_status(w, chunks != nullptr, max_chunks);
+  return summary->status;
+}
+
+sm_status smf_uncompressed_length(const uint8_t* buf, size_t n, size_t* result) {
+  smf_summary s;
+  const sm_status st = smf_index(buf, n, nullptr, 0, &s);
+  if (st == SM_OK && result) *result = (size_t)s.total_length;
+  return st;
+}
+
+}  // extern "C"

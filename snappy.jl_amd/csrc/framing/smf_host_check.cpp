@@ -1,0 +1,220 @@
+// smf_host_check.cpp -- stand-alone driver of the host-only framing code (smf_host.cpp), built with
+// -fsanitize=address,undefined by `make host_check`.  Every buffer is a heap block of exactly the
+// stream's size, so a walker that reads past a cut stream trips the sanitizer.  It also runs the
+// CRC kernel's arithmetic (k_crc32c: the tables, the per-lane granule steps, the x^(128 t)
+// multipliers) lane by lane on the CPU against the bytewise CRC.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "smf_format.h"
+
+namespace {
+
+int failures = 0;
+
+void expect(bool ok, const char* what) {
+  if (!ok) {
+    std::printf("FAIL %s\n", what);
+    ++failures;
+  }
+}
+
+typedef std::string S;
+
+S chunk(uint8_t type, const S& data, long len = -1) {
+  const uint32_t L = len < 0 ? (uint32_t)data.size() : (uint32_t)len;
+  S s;
+  s += (char)type;
+  s += (char)(L & 0xff);
+  s += (char)((L >> 8) & 0xff);
+  s += (char)((L >> 16) & 0xff);
+  return s + data;
+}
+
+const S kId = S("\xff\x06\x00\x00sNaPpY", 10);
+
+S crc_field(const S& bytes) {
+  const uint32_t m = smf_crc32c_mask(smf_crc32c(bytes.data(), bytes.size()));
+  S s;
+  for (int i = 0; i < 4; ++i) s += (char)((m >> (8 * i)) & 0xff);
+  return s;
+}
+
+S raw_chunk(const S& bytes) { return chunk(0x01, crc_field(bytes) + bytes); }
+
+struct Result {
+  smf_summary sum;
+  std::vector<uint8_t> type;
+  std::vector<uint64_t> off;
+  std::vector<uint32_t> len, crc, ulen;
+};
+
+Result walk(const S& stream, uint32_t max_chunks = 16) {
+  Result r;
+  r.type.resize(max_chunks);
+  r.off.resize(max_chunks);
+  r.len.resize(max_chunks);
+  r.crc.resize(max_chunks);
+  r.ulen.resize(max_chunks);
+  uint8_t* heap = (uint8_t*)std::malloc(stream.size() ? stream.size() : 1);
+  std::memcpy(heap, stream.data(), stream.size());
+  const smf_chunks ch{r.type.data(), r.off.data(), r.len.data(), r.crc.data(), r.ulen.data()};
+  smf_index(heap, stream.size(), &ch, max_chunks, &r.sum);
+  smf_summary count;
+  smf_index(heap, stream.size(), nullptr, 0, &count);
+  expect(count.nchunks == r.sum.nchunks && count.total_length == r.sum.total_length, "count-only walk agrees");
+  std::free(heap);
+  return r;
+}
+
+void status_case(const char* name, const S& stream, int32_t status, uint32_t nchunks = 0, uint64_t total = 0) {
+  const Result r = walk(stream);
+  if (r.sum.status != status || r.sum.nchunks != nchunks || r.sum.total_length != total) {
+    std::printf("FAIL %s: status %d (want %d), chunks %u (want %u), total %llu (want %llu)\n", name, r.sum.status, status,
+                r.sum.nchunks, nchunks, (unsigned long long)r.sum.total_length, (unsigned long long)total);
+    ++failures;
+  }
+}
+
+// k_crc32c's arithmetic, one lane after another
+uint32_t crc_like_kernel(const smf::CrcLut& T, const uint8_t* p, uint32_t n) {
+  const uint32_t* tab = &T.tab[0][0];
+  const uint32_t head = std::min<uint32_t>(n, (16u - (uint32_t)((uintptr_t)p & 15)) & 15u);
+  const uint32_t G = (n - head) / 16;
+  uint32_t acc = 0;
+  for (uint32_t t = 0; t < smf::kCrcThreads; ++t) {
+    uint32_t s = 0;
+    if (t < G) {
+      uint32_t idx = (G - 1 - t) % smf::kCrcThreads;
+      for (uint32_t cnt = (G - 1 - t) / smf::kCrcThreads + 1; cnt; --cnt, idx += smf::kCrcThreads) {
+        uint32_t w[4];
+        std::memcpy(w, p + head + 16 * (size_t)idx, 16);
+        s = smf::crc_granule(tab, s, w);
+      }
+      s = smf::gf_mul(T.xpow[t], s);
+    }
+    if (t == smf::kCrcThreads - 1) {
+      uint32_t h = 0xffffffffu;
+      for (uint32_t i = 0; i < head; ++i) h = tab[15 * 256 + ((h ^ p[i]) & 0xff)] ^ (h >> 8);
+      s ^= smf::gf_mul(smf::gf_xpow(&T, G), h);
+    }
+    acc ^= s;
+  }
+  for (uint32_t i = head + 16 * G; i < n; ++i) acc = tab[15 * 256 + ((acc ^ p[i]) & 0xff)] ^ (acc >> 8);
+  return acc ^ 0xffffffffu;
+}
+
+}  // namespace
+
+int main() {
+  // CRC known answers (the first five: RFC 3720)
+  {
+    S inc, dec;
+    for (int i = 0; i < 32; ++i) {
+      inc += (char)i;
+      dec += (char)(31 - i);
+    }
+    struct {
+      S in;
+      uint32_t crc, masked;
+    } kat[] = {{"123456789", 0xe3069283u, 0xc78ab0e5u}, {S(32, '\0'), 0x8a9136aau, 0x0fd7fffau},
+               {S(32, '\xff'), 0x62a8ab43u, 0xf909b029u}, {inc, 0x46dd794eu, 0x951f7892u},
+               {dec, 0x113fdb5cu, 0x593b0d57u},           {"", 0u, 0xa282ead8u},
+               {"a", 0xc1d04330u, 0x28e46e78u},           {S(65536, '\0'), 0x72c0c4a4u, 0x2bcbd059u}};
+    for (auto& k : kat) {
+      const uint32_t c = smf_crc32c(k.in.data(), k.in.size());
+      expect(c == k.crc && smf_crc32c_mask(c) == k.masked, "crc known answer");
+    }
+  }
+  // the kernel's arithmetic against the bytewise CRC: every alignment, lengths around every edge
+  {
+    smf::CrcLut* T = new smf::CrcLut();
+    smf::build_crc_lut(T);
+    std::vector<uint8_t> buf(16 + 70000 + 16);
+    uint32_t x = 12345;
+    for (auto& b : buf) {
+      x = x * 1664525u + 1013904223u;
+      b = (uint8_t)(x >> 24);
+    }
+    const uint32_t lens[] = {0,   1,   2,    3,    4,    5,    7,    8,    15,    16,    17,    31,   32,
+                             33,  63,  64,   65,   255,  256,  257,  1023, 1024,  1025,  4095,  4096, 4097,
+                             4111, 4112, 8191, 8192, 8193, 65535, 65536, 65537, 69999, 70000};
+    uint8_t* base = buf.data() + ((16 - ((uintptr_t)buf.data() & 15)) & 15);
+    for (uint32_t a = 0; a < 16; ++a)
+      for (uint32_t n : lens)
+        if (crc_like_kernel(*T, base + a, n) != smf_crc32c(base + a, n)) {
+          std::printf("FAIL kernel arithmetic: align %u length %u\n", a, n);
+          ++failures;
+        }
+    delete T;
+  }
+  expect(smf_max_framed_length(0) == 10 && smf_max_framed_length(1) == 19 && smf_max_framed_length(65536) == 65554 &&
+             smf_max_framed_length(65537) == 65537 + 26,
+         "max framed length");
+
+  const S a = raw_chunk("a");
+  expect(kId + a == S("\xff\x06\x00\x00sNaPpY\x01\x05\x00\x00\x78\x6e\xe4\x28\x61", 19), "golden framed 'a'");
+  // a compressed chunk: varint 5, literal tag (4 << 2), "hello"
+  const S hello = chunk(0x00, crc_field("hello") + S("\x05\x10hello", 7));
+
+  status_case("identifier only", kId, SM_OK);
+  status_case("one raw chunk", kId + a, SM_OK, 1, 1);
+  status_case("compressed chunk", kId + hello, SM_OK, 1, 5);
+  status_case("padding", kId + chunk(0xfe, S(7, '\0')) + a, SM_OK, 1, 1);
+  status_case("skippable 0x80", kId + chunk(0x80, "xyz") + a, SM_OK, 1, 1);
+  status_case("skippable 0xfd", kId + a + chunk(0xfd, "xyz") + hello, SM_OK, 2, 6);
+  status_case("repeated identifier", kId + a + kId + a, SM_OK, 2, 2);
+  status_case("zero-length chunks", kId + chunk(0xfe, "") + chunk(0x80, "") + a, SM_OK, 1, 1);
+  status_case("empty data chunks", kId + chunk(0x01, crc_field("")) + chunk(0x00, crc_field("") + S(1, '\0')), SM_OK, 2, 0);
+  status_case("empty stream", "", SMF_ERR_NO_IDENTIFIER);
+  status_case("missing identifier", a, SMF_ERR_NO_IDENTIFIER);
+  status_case("padding first", chunk(0xfe, "") + kId, SMF_ERR_NO_IDENTIFIER);
+  status_case("wrong identifier", chunk(0xff, "sNaPpy") + a, SMF_ERR_BAD_IDENTIFIER);
+  status_case("identifier length 5", chunk(0xff, "sNaPp") + a, SMF_ERR_BAD_IDENTIFIER);
+  status_case("wrong repeated identifier", kId + a + chunk(0xff, "SNaPpY"), SMF_ERR_BAD_IDENTIFIER, 1, 1);
+  status_case("identifier cut", kId.substr(0, 7), SMF_ERR_TRUNCATED);
+  status_case("reserved 0x02", kId + chunk(0x02, "abcd"), SMF_ERR_RESERVED_CHUNK);
+  status_case("reserved 0x7f", kId + a + chunk(0x7f, ""), SMF_ERR_RESERVED_CHUNK, 1, 1);
+  for (size_t cut = 1; cut <= 3; ++cut) {
+    status_case("first header cut", kId.substr(0, cut), SMF_ERR_TRUNCATED);
+    status_case("later header cut", kId + a + a.substr(0, cut), SMF_ERR_TRUNCATED, 1, 1);
+  }
+  status_case("payload cut short", kId + a + hello.substr(0, hello.size() - 1), SMF_ERR_TRUNCATED, 1, 1);
+  status_case("padding cut short", kId + chunk(0xfe, "abc", 4), SMF_ERR_TRUNCATED);
+  status_case("data chunk of 3 bytes", kId + chunk(0x01, "abc"), SMF_ERR_TRUNCATED);
+  status_case("data chunk of 0 bytes", kId + chunk(0x00, ""), SMF_ERR_TRUNCATED);
+  status_case("uncompressed chunk of 65541", kId + chunk(0x01, S(65541 + 4, 'x')), SMF_ERR_CHUNK_TOO_LARGE);
+  status_case("uncompressed chunk of 65540", kId + chunk(0x01, S(65536 + 4, 'x')), SM_OK, 1, 65536);
+  status_case("varint 65537", kId + chunk(0x00, S("abcd") + S("\x81\x80\x04", 3)), SMF_ERR_CHUNK_TOO_LARGE);
+  status_case("varint 65536", kId + chunk(0x00, S("abcd") + S("\x80\x80\x04", 3)), SM_OK, 1, 65536);
+  status_case("varint unterminated", kId + chunk(0x00, S("abcd") + S("\x80\x80", 2)), SM_ERR_VARINT);
+  status_case("varint missing", kId + chunk(0x00, "abcd"), SM_ERR_VARINT);
+  status_case("varint too long", kId + chunk(0x00, S("abcd") + S("\x80\x80\x80\x80\x10", 5)), SM_ERR_VARINT);
+
+  // the entries, and a capacity that is too small
+  {
+    const S s = kId + a + chunk(0xfe, "pad") + hello + a;
+    const Result r = walk(s);
+    expect(r.sum.status == SM_OK && r.sum.nchunks == 3 && r.sum.total_length == 7, "entries: summary");
+    expect(r.type[0] == 1 && r.off[0] == 18 && r.len[0] == 1 && r.ulen[0] == 1 && r.crc[0] == 0x28e46e78u, "entries: chunk 0");
+    expect(r.type[1] == 0 && r.off[1] == 19 + 7 + 8 && r.len[1] == 7 && r.ulen[1] == 5, "entries: chunk 1");
+    const Result small = walk(s, 2);
+    expect(small.sum.status == SM_BUFFER_TOO_SMALL && small.sum.nchunks == 3 && small.type[1] == 0, "capacity too small");
+    size_t total = 0;
+    expect(smf_uncompressed_length((const uint8_t*)s.data(), s.size(), &total) == SM_OK && total == 7, "uncompressed length");
+    smf_summary sum;
+    expect(smf_index(nullptr, 4, nullptr, 0, &sum) == SM_ERR_ARGUMENT, "null buffer");
+    expect(smf_index((const uint8_t*)s.data(), s.size(), nullptr, 0, nullptr) == SM_ERR_ARGUMENT, "null summary");
+  }
+  expect(smf::host_message(SMF_ERR_CRC) != nullptr && smf::host_message(SM_OK) == nullptr, "messages");
+
+  if (failures) {
+    std::printf("%d failure(s)\n", failures);
+    return 1;
+  }
+  std::printf("smf_host_check ok\n");
+  return 0;
+}

@@ -1,0 +1,48 @@
+// smf_internal.h -- launcher interfaces between the framing C ABI (smf_api.hip) and its kernels
+// (smf_kernels.hip).  Not part of the public ABI.  All pointers are device pointers.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "smf_format.h"
+
+namespace smf {
+
+hipError_t launch_crc32c(const uint8_t* in, const uint64_t* off, const uint32_t* len, uint32_t nblk, uint32_t* crc,
+                         int masked, const CrcLut* T, hipStream_t s);
+
+// compress: the blocks of an n-byte input and their slots; then, behind the raw compressor and the
+// CRC pass, the chunk types and places (*out_len, *status) and the packed stream
+hipError_t launch_frame_compress_plan(uint64_t n, uint32_t nblk, uint64_t pitch, uint64_t* in_off, uint32_t* in_len,
+                                      uint64_t* slot_off, hipStream_t s);
+struct PackArgs {
+  const uint8_t* in;
+  const uint64_t* in_off;
+  const uint32_t* in_len;
+  const uint8_t* slots;
+  const uint64_t* slot_off;
+  const uint32_t* comp_len;
+  const uint32_t* crc;
+  uint8_t* type;
+  uint64_t* dst_off;
+  uint32_t nblk;
+  uint8_t* dst;
+};
+hipError_t launch_frame_pack(const PackArgs& a, uint64_t* out_len, int32_t* status, hipStream_t s);
+
+// index: ch == null counts only
+hipError_t launch_frame_index(const uint8_t* in, uint64_t n, const smf_chunks* ch, uint32_t max_chunks, smf_summary* sum,
+                              hipStream_t s);
+// *d_len / *d_status = (len, status), or with sum the walk's total and status
+hipError_t launch_frame_result(uint64_t* d_len, uint64_t len, const smf_summary* sum, int32_t* d_status, int32_t status,
+                               hipStream_t s);
+
+// uncompress: places and the raw decoder's arguments; the 0x01 chunks' copies; the verdicts
+hipError_t launch_frame_plan(const smf_chunks& ch, uint32_t nchunks, uint64_t out_capacity, uint64_t* out_off,
+                             uint32_t* cap, uint32_t* dec_len, int32_t* pre, uint64_t* out_len, hipStream_t s);
+hipError_t launch_frame_copy(const uint8_t* in, const smf_chunks& ch, uint32_t nchunks, const uint64_t* out_off,
+                             const uint32_t* cap, uint8_t* out, hipStream_t s);
+hipError_t launch_frame_verify(const smf_chunks& ch, uint32_t nchunks, const int32_t* pre, const int32_t* dec_status,
+                               const uint32_t* crc_out, int32_t* chunk_status, int32_t* status, hipStream_t s);
+
+}  // namespace smf
