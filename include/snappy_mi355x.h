@@ -22,7 +22,8 @@
  *
  * Threading: an sm_ctx owns one HIP device, one stream and its scratch.  The host-buffer
  * entry points lock the ctx (concurrent callers on one ctx are serialised); the *_device entry
- * points only launch on the caller's stream and take no lock.  Distinct ctxs are independent.
+ * points only launch on the caller's stream and take no lock, with one exception: the two device
+ * compress calls in the fast modes (see sm_compress_batch_device).  Distinct ctxs are independent.
  */
 #ifndef SNAPPY_MI355X_H_
 #define SNAPPY_MI355X_H_
@@ -123,7 +124,21 @@ sm_status sm_uncompress(sm_ctx* ctx, const char* compressed, size_t compressed_l
  * Every mark is larger than any real size (<= sm_max_compressed_length(65536) = 76,490); the
  * host-buffer entry points check the lengths and return SM_ERR_DEVICE / SM_ERR_ARGUMENT instead
  * of a mark.  stream: the hipStream_t to launch on (NULL = the default stream, as everywhere in
- * HIP); nothing is synchronised. */
+ * HIP); nothing is synchronised.
+ * What the fast modes own in the ctx: a batch whose last round of blocks would leave more than
+ * half the device idle has those blocks parsed in parts (sm_batch_parts_plan), through a scratch
+ * of about 9 MB that the ctx keeps per stream handle it has been given.
+ *  - Such a call holds a mutex of the ctx from its scratch lookup to its last enqueue (a few
+ *    microseconds of host time), so calls from several host threads on one ctx are safe, on one
+ *    stream or on several, and those on one stream run in the order the lock was taken.
+ *  - The scratch is allocated (hipMalloc) by the first such call on a stream and kept until
+ *    sm_ctx_destroy.  A call made while the stream is being captured into a graph allocates
+ *    nothing: without a scratch from an earlier call it parses every block whole, as does any
+ *    call whose allocation fails.  Call once on the stream before capturing to have the parts.
+ *  - Streams are told apart by handle and a ctx keeps at most 8 scratches, never giving one up:
+ *    calls on a ninth and later stream parse every block whole, and a stream destroyed with work
+ *    in flight must not have its handle reused on this ctx before that work is done.
+ * The bytes and lengths do not depend on any of this. */
 sm_status sm_compress_batch_device(sm_ctx* ctx, const uint8_t* d_in, const uint64_t* d_in_off,
                                    const uint32_t* d_in_len, uint32_t nblk, uint8_t* d_out,
                                    const uint64_t* d_out_off, uint32_t* d_out_len, int mode, void* stream);
@@ -136,6 +151,18 @@ sm_status sm_compress_fragments_device(sm_ctx* ctx, const uint8_t* d_in, const u
                                        const uint32_t* d_in_len, uint32_t nblk, uint8_t* d_out,
                                        const uint64_t* d_out_off, uint32_t* d_out_len, uint64_t total_len,
                                        int mode, void* stream);
+/* diagnostic (host only): the rule by which the two calls above divide nblk blocks in the fast
+ * modes on a device of grid compute units.  The persistent parse kernel takes nblk - *rem blocks,
+ * whole rounds of grid; the last *rem blocks (0: none; only when nblk % grid is at most grid / 2)
+ * are parsed in *parts parts each on their own workgroups, *parts the largest power of two <= 16
+ * with *rem * *parts <= grid, and joined into the caller's slots -- the same bytes and lengths.
+ * This reports the rule only: not the mode, not SM_BATCH_PARTS=0 in the environment (read once per
+ * process; the calls then parse every block whole), not a call that found no scratch.
+ * sm_ctx_last_batch_parts tells what a call did. */
+void sm_batch_parts_plan(uint32_t nblk, uint32_t grid, uint32_t* rem, uint32_t* parts);
+/* diagnostic: the number of blocks that the ctx's last sm_compress_batch_device or
+ * sm_compress_fragments_device call parsed in parts (0: every block whole), -1 for a null ctx */
+int sm_ctx_last_batch_parts(sm_ctx* ctx);
 /* Places fragments of ONE stream at their offsets in it -- the concatenation of src/Snappy.jl:29-35
  * (fragment i's bytes follow fragment i-1's behind varint(total)) for a stream whose fragments were
  * compressed in shards, e.g. one contiguous shard per GPU (snappy.jl_amd/dist.py).

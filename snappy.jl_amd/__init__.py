@@ -43,7 +43,8 @@ ABI_SYMBOLS = (
     "sm_status_message", "sm_max_compressed_length", "sm_uncompressed_length", "sm_parse32",
     "sm_encode32", "sm_ctx_create", "sm_ctx_destroy", "sm_ctx_stream", "sm_compress", "sm_uncompress",
     "sm_compress_batch_device", "sm_uncompress_batch_device", "sm_compress_batch",
-    "sm_uncompress_batch", "sm_version", "sm_compress_fragments_device", "sm_ctx_last_path", "sm_ctx_set_small_decode",
+    "sm_uncompress_batch", "sm_version", "sm_compress_fragments_device", "sm_batch_parts_plan",
+    "sm_ctx_last_batch_parts", "sm_ctx_last_path", "sm_ctx_set_small_decode",
     "sm_ctx_set_split_compress", "sm_ctx_last_compress_split",
     "sm_find_match_length", "sm_validate_batch_device", "sm_uncompressed_length_batch_device",
     "sm_validate_compressed_buffer", "sm_compress_batch_sharded", "sm_uncompress_batch_sharded",
@@ -131,6 +132,10 @@ def load_library(path):
     L.sm_version.argtypes = []
     L.sm_compress_fragments_device.restype = i32
     L.sm_compress_fragments_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, ctypes.c_uint64, ctypes.c_int, vp]
+    L.sm_ctx_last_batch_parts.restype = ctypes.c_int
+    L.sm_ctx_last_batch_parts.argtypes = [vp]
+    L.sm_batch_parts_plan.restype = None
+    L.sm_batch_parts_plan.argtypes = [u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.sm_validate_batch_device.restype = i32
     L.sm_validate_batch_device.argtypes = [vp, vp, vp, vp, u32, vp, vp]
     L.sm_uncompressed_length_batch_device.restype = i32
@@ -461,6 +466,20 @@ def compress_fragments_device(d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_
                                             int(total_len), _mode(mode), ctypes.c_void_p(stream))
     if st:
         raise SnappyError(st)
+
+
+def batch_parts_plan(nblk, grid):
+    """(rem, parts): the fast-mode device batch calls parse the last `rem` of nblk blocks in `parts`
+    parts each on a device of `grid` compute units (rem 0: none).  Host only."""
+    rem, parts = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    lib().sm_batch_parts_plan(int(nblk), int(grid), ctypes.byref(rem), ctypes.byref(parts))
+    return rem.value, parts.value
+
+
+def last_batch_parts(device=0):
+    """Blocks that the device's last compress_batch_device / compress_fragments_device call parsed
+    in parts (0: every block whole)."""
+    return lib().sm_ctx_last_batch_parts(context(device))
 
 
 def uncompress_batch_device(d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status,

@@ -99,6 +99,19 @@ struct sm_ctx {
   bool split = true;   // sm_ctx_set_split_compress
   bool last_split = false;  // the last sm_compress parsed its fragments in parts
   std::mutex mu;       // serialises the host-buffer entry points (they share the scratch above)
+  // The device batch compress calls' part scratch (batch_parts_scratch), one per stream they were
+  // given: calls on one stream run in order and share it, calls on different streams may overlap.
+  // Allocated at full size on a stream's first call and never grown, so no later call frees or
+  // synchronises; beyond kPartStreams streams a call takes the whole-block path.
+  static constexpr int kPartStreams = 8;
+  struct PartScratch {
+    hipStream_t stream = nullptr;
+    DevBuf buf;
+  };
+  PartScratch part[kPartStreams];
+  int nparts = 0;
+  std::mutex part_mu;  // the scratch table, and a call's launches that use a scratch (compress_device)
+  std::atomic<int> last_parts{0};  // sm_ctx_last_batch_parts
 };
 
 #ifndef SM_SMALL_BODY8  // path 4 when the body is at most SM_SMALL_BODY8/8 of the output
@@ -790,6 +803,7 @@ void sm_ctx_destroy(sm_ctx* ctx) {
     ctx->idx.release();
     ctx->gat.release();
     ctx->org.release();
+    for (int i = 0; i < ctx->nparts; ++i) ctx->part[i].buf.release();  // (the caller's streams are the caller's to drain)
     ctx->stage.release();
     ctx->stage_in.release();
     if (ctx->in_ev) (void)hipEventDestroy(ctx->in_ev);
@@ -805,6 +819,63 @@ void sm_ctx_destroy(sm_ctx* ctx) {
 
 void* sm_ctx_stream(sm_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
+namespace {
+
+// SM_BATCH_PARTS=0 in the environment (read once): the device batch calls parse every block with
+// the whole-block kernel, as before the remainder rule -- the same bytes, for tests and A/Bs
+bool batch_parts_enabled() {
+  static const bool on = [] {
+    const char* e = getenv("SM_BATCH_PARTS");
+    return !(e && e[0] == '0' && e[1] == 0);
+  }();
+  return on;
+}
+
+// the part scratch of ctx for calls on stream s (nullptr: none to be had, take the whole-block
+// path); ctx->part_mu is held.  Nothing is allocated while s is being captured into a graph (an
+// allocation there fails or invalidates the capture): a scratch the stream already has is used,
+// else the call takes the whole-block path.
+uint8_t* batch_parts_buffer(sm_ctx* ctx, hipStream_t s) {
+  for (int i = 0; i < ctx->nparts; ++i)
+    if (ctx->part[i].stream == s) return (uint8_t*)ctx->part[i].buf.p;
+  if (ctx->nparts == sm_ctx::kPartStreams) return nullptr;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  sm_ctx::PartScratch& ps = ctx->part[ctx->nparts];
+  if (ps.buf.ensure(sm::batch_parts_scratch(sm::compress_grid())) != hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  ps.stream = s;
+  ++ctx->nparts;
+  return (uint8_t*)ps.buf.p;
+}
+
+// the device batch calls' compress launches (ctx's device is current).  A call that parses its
+// remainder in parts holds ctx->part_mu from the scratch lookup to its last enqueue: the launches
+// of two host threads on one stream must not interleave (screen, parse into the scratch, gather
+// out of it), or the later call's parts would replace the earlier one's before its gather runs.
+hipError_t compress_device(sm_ctx* ctx, const sm::CompressArgs& a, int mode, hipStream_t s) {
+  if (mode != SM_MODE_REFERENCE && batch_parts_enabled()) {
+    const sm::BatchParts bp = sm::batch_parts_rule(a.nblk, sm::compress_grid());
+    if (bp.rem) {
+      std::lock_guard<std::mutex> lk(ctx->part_mu);
+      uint8_t* const scratch = batch_parts_buffer(ctx, s);
+      if (scratch) {
+        ctx->last_parts.store((int)bp.rem, std::memory_order_relaxed);
+        return sm::launch_compress_batch_parts(a, mode, bp, scratch, s);
+      }
+    }
+  }
+  ctx->last_parts.store(0, std::memory_order_relaxed);
+  return sm::launch_compress(a, mode, s);
+}
+
+}  // namespace
+
 sm_status sm_compress_batch_device(sm_ctx* ctx, const uint8_t* d_in, const uint64_t* d_in_off,
                                    const uint32_t* d_in_len, uint32_t nblk, uint8_t* d_out,
                                    const uint64_t* d_out_off, uint32_t* d_out_len, int mode, void* stream) {
@@ -813,7 +884,7 @@ sm_status sm_compress_batch_device(sm_ctx* ctx, const uint8_t* d_in, const uint6
   if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len) return SM_ERR_ARGUMENT;
   DeviceGuard g(ctx->device);
   sm::CompressArgs a{d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_len, nblk, 0, 1};
-  SM_CHECK(sm::launch_compress(a, mode, (hipStream_t)stream));
+  SM_CHECK(compress_device(ctx, a, mode, (hipStream_t)stream));
   return SM_OK;
 }
 
@@ -827,8 +898,16 @@ sm_status sm_compress_fragments_device(sm_ctx* ctx, const uint8_t* d_in, const u
   if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len) return SM_ERR_ARGUMENT;
   DeviceGuard g(ctx->device);
   sm::CompressArgs a{d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_len, nblk, sm::hashtable_size(total_len), 0};
-  SM_CHECK(sm::launch_compress(a, mode, (hipStream_t)stream));
+  SM_CHECK(compress_device(ctx, a, mode, (hipStream_t)stream));
   return SM_OK;
+}
+
+int sm_ctx_last_batch_parts(sm_ctx* ctx) { return ctx ? ctx->last_parts.load(std::memory_order_relaxed) : -1; }
+
+void sm_batch_parts_plan(uint32_t nblk, uint32_t grid, uint32_t* rem, uint32_t* parts) {
+  const sm::BatchParts bp = sm::batch_parts_rule(nblk, grid);
+  if (rem) *rem = bp.rem;
+  if (parts) *parts = bp.parts;
 }
 
 sm_status sm_place_fragments_device(sm_ctx* ctx, const uint8_t* d_src, const uint64_t* d_src_off,

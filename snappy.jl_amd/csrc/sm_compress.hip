@@ -544,6 +544,62 @@ __global__ __launch_bounds__(256) void k_gather_parts(const uint8_t* __restrict_
   }
 }
 
+// The parts of the device batch calls' remainder blocks (k_compress_sc_span with sp.blk_pitch) into
+// the caller's slots: workgroup (u, y) takes part j = u % parts of block b = u / parts (a's arrays
+// start at the first remainder block), which goes behind the block's parts before it at a.out +
+// a.out_off[b]; a.out_len[b] = their sum.  What the whole-block kernel's writer does per block is
+// done here: a block whose parts sum to more than one literal of the block is written as that
+// literal from the input (emit_literal!, internal.jl:271-284), an error mark in any part (or a part
+// longer than its pitch: never expected) makes the block's length a mark and copies nothing, and an
+// empty block is its header alone.  A block the screen emitted is in its slot already.
+__global__ __launch_bounds__(256) void k_gather_parts(CompressArgs a, const uint8_t* __restrict__ src, ScSpan sp) {
+  const uint32_t b = blockIdx.x / sp.parts, j = blockIdx.x % sp.parts, t = threadIdx.x;
+  const uint32_t* const pl = sp.part_len + b * sp.parts;
+  if (pl[0] == kPartScreened) return;  // (the screen wrote a.out_len[b] too)
+  const bool first = j == 0 && blockIdx.y == 0;
+  uint32_t sum = 0, before = 0, mark = 0;
+  for (uint32_t i = 0; i < sp.parts; ++i) {  // (uniform: at most 16 lengths)
+    const uint32_t L = pl[i];
+    if (L >= kOutLenError)
+      mark |= L;
+    else if (L > sp.pitch)
+      mark |= kOutLenError | 8u;
+    else {
+      sum += L;
+      before += i < j ? L : 0u;
+    }
+  }
+  if (mark) {
+    if (first && t == 0) a.out_len[b] = mark;
+    return;
+  }
+  const uint32_t n = a.in_len[b];
+  uint8_t* const dst = a.out + a.out_off[b];
+  const uint32_t hv = a.header ? varint_len(n) : 0u;
+  if (n == 0) {  // no part ran
+    if (first && t == 0) {
+      if (hv) dst[0] = 0;
+      a.out_len[b] = hv;
+    }
+    return;
+  }
+  const uint32_t tb = literal_tag_bytes(n), lit = hv + tb + n;
+  if (sum <= lit) {
+    gather_unit(src + b * sp.blk_pitch + j * sp.pitch, pl[j], dst + before, blockIdx.y, gridDim.y);
+    if (first && t == 0) a.out_len[b] = sum;
+    return;
+  }
+  if (j) return;  // one literal: the header, the tag, the block's bytes (any alignment: by bytes)
+  if (blockIdx.y == 0) {
+    const uint32_t n1 = n - 1;
+    if (t < hv) dst[t] = (uint8_t)(((n >> (7 * t)) & 0x7f) | (t + 1 < hv ? 0x80 : 0));
+    if (t < tb) dst[hv + t] = tb == 1 ? (uint8_t)(n1 << 2) : (t == 0 ? (uint8_t)((58 + tb) << 2) : (uint8_t)(n1 >> (8 * (t - 1))));
+    if (t == 0) a.out_len[b] = lit;
+  }
+  const uint8_t* const in = a.in + a.in_off[b];
+  for (uint32_t k = blockIdx.y * blockDim.x + t; k < n; k += blockDim.x * gridDim.y) dst[hv + tb + k] = in[k];
+}
+
 // ---- a sharded stream's fragments at their places in it (Snappy.jl:29-35) ----------
 // Fragment b (len[b] bytes at src + src_off[b]) to dst + (dst_off[b] - base): dst_off[b] is the
 // fragment's offset in the whole stream (the all-gathered exclusive scan behind the varint
@@ -605,6 +661,13 @@ hipError_t launch_parts_gather(const uint8_t* src, const uint64_t* out_off, cons
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_gather_parts, dim3(nunit, 4), dim3(256), 0, s, src, out_off, sp, in, in_off, in_len, nunit,
                      tot, dst);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_parts_gather(const CompressArgs& a, const uint8_t* src, const ScSpan& sp, hipStream_t s) {
+  if (a.nblk == 0 || sp.parts == 0 || sp.blk_pitch == 0) return hipErrorInvalidValue;
+  // (a part of at most 8 super-chunks is one or two passes of a workgroup's 16-byte units)
+  k_gather_parts<<<dim3(a.nblk * sp.parts, sp.span > 8 ? 4 : 1), dim3(256), 0, s>>>(a, src, sp);  // (the overload)
   return hipGetLastError();
 }
 

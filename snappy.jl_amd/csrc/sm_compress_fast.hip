@@ -216,6 +216,38 @@ hipError_t launch_compress_fast(const CompressArgs& a0, int mode, hipStream_t s)
   return launch_compress_sc(a, mode, s);
 }
 
+// The device batch calls: the screen over every block; one launch of the whole-block parse of the
+// blocks before the last bp.rem with those in bp.parts parts each on workgroups of their own behind
+// it; the parts gathered into the caller's slots (sm_internal.h, batch_parts_rule).  All on s.
+hipError_t launch_compress_batch_parts(const CompressArgs& a0, int mode, const BatchParts& bp, uint8_t* scratch,
+                                       hipStream_t s) {
+  if ((mode != 1 && mode != 2) || bp.rem == 0 || bp.rem > a0.nblk || bp.parts < 2 ||
+      bp.parts > kBlockScs / kPartMinScs || (bp.parts & (bp.parts - 1)) ||
+      (uint64_t)bp.rem * bp.parts > compress_grid() || !scratch)
+    return hipErrorInvalidValue;
+  CompressArgs a = a0;
+  a.screened = 1;
+  hipLaunchKernelGGL(k_literal_screen, dim3(a.nblk), dim3(kScrThreads), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const uint32_t whole = a.nblk - bp.rem;
+  a.nblk = whole;
+  CompressArgs r = a;  // the remainder blocks
+  r.nblk = bp.rem;
+  r.in_off += whole;
+  r.in_len += whole;
+  r.out_off += whole;
+  r.out_len += whole;
+  const uint32_t span = kBlockScs / bp.parts;
+  uint32_t* const part_len = reinterpret_cast<uint32_t*>(scratch + batch_parts_len_offset(compress_grid()));
+  const ScSpan sp{bp.parts, span, (uint64_t)span * kSpanSlot, part_len, (uint64_t)kBlockScs * kSpanSlot};
+  CompressArgs p = r;  // ... parsed into the scratch, by workgroups of the same launch
+  p.out = scratch;
+  e = launch_compress_sc_parts(a, p, sp, mode, s);
+  if (e != hipSuccess) return e;
+  return launch_batch_parts_gather(r, scratch, sp, s);
+}
+
 // the screen, then the parse in parts (k_compress_sc_span)
 hipError_t launch_compress_span(const CompressArgs& a0, int mode, const ScSpan& sp, hipStream_t s) {
   if (mode != 1 && mode != 2) return hipErrorInvalidValue;

@@ -36,7 +36,7 @@
 //  F. the wave waits for its staging slot (super-chunk k takes slot k mod 8);
 //  G. the lanes or their tokens and literal bytes into the zeroed slot, and
 //  W. the writer wave (wave 15) copies the staged super-chunks out in order at the running output
-//     offset with aligned 16-byte stores, and writes the block's length.
+//     offset with 16-byte stores (unaligned: the slot's own units), and writes the block's length.
 // Output is deterministic.
 #include "sm_device.h"
 #include "sm_internal.h"
@@ -61,7 +61,7 @@ static_assert((kScRing & (kScRing - 1)) == 0, "the span kernel's slot sequence n
 // bytes per slot: a super-chunk's output is at most 1,040 bytes (1,024 input bytes; every copy tag
 // is shorter than its copy, every maximal literal run adds a 1-byte tag, 2 or 3 bytes only for runs
 // over 60 bytes, of which at most 15 fit between copies), plus the 20-byte reach of the last piece's
-// or and the writer's one-unit read-ahead
+// or (and room a realigning writer's one-unit read-ahead once needed; the host sizes part pitches by it)
 constexpr uint32_t kScSlot = 1088;
 constexpr uint32_t kScThreads = 64 * kScW;
 constexpr uint32_t kScTabBits = 13;       // 8 K dword buckets of two u16 slots
@@ -340,14 +340,15 @@ struct ScToks {
   uint32_t n;
 };
 
-// The next block at or after `from` (stride gridDim.x) that the screen left for the parse, or nblk
-// (wave-uniform; 64 candidates per step)
-__device__ __attribute__((always_inline)) inline uint32_t sc_next_block(const CompressArgs& a, uint32_t from, uint32_t lane) {
-  for (uint32_t b0 = from; b0 < a.nblk; b0 += 64 * gridDim.x) {
-    const uint32_t bb = b0 + lane * gridDim.x;
+// The next block at or after `from` (stride g, the persistent workgroups) that the screen left for
+// the parse, or nblk (wave-uniform; 64 candidates per step)
+__device__ __attribute__((always_inline)) inline uint32_t sc_next_block(const CompressArgs& a, uint32_t from, uint32_t g,
+                                                                   uint32_t lane) {
+  for (uint32_t b0 = from; b0 < a.nblk; b0 += 64 * g) {
+    const uint32_t bb = b0 + lane * g;
     const bool todo = bb < a.nblk && (!a.screened || a.out_len[bb] == kScreenTodoSc);
     const uint64_t m = ballot(todo);
-    if (m) return b0 + ctz64(m) * gridDim.x;
+    if (m) return b0 + ctz64(m) * g;
   }
   return a.nblk;
 }
@@ -788,28 +789,22 @@ __device__ __attribute__((always_inline)) inline void sc_superchunk(ScLds& S, co
   __hip_atomic_store(&S.rsize[slot], total + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);  // (all lanes: same value)
 }
 
-// the staged bytes [0, len) of an LDS buffer (16-byte aligned) to global g (any alignment): aligned
-// 16-byte stores of byte-shifted units, bytes at the two partial ends (one wave)
+// the staged bytes [0, len) of an LDS buffer (16-byte aligned) to global g (any alignment): the
+// buffer's own 16-byte units, one ds_read_b128 each, stored at g + 16 u whatever its alignment (the
+// memory system splits a store that straddles a line; realigning the units to g's phase in
+// registers costs more VALU than that), then the last len % 16 bytes one
+// by one (one wave)
+typedef uint32_t __attribute__((ext_vector_type(4), aligned(1))) sc_u128u;
 __device__ __attribute__((always_inline)) inline void sc_copy_out(uint8_t* const g, const uint8_t* stg, uint32_t len,
                                                                  uint32_t lane) {
-  const uint32_t ad = (uint32_t)((uintptr_t)g & 15);
-  const uint32_t u0 = ad ? 1u : 0u, u1 = (len + ad) >> 4;  // full units [u0, u1); unit u = bytes [16u - ad, +16)
-  uint4* const g16 = reinterpret_cast<uint4*>(g - ad);
-  const uint32_t* const s32 = reinterpret_cast<const uint32_t*>(stg);
-  for (uint32_t u = u0 + lane; u < u1; u += 64) {
-    const uint32_t j = 16 * u - ad;  // staging offset of the unit: five aligned dwords from j & ~3, funnel shifts
-    const uint32_t* w = s32 + (j >> 2);  // (j + 20 <= len + 4: inside the slot)
-    const uint32_t r0 = w[0], r1 = w[1], r2 = w[2], r3 = w[3], r4 = w[4];
-    g16[u] = make_uint4(__builtin_amdgcn_alignbyte(r1, r0, j), __builtin_amdgcn_alignbyte(r2, r1, j),
-                        __builtin_amdgcn_alignbyte(r3, r2, j), __builtin_amdgcn_alignbyte(r4, r3, j));
+  const uint32_t nu = len >> 4;
+  for (uint32_t u = lane; u < nu; u += 64) {
+    const uint4 v = reinterpret_cast<const uint4*>(stg)[u];
+    sc_u128u x;
+    x.x = v.x, x.y = v.y, x.z = v.z, x.w = v.w;
+    *reinterpret_cast<sc_u128u*>(g + 16 * u) = x;
   }
-  const uint32_t nh = min(u0 ? 16 - ad : 0u, len);              // head bytes [0, nh)
-  const uint32_t tb = max(16 * u1 > ad ? 16 * u1 - ad : 0u, nh);  // tail bytes [tb, len)
-  const uint32_t nt = len - tb;
-  if (lane < nh + nt) {
-    const uint32_t jj = lane < nh ? lane : tb + (lane - nh);
-    g[jj] = stg[jj];
-  }
+  if (lane < (len & 15u)) g[16 * nu + lane] = stg[16 * nu + lane];
 }
 
 // The writer wave: the staged super-chunks k0..k1-1 in order, each at the running output offset (no
@@ -866,104 +861,6 @@ __device__ __attribute__((always_inline)) inline void sc_writer(ScLds& S, uint32
   if (lane == 0) *len_out = err ? 0xfff00000u | err : o;  // (an error mark: > any block's length)
 }
 
-// Persistent: one workgroup per CU walks blocks blockIdx.x, + gridDim.x, ...; each wave loads its
-// share of the next block into registers as soon as it runs out of super-chunks, so the HBM
-// latency of the staging hides behind the block's tail.
-template <int kDense>
-__global__ __launch_bounds__(kScThreads) void k_compress_sc(CompressArgs a) {
-  __shared__ __attribute__((aligned(16))) ScLds S;
-  const uint32_t tid = threadIdx.x;
-  const uint32_t wave = uniform(tid >> 6);
-  const uint32_t lane = tid & 63;
-  static_assert(kBlockSize / 16 / kScThreads == 4, "four 16-byte pieces per thread of a full block");
-  uint4 pf0, pf1, pf2, pf3;
-  // block b's length, source, and whether its bytes are in pf0..3 (a 16-byte aligned full block)
-  uint32_t b = sc_next_block(a, blockIdx.x, lane);
-  uint32_t n = 0;
-  const uint8_t* src = nullptr;
-  bool inpf = false;
-#define SC_FETCH(bb)                                                              \
-  {                                                                               \
-    n = (bb) < a.nblk ? a.in_len[bb] : 0u;                                        \
-    src = (bb) < a.nblk ? a.in + a.in_off[bb] : nullptr;                          \
-    inpf = (bb) < a.nblk && n == kBlockSize && ((uintptr_t)src & 15) == 0;        \
-    if (inpf) {                                                                   \
-      const uint4* s16 = reinterpret_cast<const uint4*>(src);                     \
-      pf0 = s16[tid];                                                             \
-      pf1 = s16[tid + kScThreads];                                                \
-      pf2 = s16[tid + 2 * kScThreads];                                            \
-      pf3 = s16[tid + 3 * kScThreads];                                            \
-    }                                                                             \
-  }
-  SC_FETCH(b)
-  while (b < a.nblk) {
-    uint8_t* const dst = a.out + a.out_off[b];
-    if (n > kBlockSize) {  // (uniform) not a block: error mark, next
-      if (tid == 0) a.out_len[b] = 0xffffffffu;
-      b = sc_next_block(a, b + gridDim.x, lane);
-      SC_FETCH(b)
-      continue;
-    }
-    // ---- stage the block, clear the table ----
-    if (inpf) {
-      uint4* d16 = reinterpret_cast<uint4*>(S.blk);
-      d16[tid] = pf0;
-      d16[tid + kScThreads] = pf1;
-      d16[tid + 2 * kScThreads] = pf2;
-      d16[tid + 3 * kScThreads] = pf3;
-    } else if (((uintptr_t)src & 15) == 0) {
-      const uint4* s16 = reinterpret_cast<const uint4*>(src);
-      uint4* d16 = reinterpret_cast<uint4*>(S.blk);
-      const uint32_t n16 = n >> 4;
-      for (uint32_t k = tid; k < n16; k += kScThreads) d16[k] = s16[k];
-      for (uint32_t k = (n & ~15u) + tid; k < n; k += kScThreads) S.blk[k] = src[k];
-    } else {
-      for (uint32_t k = tid; k < n; k += kScThreads) S.blk[k] = src[k];
-    }
-    if (tid < 64) S.blk[n + tid] = 0;  // bytes past the block read as zeros (never part of a match)
-    {
-      uint4* t16 = reinterpret_cast<uint4*>(S.T);
-      for (uint32_t k = tid; k < 4 * kScTabWords / 16; k += kScThreads) t16[k] = make_uint4(0, 0, 0, 0);
-    }
-    const uint32_t hv = a.header ? varint_len(n) : 0u;
-    if (tid < hv) dst[tid] = (uint8_t)(((n >> (7 * tid)) & 0x7f) | (tid + 1 < hv ? 0x80 : 0));
-    if (wave == 0) {  // the hand-off words (the previous block's users are past the barrier)
-      if (lane < kScRing) {
-        S.rsize[lane] = 0;
-        S.rseq[lane] = lane;
-      }
-      if (lane == 0) {
-        S.ins = 0;
-        S.next = 0;
-        S.err = 0;
-      }
-    }
-    // the block after this one (its stride scan now, its bytes when this wave runs out of work)
-    const uint32_t bn = sc_next_block(a, b + gridDim.x, lane);
-    __syncthreads();
-
-    const uint32_t nsc = (n + kScS - 1) / kScS;
-    if (wave == kScWorkers) {
-      __builtin_amdgcn_s_setprio(SC_WPRIO);  // (the writer's chain gates the slots)
-      sc_writer(S, n, dst, hv, 0, nsc, true, &a.out_len[b], lane);
-      __builtin_amdgcn_s_setprio(0);
-    } else {
-      // (no lane-0-only code here or at the end of a super-chunk: the compiler merged two such
-      // regions across the loop's back edge into a divergent loop that hung the wave)
-      for (;;) {
-        // every lane adds 1 (one ds_add of 64 after the atomic optimizer); lane 0 sees a multiple of 64
-        const uint32_t k = uniform(__hip_atomic_fetch_add(&S.next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >> 6;
-        if (k >= nsc) break;
-        sc_superchunk<kDense>(S, k, n, wave, lane);
-      }
-    }
-    SC_FETCH(bn)  // the next block's bytes, in flight behind the other waves' last super-chunks
-    __syncthreads();
-    b = bn;
-  }
-#undef SC_FETCH
-}
-
 // ---- one block in parts, for latency (sm_compress of small inputs) ------------------------
 // Item i = (block i / parts, part j = i % parts) parses super-chunks [j span, (j + 1) span) of its
 // block on its own workgroup, so a few blocks use many CUs.  The parse of a super-chunk depends on
@@ -974,16 +871,18 @@ __global__ __launch_bounds__(kScThreads) void k_compress_sc(CompressArgs a) {
 // and kept).  Everything after that is the whole-block kernel's code, so the output equals the
 // concatenation of the block's output in k_compress_sc (sans its literal fallback, which the
 // gather checks per block).  Item outputs at out + out_off[block] + j pitch, lengths in
-// part_len[i]; a block the screen emitted as a literal has that literal as its part 0.
+// part_len[i]; a block the screen emitted as a literal has that literal as its part 0.  For the
+// device batch calls' remainder blocks (sp.blk_pitch != 0) the parts lie in a scratch at a fixed
+// pitch per block, and such a literal -- already in the caller's slot -- is marked kPartScreened.
 template <int kDense>
-__global__ __launch_bounds__(kScThreads) void k_compress_sc_span(CompressArgs a, ScSpan sp) {
-  __shared__ __attribute__((aligned(16))) ScLds S;
+__device__ __attribute__((always_inline)) inline void sc_span_item(ScLds& S, const CompressArgs& a, const ScSpan& sp,
+                                                                  const uint32_t item) {
   const uint32_t tid = threadIdx.x;
   const uint32_t wave = uniform(tid >> 6);
   const uint32_t lane = tid & 63;
-  const uint32_t b = blockIdx.x / sp.parts, j = blockIdx.x % sp.parts;
+  const uint32_t b = item / sp.parts, j = item % sp.parts;
   if (b >= a.nblk) return;
-  uint32_t* const plen = sp.part_len + blockIdx.x;
+  uint32_t* const plen = sp.part_len + item;
   const uint32_t n = a.in_len[b];
   if (n > kBlockSize) {  // not a block: an error mark in part 0 (the gather refuses it)
     if (tid == 0) *plen = j == 0 ? 0xffffffffu : 0u;
@@ -993,11 +892,11 @@ __global__ __launch_bounds__(kScThreads) void k_compress_sc_span(CompressArgs a,
   const uint32_t k0 = j * sp.span, k1 = min(k0 + sp.span, nsc);
   const bool todo = !a.screened || a.out_len[b] == kScreenTodoSc;
   if (!todo || k0 >= k1) {  // a screened literal (part 0 is its output) or a part past the block
-    if (tid == 0) *plen = (!todo && j == 0) ? a.out_len[b] : 0u;
+    if (tid == 0) *plen = (!todo && j == 0) ? (sp.blk_pitch ? kPartScreened : a.out_len[b]) : 0u;
     return;
   }
   const uint8_t* const src = a.in + a.in_off[b];
-  uint8_t* const dst = a.out + a.out_off[b] + (uint64_t)j * sp.pitch;
+  uint8_t* const dst = a.out + (sp.blk_pitch ? b * sp.blk_pitch : a.out_off[b]) + (uint64_t)j * sp.pitch;
   // ---- stage the block, clear the table (as k_compress_sc) ----
   if (((uintptr_t)src & 15) == 0) {
     const uint4* s16 = reinterpret_cast<const uint4*>(src);
@@ -1075,6 +974,118 @@ __global__ __launch_bounds__(kScThreads) void k_compress_sc_span(CompressArgs a,
   }
 }
 
+template <int kDense>
+__global__ __launch_bounds__(kScThreads) void k_compress_sc_span(CompressArgs a, ScSpan sp) {
+  __shared__ __attribute__((aligned(16))) ScLds S;
+  sc_span_item<kDense>(S, a, sp, blockIdx.x);
+}
+
+// Persistent: one workgroup per CU walks blocks blockIdx.x, + g, ...; each wave loads its
+// share of the next block into registers as soon as it runs out of super-chunks, so the HBM
+// latency of the staging hides behind the block's tail.
+// The workgroups from g on (the device batch calls' remainder blocks, sp.parts != 0) are span
+// items of the batch r instead: the LDS holds one workgroup per CU, so the dispatcher places them
+// as the persistent workgroups finish -- the parts fill the CUs that run out of whole blocks, with
+// no launch between.
+template <int kDense>
+__global__ __launch_bounds__(kScThreads) void k_compress_sc(CompressArgs a, uint32_t g, CompressArgs r, ScSpan sp) {
+  __shared__ __attribute__((aligned(16))) ScLds S;
+  if (blockIdx.x >= g) {  // (uniform)
+    sc_span_item<kDense>(S, r, sp, blockIdx.x - g);
+    return;
+  }
+  const uint32_t tid = threadIdx.x;
+  const uint32_t wave = uniform(tid >> 6);
+  const uint32_t lane = tid & 63;
+  static_assert(kBlockSize / 16 / kScThreads == 4, "four 16-byte pieces per thread of a full block");
+  uint4 pf0, pf1, pf2, pf3;
+  // block b's length, source, and whether its bytes are in pf0..3 (a 16-byte aligned full block)
+  uint32_t b = sc_next_block(a, blockIdx.x, g, lane);
+  uint32_t n = 0;
+  const uint8_t* src = nullptr;
+  bool inpf = false;
+#define SC_FETCH(bb)                                                              \
+  {                                                                               \
+    n = (bb) < a.nblk ? a.in_len[bb] : 0u;                                        \
+    src = (bb) < a.nblk ? a.in + a.in_off[bb] : nullptr;                          \
+    inpf = (bb) < a.nblk && n == kBlockSize && ((uintptr_t)src & 15) == 0;        \
+    if (inpf) {                                                                   \
+      const uint4* s16 = reinterpret_cast<const uint4*>(src);                     \
+      pf0 = s16[tid];                                                             \
+      pf1 = s16[tid + kScThreads];                                                \
+      pf2 = s16[tid + 2 * kScThreads];                                            \
+      pf3 = s16[tid + 3 * kScThreads];                                            \
+    }                                                                             \
+  }
+  SC_FETCH(b)
+  while (b < a.nblk) {
+    uint8_t* const dst = a.out + a.out_off[b];
+    if (n > kBlockSize) {  // (uniform) not a block: error mark, next
+      if (tid == 0) a.out_len[b] = 0xffffffffu;
+      b = sc_next_block(a, b + g, g, lane);
+      SC_FETCH(b)
+      continue;
+    }
+    // ---- stage the block, clear the table ----
+    if (inpf) {
+      uint4* d16 = reinterpret_cast<uint4*>(S.blk);
+      d16[tid] = pf0;
+      d16[tid + kScThreads] = pf1;
+      d16[tid + 2 * kScThreads] = pf2;
+      d16[tid + 3 * kScThreads] = pf3;
+    } else if (((uintptr_t)src & 15) == 0) {
+      const uint4* s16 = reinterpret_cast<const uint4*>(src);
+      uint4* d16 = reinterpret_cast<uint4*>(S.blk);
+      const uint32_t n16 = n >> 4;
+      for (uint32_t k = tid; k < n16; k += kScThreads) d16[k] = s16[k];
+      for (uint32_t k = (n & ~15u) + tid; k < n; k += kScThreads) S.blk[k] = src[k];
+    } else {
+      for (uint32_t k = tid; k < n; k += kScThreads) S.blk[k] = src[k];
+    }
+    if (tid < 64) S.blk[n + tid] = 0;  // bytes past the block read as zeros (never part of a match)
+    {
+      uint4* t16 = reinterpret_cast<uint4*>(S.T);
+      for (uint32_t k = tid; k < 4 * kScTabWords / 16; k += kScThreads) t16[k] = make_uint4(0, 0, 0, 0);
+    }
+    const uint32_t hv = a.header ? varint_len(n) : 0u;
+    if (tid < hv) dst[tid] = (uint8_t)(((n >> (7 * tid)) & 0x7f) | (tid + 1 < hv ? 0x80 : 0));
+    if (wave == 0) {  // the hand-off words (the previous block's users are past the barrier)
+      if (lane < kScRing) {
+        S.rsize[lane] = 0;
+        S.rseq[lane] = lane;
+      }
+      if (lane == 0) {
+        S.ins = 0;
+        S.next = 0;
+        S.err = 0;
+      }
+    }
+    // the block after this one (its stride scan now, its bytes when this wave runs out of work)
+    const uint32_t bn = sc_next_block(a, b + g, g, lane);
+    __syncthreads();
+
+    const uint32_t nsc = (n + kScS - 1) / kScS;
+    if (wave == kScWorkers) {
+      __builtin_amdgcn_s_setprio(SC_WPRIO);  // (the writer's chain gates the slots)
+      sc_writer(S, n, dst, hv, 0, nsc, true, &a.out_len[b], lane);
+      __builtin_amdgcn_s_setprio(0);
+    } else {
+      // (no lane-0-only code here or at the end of a super-chunk: the compiler merged two such
+      // regions across the loop's back edge into a divergent loop that hung the wave)
+      for (;;) {
+        // every lane adds 1 (one ds_add of 64 after the atomic optimizer); lane 0 sees a multiple of 64
+        const uint32_t k = uniform(__hip_atomic_fetch_add(&S.next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) >> 6;
+        if (k >= nsc) break;
+        sc_superchunk<kDense>(S, k, n, wave, lane);
+      }
+    }
+    SC_FETCH(bn)  // the next block's bytes, in flight behind the other waves' last super-chunks
+    __syncthreads();
+    b = bn;
+  }
+#undef SC_FETCH
+}
+
 hipError_t launch_compress_sc_span(const CompressArgs& a, int mode, const ScSpan& sp, hipStream_t s) {
   if (sp.parts == 0 || sp.span == 0 || sp.parts * sp.span < (kBlockSize + kScS - 1) / kScS ||
       sp.pitch < (uint64_t)sp.span * kScSlot)
@@ -1089,9 +1100,8 @@ hipError_t launch_compress_sc_span(const CompressArgs& a, int mode, const ScSpan
 }
 
 
-// mode 1 (SM_MODE_FAST): the more recent 4-byte match per position; mode 2 (SM_MODE_FAST_DENSE): the
-// longer of the two candidates over 16 bytes (smaller output, about 15% slower)
-hipError_t launch_compress_sc(const CompressArgs& a, int mode, hipStream_t s) {
+// the current device's CU count (cached per device)
+uint32_t compress_grid() {
   static uint32_t ncu_cache[64] = {};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
@@ -1102,12 +1112,30 @@ hipError_t launch_compress_sc(const CompressArgs& a, int mode, hipStream_t s) {
     ncu = (uint32_t)v;
     __atomic_store_n(&ncu_cache[dev], ncu, __ATOMIC_RELAXED);
   }
-  const uint32_t grid = min(a.nblk, ncu);  // one workgroup per CU (the LDS holds one)
+  return ncu;
+}
+
+// mode 1 (SM_MODE_FAST): the more recent 4-byte match per position; mode 2 (SM_MODE_FAST_DENSE): the
+// longer of the two candidates over 16 bytes (smaller output, about 15% slower).  The blocks of a
+// by the persistent workgroups and, in the same launch, the blocks of r in sp.parts parts each
+// (sp.parts == 0: none; sp.blk_pitch != 0, see ScSpan) -- either batch may be empty.
+hipError_t launch_compress_sc_parts(const CompressArgs& a, const CompressArgs& r, const ScSpan& sp, int mode,
+                                    hipStream_t s) {
+  const uint32_t g = min(a.nblk, compress_grid());  // one workgroup per CU (the LDS holds one)
+  const uint32_t items = sp.parts ? r.nblk * sp.parts : 0u;
+  if (items && (sp.span == 0 || sp.parts * sp.span < (kBlockSize + kScS - 1) / kScS ||
+                sp.pitch < (uint64_t)sp.span * kScSlot || sp.blk_pitch < sp.parts * sp.pitch))
+    return hipErrorInvalidValue;
+  if (g + items == 0) return hipSuccess;
   if (mode == 2)
-    hipLaunchKernelGGL(k_compress_sc<1>, dim3(grid), dim3(kScThreads), 0, s, a);
+    hipLaunchKernelGGL(k_compress_sc<1>, dim3(g + items), dim3(kScThreads), 0, s, a, g, r, sp);
   else
-    hipLaunchKernelGGL(k_compress_sc<0>, dim3(grid), dim3(kScThreads), 0, s, a);
+    hipLaunchKernelGGL(k_compress_sc<0>, dim3(g + items), dim3(kScThreads), 0, s, a, g, r, sp);
   return hipGetLastError();
+}
+
+hipError_t launch_compress_sc(const CompressArgs& a, int mode, hipStream_t s) {
+  return launch_compress_sc_parts(a, CompressArgs{}, ScSpan{}, mode, s);
 }
 
 }  // namespace sm

@@ -145,15 +145,54 @@ struct ScSpan {
   uint32_t parts, span;
   uint64_t pitch;
   uint32_t* part_len;
+  // blk_pitch != 0 (the device batch calls' remainder blocks, launch_compress_batch_parts): block b's parts are
+  // at out + b blk_pitch + j pitch (out_off is the caller's and is not read by the span kernel), and
+  // a block the screen emitted as a literal -- it is in the caller's slot already -- has kPartScreened
+  // as its part 0's length
+  uint64_t blk_pitch = 0;
 };
+constexpr uint32_t kPartScreened = 0xffeffffdu;  // (below the error marks, above any length)
 hipError_t launch_compress_span(const CompressArgs& a, int mode, const ScSpan& sp, hipStream_t s);
 hipError_t launch_compress_sc_span(const CompressArgs& a, int mode, const ScSpan& sp, hipStream_t s);  // (no screen)
+// the whole-block parse of a's blocks and, on workgroups behind the persistent ones in the same
+// launch, r's blocks in sp.parts parts (sp.blk_pitch != 0; sp.parts == 0: none)
+hipError_t launch_compress_sc_parts(const CompressArgs& a, const CompressArgs& r, const ScSpan& sp, int mode,
+                                    hipStream_t s);
 // The parts of nblk (<= 256 / parts) blocks behind one another into dst (a block whose parts sum to
 // more than one literal of the block -- the whole-block parse's fallback -- as that literal, from
 // in): tot[0] = the total, tot[1] = 1 on an error mark or an over-long part (nothing copied).
 hipError_t launch_parts_gather(const uint8_t* src, const uint64_t* out_off, const ScSpan& sp, const uint8_t* in,
                                const uint64_t* in_off, const uint32_t* in_len, uint32_t nblk, uint64_t* tot,
                                uint8_t* dst, hipStream_t s);
+// The device batch calls (sm_compress_batch_device, sm_compress_fragments_device; fast modes): the
+// persistent whole-block kernel runs ceil(nblk / grid) rounds of blocks, the last of them on
+// nblk % grid workgroups only.  When that remainder is at most half the grid, its blocks are parsed
+// in `parts` parts each on workgroups of their own (span items of the same launch) and joined into the
+// caller's slots (k_gather_parts, the batch overload): the same bytes and lengths.
+constexpr uint32_t kBlockScs = 64;       // 1 KiB super-chunks of a 64 KiB block
+constexpr uint32_t kPartMinScs = 4;      // a part is at least this many super-chunks
+struct BatchParts {
+  uint32_t rem;    // the last `rem` blocks are parsed in parts (0: none, the whole-block kernel takes all)
+  uint32_t parts;  // ... in this many parts each: the largest power of two with rem * parts <= grid
+};
+inline BatchParts batch_parts_rule(uint32_t nblk, uint32_t grid) {
+  const uint32_t r = grid ? nblk % grid : 0u;  // (nblk < grid: every block)
+  if (r == 0 || r > grid / 2) return {0u, 0u};
+  uint32_t p = 2;
+  while (p < kBlockScs / kPartMinScs && r * (2 * p) <= grid) p *= 2;
+  return {r, p};
+}
+// the scratch launch_compress_batch_parts needs on a device of `grid` CUs: the parts' slots (16-byte
+// aligned), then their lengths
+inline size_t batch_parts_len_offset(uint32_t grid) { return (size_t)(grid / 2) * kBlockScs * kSpanSlot; }
+inline size_t batch_parts_scratch(uint32_t grid) { return batch_parts_len_offset(grid) + 4 * (size_t)grid; }
+uint32_t compress_grid();  // the whole-block kernel's workgroup count for large batches: the device's CUs
+// launch_compress for modes 1 and 2 with the last bp.rem blocks in parts (bp from batch_parts_rule
+// with compress_grid(); bp.rem != 0); scratch: batch_parts_scratch(compress_grid()) bytes, in use
+// until the launches have run
+hipError_t launch_compress_batch_parts(const CompressArgs& a, int mode, const BatchParts& bp, uint8_t* scratch,
+                                       hipStream_t s);
+hipError_t launch_batch_parts_gather(const CompressArgs& a, const uint8_t* src, const ScSpan& sp, hipStream_t s);
 hipError_t launch_frag_gather(const uint8_t* src, const uint64_t* src_off, const uint32_t* out_len,
                               const uint32_t* in_len, uint32_t nfrag, uint64_t* tot, uint8_t* dst, hipStream_t s);
 // a sharded stream's fragments at their global offsets (sm_place_fragments_device, k_place)
