@@ -1,0 +1,274 @@
+"""Batches of raw Snappy streams of any length over include/snappy_mi355x_multi.h --
+libsnappy_mi355x_multi.so, the companion of libsnappy_mi355x.so.
+
+    compress_streams(list_of_bytes)         -> list of streams (and the fragment index when asked)
+    uncompress_streams(streams, index=...)  -> (list of bytes-or-None, status array)
+
+and, on torch tensors resident in HBM: compress_streams_device, uncompress_streams_device (no host
+synchronisation), last_indexed.
+
+A stream of at most 64 KiB is what compress_batch gives, a longer one what compress gives; the
+index (frag_first, frag_pos) names every 64 KiB fragment's offset in its stream, and with it the
+decoder runs every fragment of every stream in parallel.  It is a hint: a wrong index costs time,
+never correctness (the stream is then decoded in stream order).
+
+The package imports without this library; it is loaded on the first call here.  No CPU fallback:
+every codec call needs both HIP libraries and a device.
+"""
+import ctypes
+import os
+import threading
+
+import numpy as np
+
+from . import HERE, MODES, SnappyError, _mode, _ptr, _stream, pack_blocks
+
+LIB_PATH = os.path.join(HERE, "libsnappy_mi355x_multi.so")
+BLOCK = 65536
+MAX_INPUT = 0x7FFFFFFF
+
+# exported symbols of include/snappy_mi355x_multi.h (checked by tests/test_multi_host.py)
+MULTI_ABI_SYMBOLS = (
+    "smm_ctx_create", "smm_ctx_destroy", "smm_version", "smm_status_message", "smm_fragment_count", "smm_scratch_bytes",
+    "smm_index_check", "smm_compress_device", "smm_uncompress_device", "smm_ctx_last_indexed", "smm_compress",
+    "smm_uncompress",
+)
+
+_lib = None
+_ctx = {}
+_ctx_lock = threading.Lock()
+
+
+def library_path():
+    return LIB_PATH
+
+
+def lib():
+    """Load libsnappy_mi355x_multi.so (raises OSError if it was not built)."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise OSError("libsnappy_mi355x_multi.so not built (run __graft_entry__.build())")
+        L = ctypes.CDLL(LIB_PATH)
+        vp, sz, i32, u32, u64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64
+        L.smm_ctx_create.restype = vp
+        L.smm_ctx_create.argtypes = [ctypes.c_int]
+        L.smm_ctx_destroy.restype = None
+        L.smm_ctx_destroy.argtypes = [vp]
+        L.smm_version.restype = ctypes.c_char_p
+        L.smm_version.argtypes = []
+        L.smm_status_message.restype = ctypes.c_char_p
+        L.smm_status_message.argtypes = [i32]
+        L.smm_fragment_count.restype = u32
+        L.smm_fragment_count.argtypes = [u64]
+        L.smm_scratch_bytes.restype = sz
+        L.smm_scratch_bytes.argtypes = [u32, u32]
+        L.smm_index_check.restype = i32
+        L.smm_index_check.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp]
+        L.smm_compress_device.restype = i32
+        L.smm_compress_device.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, ctypes.c_int, vp]
+        L.smm_uncompress_device.restype = i32
+        L.smm_uncompress_device.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.smm_ctx_last_indexed.restype = ctypes.c_int
+        L.smm_ctx_last_indexed.argtypes = [vp]
+        L.smm_compress.restype = i32
+        L.smm_compress.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, ctypes.c_int]
+        L.smm_uncompress.restype = i32
+        L.smm_uncompress.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+        _lib = L
+    return _lib
+
+
+def version():
+    return lib().smm_version().decode()
+
+
+def status_message(code):
+    return lib().smm_status_message(int(code)).decode()
+
+
+def context(device=0):
+    """Per-device smm_ctx (an sm_ctx of its own plus scratch).  Raises if no device is usable."""
+    with _ctx_lock:
+        c = _ctx.get(device)
+        if c is None:
+            c = lib().smm_ctx_create(device)
+            if not c:
+                raise SnappyError(32, "no usable HIP device %d for snappy_mi355x_multi" % device)
+            _ctx[device] = c
+    return c
+
+
+def fragment_count(n):
+    """ceil(n / 65536): the 64 KiB fragments (and index entries) of an n-byte input."""
+    return lib().smm_fragment_count(int(n))
+
+
+def scratch_bytes(nstreams, max_fragments):
+    return lib().smm_scratch_bytes(int(nstreams), int(max_fragments))
+
+
+def frag_first_of(lengths):
+    """The index's frag_first for inputs of these lengths, on the host: the exclusive scan of
+    fragment_count (nstreams + 1 entries)."""
+    counts = [(int(n) + BLOCK - 1) // BLOCK if int(n) <= MAX_INPUT else 0 for n in lengths]
+    return np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.uint32)
+
+
+def _addr(a):
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def index_check(streams, index, capacities=None, max_fragments=None):
+    """Which streams the decoder would take by fragments given this index (structure only, on the
+    host; smm_index_check): a uint8 array."""
+    buf, in_off, in_len = pack_blocks(streams)
+    cap = _capacities(streams, capacities)
+    first = pos = None
+    if index is not None:
+        first = np.ascontiguousarray(index[0], dtype=np.uint32)
+        pos = np.ascontiguousarray(index[1], dtype=np.uint32)
+    if max_fragments is None:
+        max_fragments = pos.size if pos is not None else 0
+    if pos is not None and pos.size < max_fragments:
+        raise ValueError("frag_pos is shorter than max_fragments")
+    out = np.zeros(len(streams), np.uint8)
+    keep = np.zeros(1, np.uint8)
+    st = lib().smm_index_check(_addr(buf) or keep.ctypes.data, _addr(in_off), _addr(in_len), len(streams),
+                               int(max_fragments), _addr(cap), first.ctypes.data if first is not None else None,
+                               (_addr(pos) or keep.ctypes.data) if pos is not None else None, _addr(out))
+    if st:
+        raise SnappyError(st)
+    return out
+
+
+# ---- host buffers -----------------------------------------------------------------------
+
+def _slots(in_len):
+    caps = (32 + in_len.astype(np.uint64) + in_len.astype(np.uint64) // 6 + 15) // 16 * 16
+    offs = np.zeros(in_len.size, dtype=np.uint64)
+    if in_len.size > 1:
+        offs[1:] = np.cumsum(caps[:-1], dtype=np.uint64)
+    return offs, caps
+
+
+def compress_streams(datas, mode="fast", device=0, return_index=False):
+    """Compress independent inputs of any length (each at most 2^31 - 1 bytes) in one call on the
+    GPU; returns a list of raw Snappy streams (bytes), and with return_index also the index
+    (frag_first, frag_pos) as uint32 arrays.  Raises SnappyError with the first failing stream's
+    status."""
+    datas = [bytes(d) if not isinstance(d, bytes) else d for d in datas]
+    n = len(datas)
+    if any(len(d) > MAX_INPUT for d in datas):
+        raise SnappyError(16)
+    buf, in_off, in_len = pack_blocks(datas)
+    first = np.zeros(n + 1, np.uint32)
+    entries = int(frag_first_of(in_len)[-1])
+    pos = np.zeros(max(entries, 1), np.uint32)
+    outs = []
+    if n:
+        out_off, caps = _slots(in_len)
+        out = np.empty(int(out_off[-1] + caps[-1]), dtype=np.uint8)
+        out_len = np.zeros(n, np.uint32)
+        status = np.zeros(n, np.int32)
+        keep = np.zeros(1, np.uint8)
+        st = lib().smm_compress(context(device), _addr(buf) or keep.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, n,
+                                out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data, status.ctypes.data,
+                                first.ctypes.data if return_index else None, pos.ctypes.data if return_index else None,
+                                _mode(mode))
+        if st:
+            raise SnappyError(st)
+        if status.any():
+            raise SnappyError(int(status[np.nonzero(status)[0][0]]))
+        outs = [out[int(o): int(o) + int(l)].tobytes() for o, l in zip(out_off, out_len)]
+    if return_index:
+        return outs, (first, pos[:entries])
+    return outs
+
+
+def _capacities(streams, capacities):
+    if capacities is None:
+        from . import parse32
+        capacities = []
+        for s in streams:
+            try:
+                capacities.append(parse32(s)[0])
+            except SnappyError:
+                capacities.append(0)
+    return np.array(capacities, dtype=np.uint32)
+
+
+def uncompress_streams(streams, index=None, capacities=None, device=0):
+    """Decode independent raw Snappy streams of any length in one call on the GPU; returns (list
+    of bytes-or-None, status array).  index: the (frag_first, frag_pos) compress_streams returned
+    for exactly these streams -- a hint that lets every fragment decode in parallel."""
+    n = len(streams)
+    if n == 0:
+        return [], np.zeros(0, np.int32)
+    buf, in_off, in_len = pack_blocks(streams)
+    cap = _capacities(streams, capacities)
+    out_off = np.zeros(n, dtype=np.uint64)
+    if n > 1:
+        out_off[1:] = np.cumsum(cap[:-1].astype(np.uint64), dtype=np.uint64)
+    out = np.empty(max(int(cap.astype(np.uint64).sum()), 1), dtype=np.uint8)
+    out_len = np.zeros(n, np.uint32)
+    status = np.zeros(n, np.int32)
+    first = pos = None
+    if index is not None:
+        first = np.ascontiguousarray(index[0], dtype=np.uint32)
+        pos = np.ascontiguousarray(index[1], dtype=np.uint32)
+        if first.size != n + 1 or pos.size < int(first[-1]):
+            raise ValueError("index does not fit the streams")
+        if pos.size == 0:
+            pos = np.zeros(1, np.uint32)
+    keep = np.zeros(1, np.uint8)
+    st = lib().smm_uncompress(context(device), _addr(buf) or keep.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, n,
+                              out.ctypes.data, out_off.ctypes.data, cap.ctypes.data, out_len.ctypes.data,
+                              status.ctypes.data, first.ctypes.data if first is not None else None,
+                              pos.ctypes.data if pos is not None else None)
+    if st:
+        raise SnappyError(st)
+    res = [out[int(o): int(o) + int(l)].tobytes() if s == 0 else None for o, l, s in zip(out_off, out_len, status)]
+    return res, status
+
+
+# ---- device API (torch tensors resident in HBM; asynchronous on `stream`) ---------------------
+
+def _opt(t):
+    return _ptr(t) if t is not None else None
+
+
+def compress_streams_device(d_in, d_in_off, d_in_len, max_fragments, d_out, d_out_off, d_out_len, d_status,
+                            d_frag_first=None, d_frag_pos=None, mode="fast", stream=None, device=None):
+    """smm_compress_device: d_in / d_out uint8, d_in_off / d_out_off int64, d_in_len / d_out_len /
+    d_status int32 CUDA tensors (the C ABI's unsigned values, bit for bit); the index tensors
+    (int32, nstreams + 1 and max_fragments entries) both or neither.  Nothing is synchronised."""
+    dev = d_out.device.index if device is None else device
+    st = lib().smm_compress_device(context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), d_in_len.numel(),
+                                   int(max_fragments), _ptr(d_out), _ptr(d_out_off), _ptr(d_out_len), _ptr(d_status),
+                                   _opt(d_frag_first), _opt(d_frag_pos), _mode(mode), ctypes.c_void_p(_stream(stream, dev)))
+    if st:
+        raise SnappyError(st)
+
+
+def uncompress_streams_device(d_in, d_in_off, d_in_len, max_fragments, d_out, d_out_off, d_out_cap, d_out_len, d_status,
+                              d_frag_first=None, d_frag_pos=None, stream=None, device=None):
+    """smm_uncompress_device (tensor types as in compress_streams_device).  max_fragments: the
+    entries of d_frag_pos.  Nothing is synchronised."""
+    dev = d_out.device.index if device is None else device
+    st = lib().smm_uncompress_device(context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), d_in_len.numel(),
+                                     int(max_fragments), _ptr(d_out), _ptr(d_out_off), _ptr(d_out_cap), _ptr(d_out_len),
+                                     _ptr(d_status), _opt(d_frag_first), _opt(d_frag_pos),
+                                     ctypes.c_void_p(_stream(stream, dev)))
+    if st:
+        raise SnappyError(st)
+
+
+def last_indexed(device=0):
+    """Diagnostic: how many streams the device's last uncompress call decoded by fragments (waits
+    for the device); -1 before the first call."""
+    return int(lib().smm_ctx_last_indexed(context(device)))
+
+
+__all__ = ["MULTI_ABI_SYMBOLS", "MODES", "compress_streams", "uncompress_streams", "compress_streams_device",
+           "uncompress_streams_device", "fragment_count", "scratch_bytes", "frag_first_of", "index_check", "last_indexed"]
