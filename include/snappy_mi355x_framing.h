@@ -97,6 +97,33 @@ sm_status smf_index(const uint8_t* buf, size_t n, const smf_chunks* chunks, uint
 /* The stream's total uncompressed length, from its chunk headers alone (no CRC or payload check). */
 sm_status smf_uncompressed_length(const uint8_t* buf, size_t n, size_t* result);
 
+/* ---- the seek index (host helpers, no device needed) ------------------------------- */
+/* The seek index of a framed stream is its smf_chunks arrays plus chunk_off: nchunks + 1 u64, the
+ * exclusive scan of ulen, so chunk c holds bytes [chunk_off[c], chunk_off[c + 1]) of the
+ * uncompressed content and chunk_off[nchunks] is the total length.
+ * smf_chunk_offsets fills chunk_off from ulen (host arrays). */
+sm_status smf_chunk_offsets(const uint32_t* ulen, uint32_t nchunks, uint64_t* chunk_off);
+/* The chunks that bytes [lo, lo + len) touch in a stream of full 64 KiB chunks:
+ * floor((lo + len - 1) / 65536) - floor(lo / 65536) + 1, or 0 for len == 0 (and for lo + len
+ * overflowing).  Exact for streams of this library's encoder.  A foreign stream may have smaller
+ * or empty chunks, so a range of it may touch more: there the caller bounds max_range_chunks
+ * itself (smf_range_plan counts, or nchunks per range always suffices). */
+uint64_t smf_range_chunk_count(uint64_t lo, uint64_t len);
+/* The plan of smf_uncompress_ranges_device over HOST arrays, by the rules the device runs: for
+ * range r, first[r] / count[r] = the chunks [first, first + count) that get a slot (from the chunk
+ * holding lo to the chunk holding lo + len - 1; empty chunks in between keep their slot and are
+ * passed over), and status[r] = SM_OK, SM_ERR_ARGUMENT for a range that leaves the stream, or
+ * SM_ERR_ARGUMENT for a touched entry that fails its checks (below) -- what is known before any
+ * byte is decoded.  *total = the sum of the counts.  n = the framed stream's length.  Returns
+ * SM_OK, or SM_BUFFER_TOO_SMALL when *total > max_range_chunks (every status[r] is then
+ * SM_ERR_ARGUMENT, as on the device).  first / count / status / total may each be NULL. */
+sm_status smf_range_plan(const smf_chunks* chunks, const uint64_t* chunk_off, uint32_t nchunks, uint64_t n,
+                         const uint64_t* lo, const uint64_t* len, uint32_t nranges, uint32_t max_range_chunks,
+                         uint32_t* first, uint32_t* count, int32_t* status, uint64_t* total);
+/* Bytes of ctx scratch a smf_uncompress_ranges_device call with these bounds needs: the per-slot
+ * arrays and 2 * nranges edge slots of 65536 bytes. */
+size_t smf_range_scratch_bytes(uint32_t nranges, uint32_t max_range_chunks);
+
 /* ---- context ---------------------------------------------------------------------- */
 /* NULL without a usable device. */
 smf_ctx* smf_ctx_create(int device);
@@ -152,7 +179,63 @@ sm_status smf_uncompress_chunks_device(smf_ctx* ctx, const uint8_t* d_in, const 
 sm_status smf_uncompress_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t out_capacity,
                                 uint64_t* d_out_len, int32_t* d_status, void* stream);
 
+/* d_chunk_off[0, nchunks] (device) = the exclusive scan of d_ulen[0, nchunks) (device): completes
+ * an index that smf_index_device produced, of a foreign stream too.  One kernel, asynchronous. */
+sm_status smf_chunk_offsets_device(smf_ctx* ctx, const uint32_t* d_ulen, uint32_t nchunks, uint64_t* d_chunk_off,
+                                   void* stream);
+
+/* smf_compress_device that also hands out the seek index of the stream it packs, so that nobody
+ * has to walk it: the framed bytes, *d_out_len and *d_status are exactly smf_compress_device's;
+ * d_chunks (a HOST struct of DEVICE arrays of max_chunks entries), d_chunk_off (device,
+ * max_chunks + 1) and *d_nchunks (device) receive what smf_index_device followed by
+ * smf_chunk_offsets_device would give for it, entry for entry.  max_chunks < ceil(n / 65536)
+ * returns SM_BUFFER_TOO_SMALL and launches nothing.  With *d_status = SM_ERR_DEVICE the index is
+ * unspecified and *d_nchunks = 0.  No host synchronisation (scratch growth as smf_compress_device). */
+sm_status smf_compress_indexed_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, uint8_t* d_out,
+                                      uint64_t out_capacity, uint64_t* d_out_len, int32_t* d_status, int mode,
+                                      const smf_chunks* d_chunks, uint64_t* d_chunk_off, uint32_t max_chunks,
+                                      uint32_t* d_nchunks, void* stream);
+
+/* Ranged decode, batched: range r asks for bytes [d_lo[r], d_lo[r] + d_len[r]) of the uncompressed
+ * content of the indexed stream d_in[0, n), written to d_out + d_out_off[r].  Only the chunks a
+ * range touches -- those with ulen > 0 whose [chunk_off[c], chunk_off[c + 1]) meets it -- are
+ * decoded, each whole and with its CRC checked whole; damage elsewhere is not seen.
+ *   d_len[r] == 0: nothing is touched, SM_OK, d_out_len[r] = 0.
+ *   lo + len overflowing or past chunk_off[nchunks]: SM_ERR_ARGUMENT, d_out_len[r] = 0, nothing written.
+ *   else d_range_status[r] = SM_OK and d_out_len[r] = len with the bytes decode(stream)[lo : lo + len],
+ *   or the status of the first failing touched chunk in stream order (what
+ *   smf_uncompress_chunks_device reports for it: the raw decoder's SM_ERR_*, SMF_ERR_CRC) and
+ *   d_out_len[r] = 0; a failing range's bytes are unspecified but stay inside its own output.
+ * The index is an untrusted hint: no value in it causes a read outside d_in[0, n) or a write
+ * outside a range's [d_out_off[r], + len).  A touched entry fails its chunk with SM_ERR_ARGUMENT
+ * unless type <= 1, ulen <= 65536, chunk_off[c + 1] - chunk_off[c] == ulen, pay_off + pay_len <= n
+ * without overflow, for a 0x01 chunk pay_len == ulen, and, lying only partly inside the range, it
+ * is the range's first or last chunk.  chunk_off should be non-decreasing; the searches are
+ * bounded by nchunks whatever it holds.
+ * max_range_chunks: the caller's bound on the slots summed over all ranges (smf_range_plan's
+ * counts; smf_range_chunk_count for this library's streams); it sizes the launches and the ctx
+ * scratch (smf_range_scratch_bytes).  If the device plan counts more, every d_range_status[r] =
+ * SM_ERR_ARGUMENT, every d_out_len[r] = 0 and nothing is written to d_out.
+ * A chunk that lies wholly inside its range decodes straight into d_out; the at most two others of
+ * a range decode into ctx-owned edge slots, of which the covered bytes are copied out.  Chunks that
+ * several ranges touch are decoded once per range.  Ranges whose outputs overlap race.
+ * nchunks and nranges are at most 2^31 - 1.  No host synchronisation, except when the ctx's
+ * scratch has to grow. */
+sm_status smf_uncompress_ranges_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, const smf_chunks* d_chunks,
+                                       const uint64_t* d_chunk_off, uint32_t nchunks, const uint64_t* d_lo,
+                                       const uint64_t* d_len, uint32_t nranges, uint32_t max_range_chunks,
+                                       uint8_t* d_out, const uint64_t* d_out_off, uint64_t* d_out_len,
+                                       int32_t* d_range_status, void* stream);
+
 /* ---- host memory (H2D + the device path + D2H, synchronous) ------------------------- */
+/* Bytes [lo, lo + len) of the uncompressed content of a framed stream in host memory.  The stream
+ * is indexed on the host; only the bytes from the first touched chunk's payload to the last
+ * touched chunk's end are uploaded, and smf_uncompress_ranges_device decodes them.
+ * *out_len: in = capacity (< len: SM_BUFFER_TOO_SMALL, *out_len = len), out = bytes written.
+ * Returns the walk's structural error as smf_uncompress does, also when it lies behind the range;
+ * SM_ERR_ARGUMENT for a range that leaves the stream; else the range's status. */
+sm_status smf_uncompress_range(smf_ctx* ctx, const uint8_t* framed, size_t n, uint64_t lo, uint64_t len,
+                               uint8_t* output, size_t* out_len);
 /* *framed_length: in = capacity (>= smf_max_framed_length(n)), out = bytes written. */
 sm_status smf_compress(smf_ctx* ctx, const uint8_t* input, size_t n, uint8_t* framed, size_t* framed_length, int mode);
 /* The stream is indexed on the host, decoded and CRC-checked on the device.

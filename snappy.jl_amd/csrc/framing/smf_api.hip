@@ -1,6 +1,7 @@
 // smf_api.hip -- C ABI of the framing format (include/snappy_mi355x_framing.h) over the raw
 // codec's public batched device calls (libsnappy_mi355x.so, linked by name) and the kernels of
-// smf_kernels.hip.  The host-only entry points live in smf_host.cpp.
+// smf_kernels.hip and smf_range.hip (the seek index and the ranged decode).  The host-only entry
+// points live in smf_host.cpp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -77,6 +78,8 @@ struct smf_ctx {
   DevBuf dmeta;                  // decode: per-chunk arrays
   DevBuf idx;                    // a stream's index (smf_uncompress_device, smf_uncompress)
   DevBuf io_in, io_out, res;     // the host-buffer calls' staging; small results
+  DevBuf rmeta, redge;           // ranged decode: per-range and per-slot arrays, the edge slots
+  DevBuf roff;                   // smf_uncompress_range: the index slice's chunk_off
   std::mutex mu;                 // serialises the host-buffer entry points
 };
 
@@ -150,7 +153,8 @@ void smf_ctx_destroy(smf_ctx* ctx) {
   {
     DeviceGuard g(ctx->device);
     (void)hipDeviceSynchronize();  // (the *_device calls ran on the callers' streams)
-    for (DevBuf* b : {&ctx->lut, &ctx->cmeta, &ctx->slots, &ctx->dmeta, &ctx->idx, &ctx->io_in, &ctx->io_out, &ctx->res})
+    for (DevBuf* b : {&ctx->lut, &ctx->cmeta, &ctx->slots, &ctx->dmeta, &ctx->idx, &ctx->io_in, &ctx->io_out, &ctx->res,
+                      &ctx->rmeta, &ctx->redge, &ctx->roff})
       b->release();
   }
   sm_ctx_destroy(ctx->sm);
@@ -168,13 +172,25 @@ sm_status smf_crc32c_batch_device(smf_ctx* ctx, const uint8_t* d_in, const uint6
   return SM_OK;
 }
 
-sm_status smf_compress_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t out_capacity,
-                              uint64_t* d_out_len, int32_t* d_status, int mode, void* stream) {
+// smf_compress_device; with d_chunk_off also the encoder's index (smf_compress_indexed_device)
+static sm_status compress_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t out_capacity,
+                                 uint64_t* d_out_len, int32_t* d_status, int mode, const smf_chunks* d_chunks,
+                                 uint64_t* d_chunk_off, uint32_t max_chunks, uint32_t* d_nchunks, void* stream) {
   if (!ctx || !d_out || !d_out_len || !d_status || (n && !d_in)) return SM_ERR_ARGUMENT;
   if (mode != SM_MODE_REFERENCE && mode != SM_MODE_FAST && mode != SM_MODE_FAST_DENSE) return SM_ERR_ARGUMENT;
   const uint64_t nblk64 = (n + smf::kBlock - 1) / smf::kBlock;
   if (nblk64 > 0x7fffffffull) return SM_ERR_INPUT_TOO_LARGE;
   if (out_capacity < smf_max_framed_length(n)) return SM_BUFFER_TOO_SMALL;
+  smf_chunks ich{nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (d_chunk_off) {
+    if (!d_nchunks) return SM_ERR_ARGUMENT;
+    if (max_chunks < nblk64) return SM_BUFFER_TOO_SMALL;
+    if (nblk64) {
+      if (!d_chunks) return SM_ERR_ARGUMENT;
+      ich = *d_chunks;
+      if (!ich.type || !ich.pay_off || !ich.pay_len || !ich.crc || !ich.ulen) return SM_ERR_ARGUMENT;
+    }
+  }
   const uint32_t nblk = (uint32_t)nblk64;
   hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(ctx->device);
@@ -194,6 +210,65 @@ sm_status smf_compress_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, uin
   SMF_CHECK(smf::launch_crc32c(d_in, in_off, in_len, nblk, crc, 1, (const smf::CrcLut*)ctx->lut.p, s));
   const smf::PackArgs a{d_in, in_off, in_len, slots, slot_off, comp_len, crc, type, dst_off, nblk, d_out};
   SMF_CHECK(smf::launch_frame_pack(a, d_out_len, d_status, s));
+  if (d_chunk_off) SMF_CHECK(smf::launch_frame_index_out(a, n, ich, d_chunk_off, d_nchunks, d_status, s));
+  return SM_OK;
+}
+
+sm_status smf_compress_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, uint8_t* d_out, uint64_t out_capacity,
+                              uint64_t* d_out_len, int32_t* d_status, int mode, void* stream) {
+  return compress_device(ctx, d_in, n, d_out, out_capacity, d_out_len, d_status, mode, nullptr, nullptr, 0, nullptr,
+                         stream);
+}
+
+sm_status smf_compress_indexed_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, uint8_t* d_out,
+                                      uint64_t out_capacity, uint64_t* d_out_len, int32_t* d_status, int mode,
+                                      const smf_chunks* d_chunks, uint64_t* d_chunk_off, uint32_t max_chunks,
+                                      uint32_t* d_nchunks, void* stream) {
+  if (!d_chunk_off) return SM_ERR_ARGUMENT;
+  return compress_device(ctx, d_in, n, d_out, out_capacity, d_out_len, d_status, mode, d_chunks, d_chunk_off, max_chunks,
+                         d_nchunks, stream);
+}
+
+sm_status smf_chunk_offsets_device(smf_ctx* ctx, const uint32_t* d_ulen, uint32_t nchunks, uint64_t* d_chunk_off,
+                                   void* stream) {
+  if (!ctx || !d_chunk_off || (nchunks && !d_ulen)) return SM_ERR_ARGUMENT;
+  DeviceGuard g(ctx->device);
+  SMF_CHECK(smf::launch_chunk_offsets(d_ulen, nchunks, d_chunk_off, (hipStream_t)stream));
+  return SM_OK;
+}
+
+sm_status smf_uncompress_ranges_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, const smf_chunks* d_chunks,
+                                       const uint64_t* d_chunk_off, uint32_t nchunks, const uint64_t* d_lo,
+                                       const uint64_t* d_len, uint32_t nranges, uint32_t max_range_chunks,
+                                       uint8_t* d_out, const uint64_t* d_out_off, uint64_t* d_out_len,
+                                       int32_t* d_range_status, void* stream) {
+  if (!ctx || nchunks > smf::kMaxIndexChunks || nranges > smf::kMaxIndexChunks) return SM_ERR_ARGUMENT;
+  if (nranges == 0) return SM_OK;
+  if (!d_chunk_off || !d_lo || !d_len || !d_out_off || !d_out_len || !d_range_status) return SM_ERR_ARGUMENT;
+  smf_chunks ch{nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (nchunks) {
+    if (!d_in || !d_out || !d_chunks) return SM_ERR_ARGUMENT;
+    ch = *d_chunks;
+    if (!ch.type || !ch.pay_off || !ch.pay_len || !ch.crc || !ch.ulen) return SM_ERR_ARGUMENT;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  DeviceGuard g(ctx->device);
+  const uint32_t m = max_range_chunks;
+  SMF_CHECK(ctx->rmeta.ensure(smf::range_meta_bytes(nranges, m)));
+  SMF_CHECK(ctx->redge.ensure(smf::range_edge_bytes(nranges)));
+  smf::RangeArgs a{d_in,    n,     ch,        d_chunk_off, nchunks,        d_lo,
+                   d_len,   nranges, m,       d_out,       d_out_off,      d_out_len,
+                   d_range_status, (uint8_t*)ctx->redge.p, smf::carve_range((uint8_t*)ctx->rmeta.p, nranges, m)};
+  SMF_CHECK(smf::launch_range_plan(a, s));
+  if (m) {
+    // every slot's output offset is relative to the edge slots (smf_range.hip, k_range_slots)
+    SMF_PASS(sm_uncompress_batch_device(ctx->sm, d_in ? d_in : a.edge, a.s.in_off, a.s.dec_len, m, a.edge, a.s.out_off,
+                                        a.s.cap, a.s.dec_out_len, a.s.dec_status, stream));
+    SMF_CHECK(smf::launch_range_copy(a, s));
+    SMF_CHECK(smf::launch_crc32c(a.edge, a.s.out_off, a.s.cap, m, a.s.crc_out, 1, (const smf::CrcLut*)ctx->lut.p, s));
+    SMF_CHECK(smf::launch_range_trim(a, s));
+  }
+  SMF_CHECK(smf::launch_range_verdicts(a, s));
   return SM_OK;
 }
 
@@ -361,6 +436,71 @@ sm_status smf_uncompress(smf_ctx* ctx, const uint8_t* framed, size_t n, uint8_t*
 sm_status smf_validate(smf_ctx* ctx, const uint8_t* framed, size_t n) {
   if (!ctx || (n && !framed)) return SM_ERR_ARGUMENT;
   return uncompress_host(ctx, framed, n, nullptr, nullptr);
+}
+
+sm_status smf_uncompress_range(smf_ctx* ctx, const uint8_t* framed, size_t n, uint64_t lo, uint64_t len,
+                               uint8_t* output, size_t* out_len) {
+  if (!ctx || !out_len || (n && !framed) || (*out_len && !output)) return SM_ERR_ARGUMENT;
+  smf_summary sum;
+  SMF_PASS(smf_index(framed, n, nullptr, 0, &sum));
+  if (lo + len < lo || lo + len > sum.total_length) return SM_ERR_ARGUMENT;
+  if (len > *out_len) {
+    *out_len = (size_t)len;
+    return SM_BUFFER_TOO_SMALL;
+  }
+  *out_len = 0;
+  if (len == 0) return SM_OK;
+  const uint32_t nc = sum.nchunks;
+  std::vector<uint8_t> type(nc);
+  std::vector<uint64_t> pay_off(nc), chunk_off((size_t)nc + 1);
+  std::vector<uint32_t> pay_len(nc), crc(nc), ulen(nc);
+  const smf_chunks h{type.data(), pay_off.data(), pay_len.data(), crc.data(), ulen.data()};
+  SMF_PASS(smf_index(framed, n, &h, nc, &sum));
+  SMF_PASS(smf_chunk_offsets(ulen.data(), nc, chunk_off.data()));
+  // the touched chunks [f, f + k), their bytes in the stream, and the index slice rebased to them
+  const smf::RangeChunks rc = smf::range_chunks(chunk_off.data(), nc, lo, len);
+  if (rc.status != SM_OK || rc.count == 0) return SM_ERR_ARGUMENT;
+  const uint32_t f = rc.first, k = rc.count;
+  const uint64_t span0 = pay_off[f], span = pay_off[f + k - 1] + pay_len[f + k - 1] - span0, base = chunk_off[f];
+  for (uint32_t c = f; c < f + k; ++c) pay_off[c] -= span0;
+  for (uint32_t c = f; c <= f + k; ++c) chunk_off[c] -= base;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  smf_chunks d;
+  int32_t* chunk_status = nullptr;
+  SMF_PASS(index_scratch(ctx, k, d, chunk_status));
+  SMF_CHECK(ctx->roff.ensure(8 * ((size_t)k + 1)));
+  SMF_CHECK(ctx->io_in.ensure((size_t)span));
+  SMF_CHECK(ctx->io_out.ensure((size_t)len));
+  SMF_CHECK(hipMemcpyAsync(ctx->io_in.p, framed + span0, (size_t)span, hipMemcpyHostToDevice, s));
+  SMF_CHECK(hipMemcpyAsync(d.type, h.type + f, k, hipMemcpyHostToDevice, s));
+  SMF_CHECK(hipMemcpyAsync(d.pay_off, h.pay_off + f, 8 * (size_t)k, hipMemcpyHostToDevice, s));
+  SMF_CHECK(hipMemcpyAsync(d.pay_len, h.pay_len + f, 4 * (size_t)k, hipMemcpyHostToDevice, s));
+  SMF_CHECK(hipMemcpyAsync(d.crc, h.crc + f, 4 * (size_t)k, hipMemcpyHostToDevice, s));
+  SMF_CHECK(hipMemcpyAsync(d.ulen, h.ulen + f, 4 * (size_t)k, hipMemcpyHostToDevice, s));
+  SMF_CHECK(hipMemcpyAsync(ctx->roff.p, chunk_off.data() + f, 8 * ((size_t)k + 1), hipMemcpyHostToDevice, s));
+  // the range's words in ctx->res: lo, len, out_off | out_len, status
+  struct {
+    uint64_t lo, len, out_off;
+  } arg{lo - base, len, 0};
+  struct {
+    uint64_t len;
+    int32_t st, pad;
+  } r;
+  uint64_t* d_arg = (uint64_t*)((uint8_t*)ctx->res.p + 128);
+  uint64_t* d_len = (uint64_t*)((uint8_t*)ctx->res.p + 160);
+  int32_t* d_st = (int32_t*)((uint8_t*)ctx->res.p + 168);
+  SMF_CHECK(hipMemcpyAsync(d_arg, &arg, sizeof(arg), hipMemcpyHostToDevice, s));
+  SMF_PASS(smf_uncompress_ranges_device(ctx, (const uint8_t*)ctx->io_in.p, span, &d, (const uint64_t*)ctx->roff.p, k,
+                                        d_arg, d_arg + 1, 1, k, (uint8_t*)ctx->io_out.p, d_arg + 2, d_len, d_st, s));
+  SMF_CHECK(hipMemcpyAsync(&r, d_len, 16, hipMemcpyDeviceToHost, s));
+  SMF_CHECK(hipStreamSynchronize(s));  // (also: the pageable uploads above have left their host buffers)
+  if (r.st != SM_OK) return r.st;
+  if (r.len != len) return SM_ERR_DEVICE;
+  SMF_CHECK(hipMemcpy(output, ctx->io_out.p, (size_t)len, hipMemcpyDeviceToHost));
+  *out_len = (size_t)len;
+  return SM_OK;
 }
 
 }  // extern "C"

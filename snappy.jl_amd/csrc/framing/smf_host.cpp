@@ -2,6 +2,7 @@
 // the chunk walker over a host buffer, the bytewise CRC-32C and the size helpers.  No HIP and no
 // call into the raw codec, so this file also builds alone (the sanitizer driver, smf_host_check.cpp).
 #include "smf_format.h"
+#include "smf_range.h"
 
 namespace {
 
@@ -114,6 +115,53 @@ sm_status smf_uncompressed_length(const uint8_t* buf, size_t n, size_t* result) 
   const sm_status st = smf_index(buf, n, nullptr, 0, &s);
   if (st == SM_OK && result) *result = (size_t)s.total_length;
   return st;
+}
+
+sm_status smf_chunk_offsets(const uint32_t* ulen, uint32_t nchunks, uint64_t* chunk_off) {
+  if (!chunk_off || (nchunks && !ulen)) return SM_ERR_ARGUMENT;
+  uint64_t at = 0;
+  for (uint32_t c = 0; c < nchunks; ++c) {
+    chunk_off[c] = at;
+    at += ulen[c];
+  }
+  chunk_off[nchunks] = at;
+  return SM_OK;
+}
+
+uint64_t smf_range_chunk_count(uint64_t lo, uint64_t len) {
+  if (len == 0 || lo + len < lo) return 0;
+  return (lo + len - 1) / smf::kBlock - lo / smf::kBlock + 1;
+}
+
+// the device's plan, range by range and slot by slot (smf_range.h)
+sm_status smf_range_plan(const smf_chunks* chunks, const uint64_t* chunk_off, uint32_t nchunks, uint64_t n,
+                         const uint64_t* lo, const uint64_t* len, uint32_t nranges, uint32_t max_range_chunks,
+                         uint32_t* first, uint32_t* count, int32_t* status, uint64_t* total) {
+  if (!chunk_off || nchunks > smf::kMaxIndexChunks || nranges > smf::kMaxIndexChunks) return SM_ERR_ARGUMENT;
+  if (nranges && (!lo || !len)) return SM_ERR_ARGUMENT;
+  if (nchunks && (!chunks || !chunks->type || !chunks->pay_off || !chunks->pay_len || !chunks->crc || !chunks->ulen))
+    return SM_ERR_ARGUMENT;
+  uint64_t sum = 0;
+  for (uint32_t r = 0; r < nranges; ++r) {
+    const smf::RangeChunks rc = smf::range_chunks(chunk_off, nchunks, lo[r], len[r]);
+    int32_t st = rc.status;
+    for (uint32_t k = 0; k < rc.count && st == SM_OK; ++k) {
+      bool skip;
+      st = smf::slot_place(*chunks, chunk_off, n, rc.first + k, lo[r], len[r], k == 0, k == rc.count - 1, skip).status;
+    }
+    if (first) first[r] = rc.first;
+    if (count) count[r] = rc.count;
+    if (status) status[r] = st;
+    sum += rc.count;
+  }
+  if (total) *total = sum;
+  if (sum <= max_range_chunks) return SM_OK;
+  for (uint32_t r = 0; r < nranges && status; ++r) status[r] = SM_ERR_ARGUMENT;
+  return SM_BUFFER_TOO_SMALL;
+}
+
+size_t smf_range_scratch_bytes(uint32_t nranges, uint32_t max_range_chunks) {
+  return smf::range_meta_bytes(nranges, max_range_chunks) + smf::range_edge_bytes(nranges);
 }
 
 }  // extern "C"

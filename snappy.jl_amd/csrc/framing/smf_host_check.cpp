@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "smf_format.h"
+#include "smf_range.h"
 
 namespace {
 
@@ -105,6 +106,221 @@ uint32_t crc_like_kernel(const smf::CrcLut& T, const uint8_t* p, uint32_t n) {
   }
   for (uint32_t i = head + 16 * G; i < n; ++i) acc = tab[15 * 256 + ((acc ^ p[i]) & 0xff)] ^ (acc >> 8);
   return acc ^ 0xffffffffu;
+}
+
+// ---- the seek index and the range plan (smf_range.h through smf_range_plan) --------------------
+// An index in heap blocks of exactly its size, so a search or a check that leaves an array trips
+// the sanitizer.  The stream behind it is never read by the plan: only its length counts.
+struct Index {
+  uint32_t nc;
+  uint64_t n;  // the framed stream's length
+  uint8_t* type;
+  uint64_t *pay_off, *chunk_off;
+  uint32_t *pay_len, *crc, *ulen;
+  // 0x01 chunks of the given lengths behind the identifier
+  Index(const std::vector<uint32_t>& lens) : nc((uint32_t)lens.size()) {
+    type = (uint8_t*)std::malloc(nc ? nc : 1);
+    pay_off = (uint64_t*)std::malloc(8 * (size_t)(nc ? nc : 1));
+    chunk_off = (uint64_t*)std::malloc(8 * ((size_t)nc + 1));
+    pay_len = (uint32_t*)std::malloc(4 * (size_t)(nc ? nc : 1));
+    crc = (uint32_t*)std::malloc(4 * (size_t)(nc ? nc : 1));
+    ulen = (uint32_t*)std::malloc(4 * (size_t)(nc ? nc : 1));
+    uint64_t pos = 10;
+    for (uint32_t c = 0; c < nc; ++c) {
+      type[c] = 1;
+      pay_off[c] = pos + 8;
+      pay_len[c] = ulen[c] = lens[c];
+      crc[c] = 0;
+      pos += 8 + lens[c];
+    }
+    n = pos;
+    expect(smf_chunk_offsets(ulen, nc, chunk_off) == SM_OK, "chunk offsets");
+  }
+  ~Index() {
+    std::free(type);
+    std::free(pay_off);
+    std::free(chunk_off);
+    std::free(pay_len);
+    std::free(crc);
+    std::free(ulen);
+  }
+  smf_chunks chunks() const { return smf_chunks{type, pay_off, pay_len, crc, ulen}; }
+  uint64_t total() const { return chunk_off[nc]; }
+};
+
+struct Planned {
+  sm_status rc;
+  uint32_t first, count;
+  int32_t status;
+  uint64_t total;
+};
+
+Planned plan_one(const Index& ix, uint64_t lo, uint64_t len, uint32_t max_range_chunks = 0xffffffffu) {
+  Planned p{};
+  uint64_t* a = (uint64_t*)std::malloc(16);
+  a[0] = lo;
+  a[1] = len;
+  const smf_chunks ch = ix.chunks();
+  p.rc = smf_range_plan(&ch, ix.chunk_off, ix.nc, ix.n, a, a + 1, 1, max_range_chunks, &p.first, &p.count, &p.status,
+                        &p.total);
+  std::free(a);
+  return p;
+}
+
+// every (lo, len) of the index: the plan stays inside the arrays (the sanitizer's business) and
+// inside [0, nc); touch(c) tells which ranges are expected to fail
+template <typename F>
+void sweep(const Index& ix, uint64_t total, const char* what, F bad_touched) {
+  for (uint64_t lo = 0; lo <= total + 1; ++lo)
+    for (uint64_t len = 0; len <= total + 1 - lo + 1; ++len) {
+      const Planned p = plan_one(ix, lo, len);
+      const bool in_bounds = p.count == 0 || (p.first < ix.nc && p.count <= ix.nc - p.first);
+      if (!in_bounds || p.rc != SM_OK) {
+        std::printf("FAIL %s: (%llu, %llu) leaves the index\n", what, (unsigned long long)lo, (unsigned long long)len);
+        ++failures;
+      }
+      const int want = bad_touched(lo, len, p);
+      if (want >= 0 && p.status != want) {
+        std::printf("FAIL %s: (%llu, %llu) status %d, want %d\n", what, (unsigned long long)lo, (unsigned long long)len,
+                    p.status, want);
+        ++failures;
+      }
+    }
+}
+
+void range_cases() {
+  // smf_chunk_offsets: 0, 1 and 257 chunks, lengths including 0 and 65536
+  for (uint32_t nc : {0u, 1u, 257u}) {
+    std::vector<uint32_t> lens(nc);
+    for (uint32_t c = 0; c < nc; ++c) lens[c] = c % 5 == 0 ? 0u : (c % 7 == 0 ? 65536u : c * 37u % 65537u);
+    const Index ix(lens);
+    uint64_t at = 0;
+    bool ok = true;
+    for (uint32_t c = 0; c < nc; ++c) {
+      ok = ok && ix.chunk_off[c] == at;
+      at += lens[c];
+    }
+    expect(ok && ix.chunk_off[nc] == at, "chunk offsets: the scan");
+  }
+  expect(smf_chunk_offsets(nullptr, 1, nullptr) == SM_ERR_ARGUMENT, "chunk offsets: null");
+  expect(smf_range_chunk_count(0, 0) == 0 && smf_range_chunk_count(0, 1) == 1 && smf_range_chunk_count(65535, 1) == 1 &&
+             smf_range_chunk_count(65535, 2) == 2 && smf_range_chunk_count(65536, 65536) == 1 &&
+             smf_range_chunk_count(1, 131072) == 3 && smf_range_chunk_count(UINT64_MAX, 2) == 0,
+         "range chunk count");
+  expect(smf_range_scratch_bytes(1, 0) >= 2 * 65536 && smf_range_scratch_bytes(3, 7) > smf_range_scratch_bytes(3, 6),
+         "range scratch bytes");
+
+  const std::vector<uint32_t> lens = {0, 1, 3, 0, 16, 17, 0};
+  const uint64_t total = 37;
+  // a good index: which chunks, and the edges of the contract
+  {
+    const Index ix(lens);
+    sweep(ix, total, "good index", [&](uint64_t lo, uint64_t len, const Planned& p) {
+      if (len == 0) return p.count == 0 ? (int)SM_OK : 99;
+      if (lo + len > total) return p.count == 0 ? (int)SM_ERR_ARGUMENT : 99;
+      // the chunk holding lo and the chunk holding lo + len - 1, empty ones skipped
+      uint32_t f = 0, l = 0;
+      for (uint32_t c = 0; c < ix.nc; ++c) {
+        if (ix.ulen[c] && ix.chunk_off[c] <= lo && lo < ix.chunk_off[c + 1]) f = c;
+        if (ix.ulen[c] && ix.chunk_off[c] <= lo + len - 1 && lo + len - 1 < ix.chunk_off[c + 1]) l = c;
+      }
+      return p.first == f && p.count == l - f + 1 ? (int)SM_OK : 99;
+    });
+    expect(plan_one(ix, total, 0).status == SM_OK, "lo == total, len == 0");
+    expect(plan_one(ix, total, 1).status == SM_ERR_ARGUMENT, "lo == total, len == 1");
+    expect(plan_one(ix, 5, UINT64_MAX - 2).status == SM_ERR_ARGUMENT, "lo + len overflows");
+    expect(plan_one(ix, UINT64_MAX, 1).status == SM_ERR_ARGUMENT, "lo + len overflows to 0");
+    const Planned all = plan_one(ix, 0, total);
+    expect(all.rc == SM_OK && all.first == 1 && all.count == 5 && all.total == 5, "the whole stream");
+    const Planned over = plan_one(ix, 0, total, 4);
+    expect(over.rc == SM_BUFFER_TOO_SMALL && over.total == 5 && over.status == SM_ERR_ARGUMENT, "one slot short");
+  }
+  // hostile entries: exactly the ranges that touch chunk `victim` (ulen 16, content [4, 20)) fail
+  const uint32_t victim = 4;
+  auto touches = [&](uint64_t lo, uint64_t len) { return len && lo + len <= total && lo < 20 && lo + len > 4; };
+  auto by_victim = [&](uint64_t lo, uint64_t len, const Planned&) {
+    if (len == 0) return (int)SM_OK;
+    if (lo + len > total) return (int)SM_ERR_ARGUMENT;
+    return touches(lo, len) ? (int)SM_ERR_ARGUMENT : (int)SM_OK;
+  };
+  {
+    Index ix(lens);
+    ix.type[victim] = 7;
+    sweep(ix, total, "type 7", by_victim);
+  }
+  {
+    Index ix(lens);
+    ix.pay_off[victim] = UINT64_MAX - 3;
+    sweep(ix, total, "pay_off near the top", by_victim);
+    ix.pay_off[victim] = ix.n - 15;  // one byte past the stream's end
+    sweep(ix, total, "payload one byte past the end", by_victim);
+  }
+  {
+    Index ix(lens);
+    ix.pay_len[victim] = 15;  // a 0x01 chunk whose lengths differ
+    sweep(ix, total, "0x01 lengths differ", by_victim);
+  }
+  // an ulen that chunk_off does not agree with; 65537 fails the size rule first
+  {
+    Index ix(lens);
+    ix.ulen[victim] = ix.pay_len[victim] = 65537;
+    sweep(ix, total, "ulen 65537", by_victim);
+  }
+  // hostile chunk_off: whatever it holds, the plan stays inside the arrays and never accepts a
+  // chunk whose bytes are not [chunk_off[c], chunk_off[c + 1]) of its length
+  auto any = [](uint64_t, uint64_t, const Planned&) { return -1; };
+  {
+    Index ix(lens);
+    for (uint32_t c = 0; c <= ix.nc; ++c) ix.chunk_off[c] = 9;  // constant
+    sweep(ix, total, "chunk_off constant", [&](uint64_t lo, uint64_t len, const Planned& p) {
+      return len == 0 ? (int)SM_OK : (int)SM_ERR_ARGUMENT;  // past the "total" of 9, or chunks of no bytes
+    });
+  }
+  {
+    Index ix(lens);
+    for (uint32_t c = 0; c <= ix.nc; ++c) ix.chunk_off[c] = 40 - 5 * c;  // decreasing
+    sweep(ix, total, "chunk_off decreasing", [&](uint64_t lo, uint64_t len, const Planned& p) {
+      return len == 0 ? (int)SM_OK : (int)SM_ERR_ARGUMENT;
+    });
+  }
+  {
+    Index ix(lens);
+    for (uint32_t c = 0; c <= ix.nc; ++c) ix.chunk_off[c] = UINT64_MAX;
+    sweep(ix, total, "chunk_off UINT64_MAX", [&](uint64_t lo, uint64_t len, const Planned& p) {
+      return len == 0 ? (int)SM_OK : (int)SM_ERR_ARGUMENT;
+    });
+    expect(plan_one(ix, UINT64_MAX - 1, 1).status == SM_ERR_ARGUMENT, "chunk_off UINT64_MAX: the last byte");
+    ix.chunk_off[0] = 0;  // one chunk claims everything
+    sweep(ix, total, "chunk_off 0 then UINT64_MAX", any);
+    expect(plan_one(ix, 7, UINT64_MAX - 7).status == SM_ERR_ARGUMENT, "a chunk of 2^64 bytes");
+    ix.chunk_off[3] = 2;  // not monotone in the middle
+    sweep(ix, total, "chunk_off not monotone", any);
+  }
+  // a stream of only empty data chunks, and one without chunks
+  {
+    const Index ix(std::vector<uint32_t>{0, 0, 0});
+    expect(plan_one(ix, 0, 0).status == SM_OK && plan_one(ix, 0, 0).count == 0, "empty chunks: (0, 0)");
+    expect(plan_one(ix, 0, 1).status == SM_ERR_ARGUMENT && plan_one(ix, 1, 0).status == SM_OK, "empty chunks: past the end");
+    const Index none(std::vector<uint32_t>{});
+    expect(plan_one(none, 0, 0).status == SM_OK && plan_one(none, 0, 1).status == SM_ERR_ARGUMENT, "no chunks");
+    none.chunk_off[0] = 100;  // a total without chunks
+    expect(plan_one(none, 0, 50).status == SM_ERR_ARGUMENT && plan_one(none, 0, 50).count == 0, "no chunks, hostile total");
+  }
+  // place rule: the chunk_place arithmetic for every chunk position against a byte-by-byte model
+  for (uint64_t a = 0; a < 12; ++a)
+    for (uint32_t u = 1; u < 8; ++u)
+      for (uint64_t lo = 0; lo < 14; ++lo)
+        for (uint64_t len = 1; len < 14; ++len)
+          for (int pos = 0; pos < 4; ++pos) {
+            const smf::Place p = smf::chunk_place(a, u, lo, len, pos & 1, pos & 2);
+            bool ok;
+            const bool meets = (a > lo ? a : lo) < (a + u < lo + len ? a + u : lo + len);
+            if (p.status != SM_OK) ok = !(a >= lo && a + u <= lo + len) && (pos == 0 || !meets);
+            else if (p.edge == 0) ok = a >= lo && a + u <= lo + len && p.dst == a - lo;
+            else ok = p.n > 0 && p.src + p.n <= u && p.dst + p.n <= len && a + p.src == lo + p.dst && pos != 0 &&
+                      p.edge == ((pos & 1) ? 1u : 2u);
+            expect(ok, "chunk_place");
+          }
 }
 
 }  // namespace
@@ -210,6 +426,7 @@ int main() {
     expect(smf_index((const uint8_t*)s.data(), s.size(), nullptr, 0, nullptr) == SM_ERR_ARGUMENT, "null summary");
   }
   expect(smf::host_message(SMF_ERR_CRC) != nullptr && smf::host_message(SM_OK) == nullptr, "messages");
+  range_cases();
 
   if (failures) {
     std::printf("%d failure(s)\n", failures);

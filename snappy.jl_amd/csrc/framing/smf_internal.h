@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "smf_format.h"
+#include "smf_range.h"
 
 namespace smf {
 
@@ -44,5 +45,36 @@ hipError_t launch_frame_copy(const uint8_t* in, const smf_chunks& ch, uint32_t n
                              const uint32_t* cap, uint8_t* out, hipStream_t s);
 hipError_t launch_frame_verify(const smf_chunks& ch, uint32_t nchunks, const int32_t* pre, const int32_t* dec_status,
                                const uint32_t* crc_out, int32_t* chunk_status, int32_t* status, hipStream_t s);
+
+// ---- smf_range.hip: the seek index and the ranged decode ------------------------------------
+// chunk_off[0, nchunks] = the exclusive scan of ulen
+hipError_t launch_chunk_offsets(const uint32_t* ulen, uint32_t nchunks, uint64_t* chunk_off, hipStream_t s);
+// behind launch_frame_pack: the encoder's index of the stream it packed
+hipError_t launch_frame_index_out(const PackArgs& a, uint64_t n, const smf_chunks& ch, uint64_t* chunk_off,
+                                  uint32_t* nchunks, const int32_t* status, hipStream_t s);
+
+struct RangeArgs {
+  const uint8_t* in;
+  uint64_t n;
+  smf_chunks ch;
+  const uint64_t* chunk_off;
+  uint32_t nchunks;
+  const uint64_t* lo;
+  const uint64_t* len;
+  uint32_t nranges, m;  // m = max_range_chunks: the slots
+  uint8_t* out;
+  const uint64_t* out_off;
+  uint64_t* out_len;
+  int32_t* range_status;
+  uint8_t* edge;  // 2 nranges edge slots of kEdgePitch bytes: the raw decoder's and the CRC pass's base
+  RangeScratch s;
+};
+// per range its chunks, the scan of the counts against m, per slot the raw decoder's arguments
+hipError_t launch_range_plan(const RangeArgs& a, hipStream_t s);
+// behind the raw decoder: the 0x01 chunks' copies; behind the CRC pass: the edge slots' covered bytes
+hipError_t launch_range_copy(const RangeArgs& a, hipStream_t s);
+hipError_t launch_range_trim(const RangeArgs& a, hipStream_t s);
+// per slot and, segmented by range, per range
+hipError_t launch_range_verdicts(const RangeArgs& a, hipStream_t s);
 
 }  // namespace smf

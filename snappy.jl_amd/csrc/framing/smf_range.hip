@@ -1,0 +1,273 @@
+// smf_range.hip -- the seek index and the ranged decode of the framing library: gfx950 kernels and
+// their launchers (smf_range.h).  Plumbing around the raw codec's batched decoder and k_crc32c, as
+// smf_kernels.hip's decode is; the decisions are the shared rules of smf_range.h, taken per range
+// and per slot on the device, so a call needs no host synchronisation.  block_scan and copy_bytes
+// are this file's own copies of smf_kernels.hip's: the existing entry points' objects stay as
+// they were.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "smf_format.h"
+#include "smf_internal.h"
+#include "smf_range.h"
+
+namespace smf {
+
+namespace {
+
+constexpr uint32_t kWave = 64;
+
+// n bytes from src to dst, both at any alignment, by `nthreads` threads of which this is `tid`:
+// aligned 16-byte loads of the granules src wholly covers, bytes for the partial granules at both
+// ends (no byte outside [src, src + n) is read), stores at dst's alignment (none outside
+// [dst, dst + n)).
+__device__ inline void copy_bytes(const uint8_t* __restrict__ src, uint32_t n, uint8_t* __restrict__ dst, uint32_t tid,
+                                  uint32_t nthreads) {
+  const uint32_t head = min(n, (16u - (uint32_t)((uintptr_t)src & 15)) & 15u);
+  const uint32_t G = (n - head) / 16;
+  const uint4* g = reinterpret_cast<const uint4*>(src + head);
+  for (uint32_t u = tid; u < G; u += nthreads) {
+    const uint4 v = g[u];
+    __builtin_memcpy(dst + head + 16 * u, &v, 16);
+  }
+  const uint32_t edge = n - 16 * G;  // head bytes, then the tail's
+  for (uint32_t i = tid; i < edge; i += nthreads) {
+    const uint32_t j = i < head ? i : 16 * G + i;
+    dst[j] = src[j];
+  }
+}
+
+// exclusive scan of v over the workgroup's 256 threads (sh: 4 u64); total = the sum
+__device__ inline uint64_t block_scan(uint64_t v, uint64_t* sh, uint64_t& total) {
+  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  uint64_t inc = v;
+  for (uint32_t d = 1; d < kWave; d <<= 1) {
+    const uint64_t o = __shfl_up(inc, d, kWave);
+    if (lane >= d) inc += o;
+  }
+  __syncthreads();  // (sh is free again)
+  if (lane == kWave - 1) sh[w] = inc;
+  __syncthreads();
+  uint64_t pre = 0;
+  for (uint32_t k = 0; k < w; ++k) pre += sh[k];
+  total = sh[0] + sh[1] + sh[2] + sh[3];
+  return pre + inc - v;
+}
+
+// base + off where off may stand for a place before base (the offsets of k_range_slots)
+__device__ inline uint8_t* at(uint8_t* base, uint64_t off) { return (uint8_t*)((uintptr_t)base + off); }
+
+__device__ inline uint32_t sat32(uint64_t v) { return v > 0xffffffffull ? 0xffffffffu : (uint32_t)v; }
+
+}  // namespace
+
+// ---- the seek index ------------------------------------------------------------------------------
+// chunk_off = the exclusive scan of ulen, chunk_off[nchunks] = the total, by one workgroup
+__global__ __launch_bounds__(256) void k_chunk_offsets(const uint32_t* __restrict__ ulen, uint32_t nchunks,
+                                                       uint64_t* __restrict__ chunk_off) {
+  __shared__ uint64_t sh[4];
+  uint64_t carry = 0;
+  for (uint32_t base = 0; base < nchunks; base += 256) {  // (uniform: every thread takes every tile)
+    const uint32_t c = base + threadIdx.x;
+    const uint32_t u = c < nchunks ? ulen[c] : 0u;
+    uint64_t total;
+    const uint64_t ex = block_scan(u, sh, total);
+    if (c < nchunks) chunk_off[c] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) chunk_off[nchunks] = carry;
+}
+
+hipError_t launch_chunk_offsets(const uint32_t* ulen, uint32_t nchunks, uint64_t* chunk_off, hipStream_t s) {
+  hipLaunchKernelGGL(k_chunk_offsets, dim3(1), dim3(256), 0, s, ulen, nchunks, chunk_off);
+  return hipGetLastError();
+}
+
+// The encoder's index, behind k_frame_scan: block b is data chunk b.  *status is k_frame_scan's.
+__global__ __launch_bounds__(256) void k_frame_index_out(const uint8_t* type, const uint64_t* dst_off,
+                                                         const uint32_t* comp_len, const uint32_t* in_len,
+                                                         const uint32_t* crc, uint32_t nblk, uint64_t n, smf_chunks ch,
+                                                         uint64_t* chunk_off, uint32_t* nchunks, const int32_t* status) {
+  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < nblk) {
+    const uint8_t ty = type[b];
+    ch.type[b] = ty;
+    ch.pay_off[b] = dst_off[b] + 8;
+    ch.pay_len[b] = ty == SMF_CHUNK_COMPRESSED ? comp_len[b] : in_len[b];
+    ch.crc[b] = crc[b];
+    ch.ulen[b] = in_len[b];
+    chunk_off[b] = (uint64_t)b * kBlock;
+  } else if (b == nblk) {
+    chunk_off[nblk] = n;
+    *nchunks = *status == SM_OK ? nblk : 0u;
+  }
+}
+
+hipError_t launch_frame_index_out(const PackArgs& a, uint64_t n, const smf_chunks& ch, uint64_t* chunk_off,
+                                  uint32_t* nchunks, const int32_t* status, hipStream_t s) {
+  hipLaunchKernelGGL(k_frame_index_out, dim3(a.nblk / 256 + 1), dim3(256), 0, s, a.type, a.dst_off, a.comp_len, a.in_len,
+                     a.crc, a.nblk, n, ch, chunk_off, nchunks, status);
+  return hipGetLastError();
+}
+
+// ---- the range plan ------------------------------------------------------------------------------
+// Per range: its chunks (two bounded searches) and whether it leaves the stream.
+__global__ __launch_bounds__(256) void k_range_find(RangeArgs a) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.nranges) return;
+  const RangeChunks rc = range_chunks(a.chunk_off, a.nchunks, a.lo[r], a.len[r]);
+  a.s.first[r] = rc.first;
+  a.s.count[r] = rc.count;
+  a.s.rpre[r] = rc.status;
+  a.s.fail[r] = kNoSlot;
+}
+
+// base = the exclusive scan of the counts over the ranges, and the compare with max_range_chunks,
+// by one workgroup.  Over the bound the bases are not used (they saturate).
+__global__ __launch_bounds__(256) void k_range_scan(RangeArgs a) {
+  __shared__ uint64_t sh[4];
+  uint64_t carry = 0;
+  for (uint32_t b0 = 0; b0 < a.nranges; b0 += 256) {
+    const uint32_t r = b0 + threadIdx.x;
+    const uint32_t cnt = r < a.nranges ? a.s.count[r] : 0u;
+    uint64_t total;
+    const uint64_t ex = block_scan(cnt, sh, total);
+    if (r < a.nranges) a.s.base[r] = sat32(carry + ex);
+    carry += total;
+  }
+  if (threadIdx.x == 0) {
+    const bool over = carry > a.m;
+    a.s.base[a.nranges] = sat32(carry);
+    a.s.hdr->over = over ? 1u : 0u;
+    a.s.hdr->total = over ? 0u : (uint32_t)carry;
+  }
+}
+
+// Slot j: its range (a search in the scanned counts), its chunk, the entry checks, and what the raw
+// decoder, the copy, the CRC pass and the trim get for it.  A slot that is not decoded -- unused,
+// an empty chunk, a failed check, or every slot over the bound -- is an empty stream with no room:
+// the raw decoder returns at once, and nothing else touches it.  Offsets of outputs are relative
+// to the edge slots' base, which is what the raw decoder and the CRC pass get as their buffer.
+__global__ __launch_bounds__(256) void k_range_slots(RangeArgs a) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= a.m) return;
+  uint64_t in_off = 0, out_off = 0, trim_dst = 0;
+  uint32_t dec_len = 0, cap = 0, trim_src = 0, trim_len = 0, range = kNoSlot, want = 0;
+  int32_t pre = SM_OK;
+  uint8_t copy = 0;
+  if (j < a.s.hdr->total) {
+    const uint32_t r = upper_bound(a.s.base, a.nranges + 1, j) - 1;  // base[r] <= j < base[r + 1]
+    const uint32_t k = r < a.nranges ? j - a.s.base[r] : kNoSlot, cnt = r < a.nranges ? a.s.count[r] : 0u;
+    if (k < cnt) {  // (always, for the bases the scan wrote)
+      const uint32_t c = a.s.first[r] + k;
+      bool skip;
+      const Place p = slot_place(a.ch, a.chunk_off, a.n, c, a.lo[r], a.len[r], k == 0, k == cnt - 1, skip);
+      if (!skip) {
+        range = r;
+        pre = p.status;
+        if (pre == SM_OK) {
+          const uint8_t ty = a.ch.type[c];
+          const uint8_t* const target = p.edge ? a.edge + (2 * (uint64_t)r + (p.edge - 1)) * kEdgePitch
+                                               : a.out + a.out_off[r] + p.dst;
+          out_off = (uint64_t)(uintptr_t)target - (uint64_t)(uintptr_t)a.edge;
+          in_off = a.ch.pay_off[c];
+          cap = a.ch.ulen[c];
+          want = a.ch.crc[c];
+          if (ty == SMF_CHUNK_COMPRESSED) dec_len = a.ch.pay_len[c];
+          else copy = 1;
+          if (p.edge) {
+            trim_src = p.src;
+            trim_len = p.n;
+            trim_dst = a.out_off[r] + p.dst;
+          }
+        }
+      }
+    }
+  }
+  a.s.in_off[j] = in_off;
+  a.s.out_off[j] = out_off;
+  a.s.trim_dst[j] = trim_dst;
+  a.s.dec_len[j] = dec_len;
+  a.s.cap[j] = cap;
+  a.s.trim_src[j] = trim_src;
+  a.s.trim_len[j] = trim_len;
+  a.s.range[j] = range;
+  a.s.crc_want[j] = want;
+  a.s.pre[j] = pre;
+  a.s.copy[j] = copy;
+}
+
+hipError_t launch_range_plan(const RangeArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(k_range_find, dim3((a.nranges + 255) / 256), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_range_scan, dim3(1), dim3(256), 0, s, a);
+  if (a.m) hipLaunchKernelGGL(k_range_slots, dim3((a.m + 255) / 256), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// ---- behind the raw decoder ----------------------------------------------------------------------
+// 0x01 chunks: the payload is the output, at the direct place or in the edge slot
+__global__ __launch_bounds__(256) void k_range_copy(RangeArgs a) {
+  const uint32_t j = blockIdx.x;
+  if (!a.s.copy[j]) return;
+  copy_bytes(a.in + a.s.in_off[j], a.s.cap[j], at(a.edge, a.s.out_off[j]), blockIdx.y * blockDim.x + threadIdx.x,
+             gridDim.y * blockDim.x);
+}
+
+hipError_t launch_range_copy(const RangeArgs& a, hipStream_t s) {
+  if (a.m == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_range_copy, dim3(a.m, 4), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// An edge slot's covered bytes to the range's output.  The plan's numbers keep the reads inside
+// the slot (trim_src + trim_len <= the chunk's length <= the slot) and the writes inside the range
+// (trim_dst - out_off[r] + trim_len <= len), whatever the chunk decoded to.
+__global__ __launch_bounds__(256) void k_range_trim(RangeArgs a) {
+  const uint32_t j = blockIdx.x;
+  const uint32_t n = a.s.trim_len[j];
+  if (n == 0) return;
+  copy_bytes(at(a.edge, a.s.out_off[j] + a.s.trim_src[j]), n, a.out + a.s.trim_dst[j],
+             blockIdx.y * blockDim.x + threadIdx.x, gridDim.y * blockDim.x);
+}
+
+hipError_t launch_range_trim(const RangeArgs& a, hipStream_t s) {
+  if (a.m == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_range_trim, dim3(a.m, 4), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// Per slot: why it was not decoded, else the raw decoder's status (0x00), else the CRC's verdict;
+// a failing slot enters its range's minimum.  Then per range: the first failing slot's status.
+__global__ __launch_bounds__(256) void k_range_verify(RangeArgs a) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= a.m) return;
+  const uint32_t r = a.s.range[j];
+  int32_t st = SM_OK;
+  if (r != kNoSlot) {
+    st = a.s.pre[j];
+    if (st == SM_OK && !a.s.copy[j]) st = a.s.dec_status[j];
+    if (st == SM_OK && a.s.crc_out[j] != a.s.crc_want[j]) st = SMF_ERR_CRC;
+    if (st != SM_OK) atomicMin(&a.s.fail[r], j - a.s.base[r]);
+  }
+  a.s.slot_status[j] = st;
+}
+
+__global__ __launch_bounds__(256) void k_range_result(RangeArgs a) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.nranges) return;
+  int32_t st = a.s.hdr->over ? (int32_t)SM_ERR_ARGUMENT : a.s.rpre[r];
+  if (st == SM_OK) {
+    const uint32_t f = a.s.fail[r];
+    if (f != kNoSlot) st = a.s.slot_status[a.s.base[r] + f];
+  }
+  a.range_status[r] = st;
+  a.out_len[r] = st == SM_OK ? a.len[r] : 0;
+}
+
+hipError_t launch_range_verdicts(const RangeArgs& a, hipStream_t s) {
+  if (a.m) hipLaunchKernelGGL(k_range_verify, dim3((a.m + 255) / 256), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_range_result, dim3((a.nranges + 255) / 256), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace smf

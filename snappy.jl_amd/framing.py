@@ -7,10 +7,15 @@ of libsnappy_mi355x.so.
     length_uncompressed_framed(x) -> int    from the chunk headers alone (host, no device)
     validate_framed(x)           -> status  what uncompress_framed would raise with, or 0
     index_framed(x)              -> (summary, arrays)  the host chunk walker
+    seek_index_framed(x)         -> FramedIndex  the walker's arrays plus chunk_off
+    compress_framed(x, return_index=True) -> (bytes, FramedIndex)  the encoder's own index
+    uncompress_framed_range(x, lo, length)  -> bytes   only the touched chunks are decoded
+    uncompress_framed_ranges(x, ranges)     -> (list of bytes, statuses)  one batched call
 
 and, on torch tensors resident in HBM: crc32c_batch_device, compress_framed_device,
 index_framed_device, uncompressed_length_framed_device, uncompress_chunks_device,
-uncompress_framed_device.
+uncompress_framed_device, compress_framed_indexed_device, chunk_offsets_device,
+uncompress_ranges_device.
 
 The package imports without this library; it is loaded on the first call here.  No CPU
 fallback: every codec call needs both HIP libraries and a device.
@@ -39,7 +44,11 @@ FRAMING_ABI_SYMBOLS = (
     "smf_uncompressed_length", "smf_ctx_create", "smf_ctx_destroy", "smf_crc32c_batch_device", "smf_compress_device",
     "smf_index_device", "smf_uncompressed_length_device", "smf_uncompress_chunks_device", "smf_uncompress_device",
     "smf_compress", "smf_uncompress", "smf_validate",
+) + (  # the seek index and the ranged decode (checked by tests/test_framing_range_host.py)
+    "smf_chunk_offsets", "smf_range_chunk_count", "smf_range_plan", "smf_range_scratch_bytes",
+    "smf_chunk_offsets_device", "smf_compress_indexed_device", "smf_uncompress_ranges_device", "smf_uncompress_range",
 )
+RANGE_ABI_SYMBOLS = FRAMING_ABI_SYMBOLS[-8:]
 
 
 class Chunks(ctypes.Structure):
@@ -107,6 +116,22 @@ def lib():
         L.smf_uncompress.argtypes = [vp, vp, sz, vp, ctypes.POINTER(sz)]
         L.smf_validate.restype = i32
         L.smf_validate.argtypes = [vp, vp, sz]
+        L.smf_chunk_offsets.restype = i32
+        L.smf_chunk_offsets.argtypes = [vp, u32, vp]
+        L.smf_range_chunk_count.restype = u64
+        L.smf_range_chunk_count.argtypes = [u64, u64]
+        L.smf_range_plan.restype = i32
+        L.smf_range_plan.argtypes = [pch, vp, u32, u64, vp, vp, u32, u32, vp, vp, vp, ctypes.POINTER(u64)]
+        L.smf_range_scratch_bytes.restype = sz
+        L.smf_range_scratch_bytes.argtypes = [u32, u32]
+        L.smf_chunk_offsets_device.restype = i32
+        L.smf_chunk_offsets_device.argtypes = [vp, vp, u32, vp, vp]
+        L.smf_compress_indexed_device.restype = i32
+        L.smf_compress_indexed_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, ctypes.c_int, pch, vp, u32, vp, vp]
+        L.smf_uncompress_ranges_device.restype = i32
+        L.smf_uncompress_ranges_device.argtypes = [vp, vp, u64, pch, vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp]
+        L.smf_uncompress_range.restype = i32
+        L.smf_uncompress_range.argtypes = [vp, vp, sz, u64, u64, vp, ctypes.POINTER(sz)]
         _lib = L
     return _lib
 
@@ -171,6 +196,74 @@ def index_framed(data, max_chunks=None):
     return s, arrays
 
 
+INDEX_KEYS = ("type", "pay_off", "pay_len", "crc", "ulen")
+
+
+class FramedIndex:
+    """The seek index of a framed stream: numpy arrays type / pay_off / pay_len / crc / ulen, one
+    entry per data chunk, and chunk_off (nchunks + 1, the exclusive scan of ulen: chunk c holds
+    bytes [chunk_off[c], chunk_off[c + 1]) of the content)."""
+
+    def __init__(self, arrays, chunk_off):
+        for k in INDEX_KEYS:
+            setattr(self, k, np.ascontiguousarray(arrays[k]))
+        self.chunk_off = np.ascontiguousarray(chunk_off, dtype=np.uint64)
+
+    @property
+    def nchunks(self):
+        return self.chunk_off.size - 1
+
+    @property
+    def total_length(self):
+        return int(self.chunk_off[-1])
+
+    def arrays(self):
+        return {k: getattr(self, k) for k in INDEX_KEYS}
+
+    def _struct(self):
+        return Chunks(*(getattr(self, k).ctypes.data for k in INDEX_KEYS))
+
+
+def chunk_offsets(ulen):
+    """smf_chunk_offsets: the exclusive scan of ulen, with the total as the last entry (uint64)."""
+    ulen = np.ascontiguousarray(ulen, dtype=np.uint32)
+    off = np.zeros(ulen.size + 1, np.uint64)
+    st = lib().smf_chunk_offsets(ulen.ctypes.data, ulen.size, off.ctypes.data)
+    if st:
+        raise FramingError(st)
+    return off
+
+
+def seek_index_framed(data):
+    """index_framed plus chunk_off, as a FramedIndex; raises SnappyError with the walk's
+    structural error."""
+    s, arrays = index_framed(data)
+    if s.status:
+        raise FramingError(s.status)
+    return FramedIndex(arrays, chunk_offsets(arrays["ulen"]))
+
+
+def range_chunk_count(lo, length):
+    """smf_range_chunk_count: the chunks bytes [lo, lo + length) touch in a stream of this
+    library's encoder (a foreign stream may have smaller chunks: see range_plan)."""
+    return lib().smf_range_chunk_count(int(lo), int(length))
+
+
+def range_plan(index, n, ranges, max_range_chunks=0xFFFFFFFF):
+    """smf_range_plan, the device's plan on the host: (rc, first, count, status, total) for the
+    (lo, length) pairs `ranges` over `index` (a FramedIndex) of an n-byte framed stream."""
+    lo = np.array([r[0] for r in ranges], dtype=np.uint64)
+    ln = np.array([r[1] for r in ranges], dtype=np.uint64)
+    first, count = np.zeros(lo.size, np.uint32), np.zeros(lo.size, np.uint32)
+    status = np.zeros(lo.size, np.int32)
+    total = ctypes.c_uint64(0)
+    ch = index._struct()
+    rc = lib().smf_range_plan(ctypes.byref(ch), index.chunk_off.ctypes.data, index.nchunks, int(n), lo.ctypes.data,
+                              ln.ctypes.data, lo.size, int(max_range_chunks), first.ctypes.data, count.ctypes.data,
+                              status.ctypes.data, ctypes.byref(total))
+    return int(rc), first, count, status, total.value
+
+
 def length_uncompressed_framed(data):
     """The stream's total uncompressed length from its chunk headers (no device, no CRC check)."""
     src, n, keep = _in_arg(data)
@@ -181,10 +274,13 @@ def length_uncompressed_framed(data):
     return res.value
 
 
-def compress_framed(data, mode="fast", device=0):
+def compress_framed(data, mode="fast", device=0, return_index=False):
     """Frame `data`: the stream identifier, then one chunk per 64 KiB block -- compressed (0x00)
     iff its Snappy stream is strictly shorter than the block, else uncompressed (0x01) -- each
-    with the masked CRC-32C of its uncompressed bytes.  Computed on the GPU."""
+    with the masked CRC-32C of its uncompressed bytes.  Computed on the GPU.  return_index=True:
+    (bytes, FramedIndex), the index being the encoder's own (smf_compress_indexed_device)."""
+    if return_index:
+        return _compress_framed_indexed(data, mode, device)
     src, n, keep = _in_arg(data)
     cap = 10 + 8 * ((n + 65535) // 65536) + n
     ptr, buf = _out_buffer(cap)
@@ -206,6 +302,82 @@ def uncompress_framed(data, device=0):
     if st:
         raise FramingError(st)
     return ctypes.string_at(ptr, ol.value)
+
+
+def _compress_framed_indexed(data, mode, device):
+    import torch
+    src, n, keep = _in_arg(data)
+    dev = "cuda:%d" % device
+    host = np.frombuffer(ctypes.string_at(src, n), np.uint8) if n else np.zeros(0, np.uint8)
+    d_in = torch.from_numpy(host.copy()).to(dev)
+    nblk = (n + 65535) // 65536
+    d_out = torch.empty(10 + 8 * nblk + n, dtype=torch.uint8, device=dev)
+    d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+    d_st = torch.zeros(1, dtype=torch.int32, device=dev)
+    arrays, d_off = device_chunks(nblk, device), torch.zeros(nblk + 1, dtype=torch.int64, device=dev)
+    d_nc = torch.zeros(1, dtype=torch.int32, device=dev)
+    compress_framed_indexed_device(d_in, d_out, d_len, d_st, arrays, d_off, d_nc, mode=mode)
+    if int(d_st.item()):
+        raise FramingError(int(d_st.item()))
+    nc = int(d_nc.item())
+    index = FramedIndex({k: arrays[k][:nc].cpu().numpy().view(_UNSIGNED[k]) for k in INDEX_KEYS},
+                        d_off[:nc + 1].cpu().numpy().view(np.uint64))
+    return d_out[:int(d_len.item())].cpu().numpy().tobytes(), index
+
+
+def uncompress_framed_range(data, lo, length, index=None, device=0):
+    """Bytes [lo, lo + length) of the framed stream's content; only the chunks they touch are
+    uploaded, decoded and CRC-checked.  index=None: the stream is walked on the host
+    (smf_uncompress_range), and a structural error anywhere in it is raised; with a FramedIndex
+    (from compress_framed(..., return_index=True) or seek_index_framed) nothing is walked."""
+    if index is not None:
+        out, st = uncompress_framed_ranges(data, [(lo, length)], index=index, device=device)
+        if st[0]:
+            raise FramingError(int(st[0]))
+        return out[0]
+    if int(lo) + int(length) > length_uncompressed_framed(data):  # (before any room is made for it)
+        raise FramingError(33)
+    src, n, keep = _in_arg(data)
+    ptr, buf = _out_buffer(int(length))
+    ol = ctypes.c_size_t(int(length))
+    st = lib().smf_uncompress_range(context(device), src, n, int(lo), int(length), ptr, ctypes.byref(ol))
+    if st:
+        raise FramingError(st)
+    return ctypes.string_at(ptr, ol.value)
+
+
+def uncompress_framed_ranges(data, ranges, index=None, device=0):
+    """One batched ranged decode (smf_uncompress_ranges_device) of the (lo, length) pairs
+    `ranges`: (list of bytes, int32 array of statuses); a failing range gives b"" and its status.
+    index=None walks the stream on the host first (raises on a structural error)."""
+    import torch
+    if index is None:
+        index = seek_index_framed(data)
+    src, n, keep = _in_arg(data)
+    dev = "cuda:%d" % device
+    ranges = [(int(lo), int(ln)) for lo, ln in ranges]
+    if not ranges:
+        return [], np.zeros(0, np.int32)
+    rc, _, count, status, total = range_plan(index, n, ranges)
+    host = np.frombuffer(ctypes.string_at(src, n), np.uint8) if n else np.zeros(0, np.uint8)
+    d_in = torch.from_numpy(host.copy()).to(dev)
+    arrays = {k: torch.from_numpy(getattr(index, k).view(_SIGNED[k])).to(dev) for k in INDEX_KEYS}
+    d_off = torch.from_numpy(index.chunk_off.view(np.int64)).to(dev)
+    # outputs behind one another, each at a 16-byte boundary; a range that leaves the stream is
+    # rejected before anything is written and gets no room
+    room = [ln if lo + ln <= index.total_length else 0 for lo, ln in ranges]
+    out_off = np.concatenate([[0], np.cumsum([(r + 15) // 16 * 16 for r in room])]).astype(np.int64)
+    d_out = torch.empty(max(int(out_off[-1]), 1), dtype=torch.uint8, device=dev)
+    d_lo = torch.tensor(np.array([r[0] for r in ranges], np.uint64).view(np.int64), device=dev)
+    d_ln = torch.tensor(np.array([r[1] for r in ranges], np.uint64).view(np.int64), device=dev)
+    d_oo = torch.from_numpy(out_off[:-1].copy()).to(dev)
+    d_ol = torch.zeros(len(ranges), dtype=torch.int64, device=dev)
+    d_st = torch.zeros(len(ranges), dtype=torch.int32, device=dev)
+    uncompress_ranges_device(d_in, arrays, d_off, index.nchunks, d_lo, d_ln, int(total), d_out, d_oo, d_ol, d_st, n=n)
+    st = d_st.cpu().numpy()
+    lens = d_ol.cpu().numpy()
+    out = d_out.cpu().numpy()
+    return [out[o:o + int(k)].tobytes() for o, k in zip(out_off[:-1].tolist(), lens.tolist())], st
 
 
 def validate_framed(data, device=0):
@@ -237,6 +409,10 @@ def device_chunks(max_chunks, device=0):
 
 def _chunks_struct(arrays):
     return Chunks(*(arrays[k].data_ptr() for k in ("type", "pay_off", "pay_len", "crc", "ulen")))
+
+
+_SIGNED = {"type": np.uint8, "pay_off": np.int64, "pay_len": np.int32, "crc": np.int32, "ulen": np.int32}
+_UNSIGNED = {"type": np.uint8, "pay_off": np.uint64, "pay_len": np.uint32, "crc": np.uint32, "ulen": np.uint32}
 
 
 def crc32c_batch_device(d_in, d_off, d_len, d_crc, masked=False, stream=None, device=None):
@@ -316,6 +492,49 @@ def uncompress_framed_device(d_in, d_out, d_out_len, d_status, n=None, stream=No
                                            _ptr(d_out_len), _ptr(d_status), _sp(stream, dev)))
 
 
+def compress_framed_indexed_device(d_in, d_out, d_out_len, d_status, arrays, d_chunk_off, d_nchunks, mode="fast",
+                                   stream=None, device=None):
+    """compress_framed_device that also writes the stream's seek index (smf_compress_indexed_device):
+    arrays = device_chunks(max_chunks), d_chunk_off int64[max_chunks + 1], d_nchunks int32[1];
+    max_chunks is taken from d_chunk_off and must be at least ceil(d_in.numel() / 65536)."""
+    dev = _dev(d_out, device)
+    n = d_in.numel()
+    ch = _chunks_struct(arrays)
+    st = lib().smf_compress_indexed_device(context(dev), _ptr(d_in) if n else None, n, _ptr(d_out), d_out.numel(),
+                                           _ptr(d_out_len), _ptr(d_status), _mode(mode), ctypes.byref(ch),
+                                           _ptr(d_chunk_off), d_chunk_off.numel() - 1, _ptr(d_nchunks), _sp(stream, dev))
+    if st:
+        raise FramingError(st)
+
+
+def chunk_offsets_device(d_ulen, nchunks, d_chunk_off, stream=None, device=None):
+    """d_chunk_off (int64[nchunks + 1]) = the exclusive scan of d_ulen[:nchunks] (int32, as
+    device_chunks()["ulen"]): completes an index_framed_device index."""
+    dev = _dev(d_chunk_off, device)
+    st = lib().smf_chunk_offsets_device(context(dev), _ptr(d_ulen), int(nchunks), _ptr(d_chunk_off), _sp(stream, dev))
+    if st:
+        raise FramingError(st)
+
+
+def uncompress_ranges_device(d_in, arrays, d_chunk_off, nchunks, d_lo, d_len, max_range_chunks, d_out, d_out_off,
+                             d_out_len, d_range_status, n=None, stream=None, device=None):
+    """Batched ranged decode (smf_uncompress_ranges_device) of the indexed framed stream d_in[:n]:
+    range r = bytes [d_lo[r], d_lo[r] + d_len[r]) of the content, written to d_out[d_out_off[r]:];
+    d_lo / d_len / d_out_off / d_out_len int64[nranges], d_range_status int32[nranges]."""
+    dev = _dev(d_out, device)
+    n = d_in.numel() if n is None else int(n)
+    ch = _chunks_struct(arrays)
+    st = lib().smf_uncompress_ranges_device(context(dev), _ptr(d_in) if n else None, n, ctypes.byref(ch),
+                                            _ptr(d_chunk_off), int(nchunks), _ptr(d_lo), _ptr(d_len), d_lo.numel(),
+                                            int(max_range_chunks), _ptr(d_out), _ptr(d_out_off), _ptr(d_out_len),
+                                            _ptr(d_range_status), _sp(stream, dev))
+    if st:
+        raise FramingError(st)
+
+
 __all__ = ["FRAMING_ABI_SYMBOLS", "MODES", "compress_framed", "uncompress_framed", "length_uncompressed_framed",
            "validate_framed", "index_framed", "crc32c_batch_device", "compress_framed_device", "index_framed_device",
-           "uncompressed_length_framed_device", "uncompress_chunks_device", "uncompress_framed_device"]
+           "uncompressed_length_framed_device", "uncompress_chunks_device", "uncompress_framed_device", "FramedIndex",
+           "seek_index_framed", "chunk_offsets", "range_chunk_count", "range_plan", "uncompress_framed_range",
+           "uncompress_framed_ranges", "compress_framed_indexed_device", "chunk_offsets_device",
+           "uncompress_ranges_device"]
