@@ -3,6 +3,7 @@
 // smf_kernels.hip and smf_range.hip (the seek index and the ranged decode).  The host-only entry
 // points live in smf_host.cpp.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -11,6 +12,8 @@
 #include <new>
 #include <vector>
 
+#include "../common/smc_hip_host.h"
+#include "../common/smc_layout.h"
 #include "smf_format.h"
 #include "smf_internal.h"
 
@@ -20,52 +23,94 @@
 
 namespace {
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t n) {  // (growing frees the old buffer: hipFree waits for the device)
-    if (n <= cap) return hipSuccess;
-    release();
-    const size_t want = n < 4096 ? 4096 : n;
-    const hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    else p = nullptr;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
+constexpr uint64_t kSlotPitch = smc::kFramingSlotPitch;
 
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
+// ---- scratch layouts: each is sized by its own carve from a null base (smc::Carve) ----------------
+struct CompressMeta {  // per block (ctx->cmeta)
+  uint64_t *in_off, *slot_off, *dst_off;
+  uint32_t *in_len, *comp_len, *crc;
+  uint8_t* type;
+  uintptr_t end;
 };
+constexpr CompressMeta carve_compress(uintptr_t base, size_t n) {
+  smc::Carve c{base};
+  CompressMeta m{};
+  m.in_off = c.take<uint64_t>(n);
+  m.slot_off = c.take<uint64_t>(n);
+  m.dst_off = c.take<uint64_t>(n);
+  m.in_len = c.take<uint32_t>(n);
+  m.comp_len = c.take<uint32_t>(n);
+  m.crc = c.take<uint32_t>(n);
+  m.type = c.take<uint8_t>(n);
+  m.end = c.p;
+  return m;
+}
+constexpr size_t compress_bytes(size_t n) { return carve_compress(0, n).end; }
 
-// consecutive arrays of one scratch buffer, the widest element types first
-struct Carve {
-  uint8_t* p;
-  template <typename T>
-  T* take(size_t n) {
-    T* r = reinterpret_cast<T*>(p);
-    p += (n * sizeof(T) + 15) / 16 * 16;
-    return r;
-  }
+struct DecodeMeta {  // per chunk (ctx->dmeta)
+  uint64_t* out_off;
+  uint32_t *cap, *dec_len, *dec_out_len, *crc_out;
+  int32_t *pre, *dec_status;
+  uintptr_t end;
 };
+constexpr DecodeMeta carve_decode(uintptr_t base, size_t n) {
+  smc::Carve c{base};
+  DecodeMeta m{};
+  m.out_off = c.take<uint64_t>(n);
+  m.cap = c.take<uint32_t>(n);
+  m.dec_len = c.take<uint32_t>(n);
+  m.pre = c.take<int32_t>(n);
+  m.dec_out_len = c.take<uint32_t>(n);
+  m.dec_status = c.take<int32_t>(n);
+  m.crc_out = c.take<uint32_t>(n);
+  m.end = c.p;
+  return m;
+}
+constexpr size_t decode_bytes(size_t n) { return carve_decode(0, n).end; }
 
-constexpr uint64_t kSlotPitch = 76496;  // sm_max_compressed_length(65536) = 76490, 16-byte aligned
-constexpr size_t kCompressMeta = 8 + 8 + 8 + 4 + 4 + 4 + 1;      // scratch bytes per block (+ padding)
-constexpr size_t kDecodeMeta = 8 + 4 + 4 + 4 + 4 + 4 + 4;        // per chunk
-constexpr size_t kIndexMeta = 8 + 4 + 4 + 4 + 4 + 1;             // per index entry (+ chunk status)
-inline size_t meta_bytes(size_t per, size_t n) { return per * n + 16 * 8; }
+struct IndexMeta {  // a stream's index and the per-chunk status behind it (ctx->idx)
+  smf_chunks ch;
+  int32_t* chunk_status;
+  uintptr_t end;
+};
+constexpr IndexMeta carve_index(uintptr_t base, size_t n) {
+  smc::Carve c{base};
+  IndexMeta m{};
+  m.ch.pay_off = c.take<uint64_t>(n);
+  m.ch.pay_len = c.take<uint32_t>(n);
+  m.ch.crc = c.take<uint32_t>(n);
+  m.ch.ulen = c.take<uint32_t>(n);
+  m.chunk_status = c.take<int32_t>(n);
+  m.ch.type = c.take<uint8_t>(n);
+  m.end = c.p;
+  return m;
+}
+constexpr size_t index_bytes(size_t n) { return carve_index(0, n).end; }
+
+// A buffer of cap bytes holds cap / kIndexEntryBound entries, for every cap a DevBuf has (4096 at
+// the least): index_bytes(e) <= e * index_bytes(16) / 16 + 15 * index_bytes(1) / 16, the bytes of
+// an entry and under 16 of padding per array, and with e = cap / kIndexEntryBound the padding is
+// at most e.
+constexpr size_t kIndexEntryBound = 26;
+static_assert(index_bytes(16) / 16 < kIndexEntryBound && 15 * (index_bytes(1) / 16) <= 4096 / kIndexEntryBound,
+              "kIndexEntryBound does not cover an index entry of carve_index");
+
+// ---- the small device results in ctx->res ---------------------------------------------------------
+struct LenStatus {  // what a *_device call leaves in *d_out_len and *d_status
+  uint64_t len;
+  int32_t st, pad;
+};
+struct Results {
+  smf_summary sum;  // smf_uncompress_device, smf_uncompressed_length_device: the walk's summary
+  alignas(64) LenStatus io;  // smf_compress, smf_uncompress, smf_validate
+  alignas(64) uint64_t range[3];  // smf_uncompress_range: lo, len, out_off
+  alignas(32) LenStatus range_out;
+};
+static_assert(offsetof(Results, io) == 64 && offsetof(Results, range) == 128 && offsetof(Results, range_out) == 160 &&
+                  sizeof(Results) <= 4096,
+              "the layout of ctx->res");
+
+bool valid_chunks(const smf_chunks& ch) { return ch.type && ch.pay_off && ch.pay_len && ch.crc && ch.ulen; }
 
 }  // namespace
 
@@ -83,29 +128,32 @@ struct smf_ctx {
   std::mutex mu;                 // serialises the host-buffer entry points
 };
 
-#define SMF_CHECK(x)                               \
-  do {                                             \
-    if ((x) != hipSuccess) return SM_ERR_DEVICE;   \
-  } while (0)
-#define SMF_PASS(x)                \
-  do {                             \
-    const sm_status st_ = (x);     \
-    if (st_ != SM_OK) return st_;  \
-  } while (0)
-
 namespace {
 
 // the index arrays of up to n chunks in ctx->idx, and the per-chunk status behind them
-sm_status index_scratch(smf_ctx* ctx, size_t n, smf_chunks& ch, int32_t*& chunk_status) {
-  SMF_CHECK(ctx->idx.ensure(meta_bytes(kIndexMeta, n)));
-  Carve c{(uint8_t*)ctx->idx.p};
-  ch.pay_off = c.take<uint64_t>(n);
-  ch.pay_len = c.take<uint32_t>(n);
-  ch.crc = c.take<uint32_t>(n);
-  ch.ulen = c.take<uint32_t>(n);
-  chunk_status = c.take<int32_t>(n);
-  ch.type = c.take<uint8_t>(n);
+sm_status index_scratch(smf_ctx* ctx, size_t n, IndexMeta& m) {
+  SM_CHECK(ctx->idx.ensure(index_bytes(n)));
+  m = carve_index((uintptr_t)ctx->idx.p, n);
   return SM_OK;
+}
+
+// a host index's entries [first, first + count) to the device arrays
+sm_status upload_chunks(const smf_chunks& dst, const smf_chunks& src, uint32_t first, uint32_t count, hipStream_t s) {
+  if (count == 0) return SM_OK;
+  const size_t k = count;
+  SM_CHECK(hipMemcpyAsync(dst.type, src.type + first, k, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(dst.pay_off, src.pay_off + first, 8 * k, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(dst.pay_len, src.pay_len + first, 4 * k, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(dst.crc, src.crc + first, 4 * k, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(dst.ulen, src.ulen + first, 4 * k, hipMemcpyHostToDevice, s));
+  return SM_OK;
+}
+
+// The pair a *_device call on s left at d: read back (synchronises s); a status in it is returned.
+sm_status read_back(const LenStatus* d, LenStatus& r, hipStream_t s) {
+  SM_CHECK(hipMemcpyAsync(&r, d, sizeof(r), hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipStreamSynchronize(s));
+  return r.st;
 }
 
 }  // namespace
@@ -167,8 +215,8 @@ sm_status smf_crc32c_batch_device(smf_ctx* ctx, const uint8_t* d_in, const uint6
   if (nblk == 0) return SM_OK;
   if (!d_in || !d_off || !d_len || !d_crc) return SM_ERR_ARGUMENT;
   DeviceGuard g(ctx->device);
-  SMF_CHECK(smf::launch_crc32c(d_in, d_off, d_len, nblk, d_crc, masked ? 1 : 0, (const smf::CrcLut*)ctx->lut.p,
-                               (hipStream_t)stream));
+  SM_CHECK(smf::launch_crc32c(d_in, d_off, d_len, nblk, d_crc, masked ? 1 : 0, (const smf::CrcLut*)ctx->lut.p,
+                              (hipStream_t)stream));
   return SM_OK;
 }
 
@@ -177,7 +225,7 @@ static sm_status compress_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, 
                                  uint64_t* d_out_len, int32_t* d_status, int mode, const smf_chunks* d_chunks,
                                  uint64_t* d_chunk_off, uint32_t max_chunks, uint32_t* d_nchunks, void* stream) {
   if (!ctx || !d_out || !d_out_len || !d_status || (n && !d_in)) return SM_ERR_ARGUMENT;
-  if (mode != SM_MODE_REFERENCE && mode != SM_MODE_FAST && mode != SM_MODE_FAST_DENSE) return SM_ERR_ARGUMENT;
+  if (!valid_mode(mode)) return SM_ERR_ARGUMENT;
   const uint64_t nblk64 = (n + smf::kBlock - 1) / smf::kBlock;
   if (nblk64 > 0x7fffffffull) return SM_ERR_INPUT_TOO_LARGE;
   if (out_capacity < smf_max_framed_length(n)) return SM_BUFFER_TOO_SMALL;
@@ -188,29 +236,22 @@ static sm_status compress_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, 
     if (nblk64) {
       if (!d_chunks) return SM_ERR_ARGUMENT;
       ich = *d_chunks;
-      if (!ich.type || !ich.pay_off || !ich.pay_len || !ich.crc || !ich.ulen) return SM_ERR_ARGUMENT;
+      if (!valid_chunks(ich)) return SM_ERR_ARGUMENT;
     }
   }
   const uint32_t nblk = (uint32_t)nblk64;
   hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(ctx->device);
-  SMF_CHECK(ctx->cmeta.ensure(meta_bytes(kCompressMeta, nblk)));
-  SMF_CHECK(ctx->slots.ensure((size_t)nblk * kSlotPitch));
-  Carve c{(uint8_t*)ctx->cmeta.p};
-  uint64_t* in_off = c.take<uint64_t>(nblk);
-  uint64_t* slot_off = c.take<uint64_t>(nblk);
-  uint64_t* dst_off = c.take<uint64_t>(nblk);
-  uint32_t* in_len = c.take<uint32_t>(nblk);
-  uint32_t* comp_len = c.take<uint32_t>(nblk);
-  uint32_t* crc = c.take<uint32_t>(nblk);
-  uint8_t* type = c.take<uint8_t>(nblk);
+  SM_CHECK(ctx->cmeta.ensure(compress_bytes(nblk)));
+  SM_CHECK(ctx->slots.ensure((size_t)nblk * kSlotPitch));
+  const CompressMeta m = carve_compress((uintptr_t)ctx->cmeta.p, nblk);
   uint8_t* slots = (uint8_t*)ctx->slots.p;
-  SMF_CHECK(smf::launch_frame_compress_plan(n, nblk, kSlotPitch, in_off, in_len, slot_off, s));
-  SMF_PASS(sm_compress_batch_device(ctx->sm, d_in, in_off, in_len, nblk, slots, slot_off, comp_len, mode, stream));
-  SMF_CHECK(smf::launch_crc32c(d_in, in_off, in_len, nblk, crc, 1, (const smf::CrcLut*)ctx->lut.p, s));
-  const smf::PackArgs a{d_in, in_off, in_len, slots, slot_off, comp_len, crc, type, dst_off, nblk, d_out};
-  SMF_CHECK(smf::launch_frame_pack(a, d_out_len, d_status, s));
-  if (d_chunk_off) SMF_CHECK(smf::launch_frame_index_out(a, n, ich, d_chunk_off, d_nchunks, d_status, s));
+  SM_CHECK(smf::launch_frame_compress_plan(n, nblk, kSlotPitch, m.in_off, m.in_len, m.slot_off, s));
+  SM_PASS(sm_compress_batch_device(ctx->sm, d_in, m.in_off, m.in_len, nblk, slots, m.slot_off, m.comp_len, mode, stream));
+  SM_CHECK(smf::launch_crc32c(d_in, m.in_off, m.in_len, nblk, m.crc, 1, (const smf::CrcLut*)ctx->lut.p, s));
+  const smf::PackArgs a{d_in, m.in_off, m.in_len, slots, m.slot_off, m.comp_len, m.crc, m.type, m.dst_off, nblk, d_out};
+  SM_CHECK(smf::launch_frame_pack(a, d_out_len, d_status, s));
+  if (d_chunk_off) SM_CHECK(smf::launch_frame_index_out(a, n, ich, d_chunk_off, d_nchunks, d_status, s));
   return SM_OK;
 }
 
@@ -233,7 +274,7 @@ sm_status smf_chunk_offsets_device(smf_ctx* ctx, const uint32_t* d_ulen, uint32_
                                    void* stream) {
   if (!ctx || !d_chunk_off || (nchunks && !d_ulen)) return SM_ERR_ARGUMENT;
   DeviceGuard g(ctx->device);
-  SMF_CHECK(smf::launch_chunk_offsets(d_ulen, nchunks, d_chunk_off, (hipStream_t)stream));
+  SM_CHECK(smf::launch_chunk_offsets(d_ulen, nchunks, d_chunk_off, (hipStream_t)stream));
   return SM_OK;
 }
 
@@ -249,26 +290,26 @@ sm_status smf_uncompress_ranges_device(smf_ctx* ctx, const uint8_t* d_in, uint64
   if (nchunks) {
     if (!d_in || !d_out || !d_chunks) return SM_ERR_ARGUMENT;
     ch = *d_chunks;
-    if (!ch.type || !ch.pay_off || !ch.pay_len || !ch.crc || !ch.ulen) return SM_ERR_ARGUMENT;
+    if (!valid_chunks(ch)) return SM_ERR_ARGUMENT;
   }
   hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(ctx->device);
   const uint32_t m = max_range_chunks;
-  SMF_CHECK(ctx->rmeta.ensure(smf::range_meta_bytes(nranges, m)));
-  SMF_CHECK(ctx->redge.ensure(smf::range_edge_bytes(nranges)));
+  SM_CHECK(ctx->rmeta.ensure(smf::range_meta_bytes(nranges, m)));
+  SM_CHECK(ctx->redge.ensure(smf::range_edge_bytes(nranges)));
   smf::RangeArgs a{d_in,    n,     ch,        d_chunk_off, nchunks,        d_lo,
                    d_len,   nranges, m,       d_out,       d_out_off,      d_out_len,
                    d_range_status, (uint8_t*)ctx->redge.p, smf::carve_range((uint8_t*)ctx->rmeta.p, nranges, m)};
-  SMF_CHECK(smf::launch_range_plan(a, s));
+  SM_CHECK(smf::launch_range_plan(a, s));
   if (m) {
     // every slot's output offset is relative to the edge slots (smf_range.hip, k_range_slots)
-    SMF_PASS(sm_uncompress_batch_device(ctx->sm, d_in ? d_in : a.edge, a.s.in_off, a.s.dec_len, m, a.edge, a.s.out_off,
-                                        a.s.cap, a.s.dec_out_len, a.s.dec_status, stream));
-    SMF_CHECK(smf::launch_range_copy(a, s));
-    SMF_CHECK(smf::launch_crc32c(a.edge, a.s.out_off, a.s.cap, m, a.s.crc_out, 1, (const smf::CrcLut*)ctx->lut.p, s));
-    SMF_CHECK(smf::launch_range_trim(a, s));
+    SM_PASS(sm_uncompress_batch_device(ctx->sm, d_in ? d_in : a.edge, a.s.in_off, a.s.dec_len, m, a.edge, a.s.out_off,
+                                       a.s.cap, a.s.dec_out_len, a.s.dec_status, stream));
+    SM_CHECK(smf::launch_range_copy(a, s));
+    SM_CHECK(smf::launch_crc32c(a.edge, a.s.out_off, a.s.cap, m, a.s.crc_out, 1, (const smf::CrcLut*)ctx->lut.p, s));
+    SM_CHECK(smf::launch_range_trim(a, s));
   }
-  SMF_CHECK(smf::launch_range_verdicts(a, s));
+  SM_CHECK(smf::launch_range_verdicts(a, s));
   return SM_OK;
 }
 
@@ -277,11 +318,9 @@ sm_status smf_index_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, const 
   if (!ctx || !d_summary || (n && !d_in)) return SM_ERR_ARGUMENT;
   smf_chunks none{nullptr, nullptr, nullptr, nullptr, nullptr};
   if (d_chunks && max_chunks == 0) d_chunks = &none;  // (nothing is stored; more than 0 chunks is still too small)
-  if (d_chunks && max_chunks &&
-      (!d_chunks->type || !d_chunks->pay_off || !d_chunks->pay_len || !d_chunks->crc || !d_chunks->ulen))
-    return SM_ERR_ARGUMENT;
+  if (d_chunks && max_chunks && !valid_chunks(*d_chunks)) return SM_ERR_ARGUMENT;
   DeviceGuard g(ctx->device);
-  SMF_CHECK(smf::launch_frame_index(d_in, n, d_chunks, max_chunks, d_summary, (hipStream_t)stream));
+  SM_CHECK(smf::launch_frame_index(d_in, n, d_chunks, max_chunks, d_summary, (hipStream_t)stream));
   return SM_OK;
 }
 
@@ -289,9 +328,9 @@ sm_status smf_uncompressed_length_device(smf_ctx* ctx, const uint8_t* d_in, uint
                                          int32_t* d_status, void* stream) {
   if (!ctx || !d_len || !d_status || (n && !d_in)) return SM_ERR_ARGUMENT;
   DeviceGuard g(ctx->device);
-  smf_summary* sum = (smf_summary*)ctx->res.p;
-  SMF_CHECK(smf::launch_frame_index(d_in, n, nullptr, 0, sum, (hipStream_t)stream));
-  SMF_CHECK(smf::launch_frame_result(d_len, 0, sum, d_status, 0, (hipStream_t)stream));
+  smf_summary* sum = &((Results*)ctx->res.p)->sum;
+  SM_CHECK(smf::launch_frame_index(d_in, n, nullptr, 0, sum, (hipStream_t)stream));
+  SM_CHECK(smf::launch_frame_result(d_len, 0, sum, d_status, 0, (hipStream_t)stream));
   return SM_OK;
 }
 
@@ -303,25 +342,18 @@ sm_status smf_uncompress_chunks_device(smf_ctx* ctx, const uint8_t* d_in, const 
   if (nchunks) {
     if (!d_in || !d_out || !d_chunk_status || !d_chunks) return SM_ERR_ARGUMENT;
     ch = *d_chunks;
-    if (!ch.type || !ch.pay_off || !ch.pay_len || !ch.crc || !ch.ulen) return SM_ERR_ARGUMENT;
+    if (!valid_chunks(ch)) return SM_ERR_ARGUMENT;
   }
   hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(ctx->device);
-  SMF_CHECK(ctx->dmeta.ensure(meta_bytes(kDecodeMeta, nchunks)));
-  Carve c{(uint8_t*)ctx->dmeta.p};
-  uint64_t* out_off = c.take<uint64_t>(nchunks);
-  uint32_t* cap = c.take<uint32_t>(nchunks);
-  uint32_t* dec_len = c.take<uint32_t>(nchunks);
-  int32_t* pre = c.take<int32_t>(nchunks);
-  uint32_t* dec_out_len = c.take<uint32_t>(nchunks);
-  int32_t* dec_status = c.take<int32_t>(nchunks);
-  uint32_t* crc_out = c.take<uint32_t>(nchunks);
-  SMF_CHECK(smf::launch_frame_plan(ch, nchunks, out_capacity, out_off, cap, dec_len, pre, d_out_len, s));
-  SMF_PASS(sm_uncompress_batch_device(ctx->sm, d_in, ch.pay_off, dec_len, nchunks, d_out, out_off, cap, dec_out_len,
-                                      dec_status, stream));
-  SMF_CHECK(smf::launch_frame_copy(d_in, ch, nchunks, out_off, cap, d_out, s));
-  SMF_CHECK(smf::launch_crc32c(d_out, out_off, cap, nchunks, crc_out, 1, (const smf::CrcLut*)ctx->lut.p, s));
-  SMF_CHECK(smf::launch_frame_verify(ch, nchunks, pre, dec_status, crc_out, d_chunk_status, d_status, s));
+  SM_CHECK(ctx->dmeta.ensure(decode_bytes(nchunks)));
+  const DecodeMeta m = carve_decode((uintptr_t)ctx->dmeta.p, nchunks);
+  SM_CHECK(smf::launch_frame_plan(ch, nchunks, out_capacity, m.out_off, m.cap, m.dec_len, m.pre, d_out_len, s));
+  SM_PASS(sm_uncompress_batch_device(ctx->sm, d_in, ch.pay_off, m.dec_len, nchunks, d_out, m.out_off, m.cap,
+                                     m.dec_out_len, m.dec_status, stream));
+  SM_CHECK(smf::launch_frame_copy(d_in, ch, nchunks, m.out_off, m.cap, d_out, s));
+  SM_CHECK(smf::launch_crc32c(d_out, m.out_off, m.cap, nchunks, m.crc_out, 1, (const smf::CrcLut*)ctx->lut.p, s));
+  SM_CHECK(smf::launch_frame_verify(ch, nchunks, m.pre, m.dec_status, m.crc_out, d_chunk_status, d_status, s));
   return SM_OK;
 }
 
@@ -330,30 +362,30 @@ sm_status smf_uncompress_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, u
   if (!ctx || !d_out_len || !d_status || (n && !d_in)) return SM_ERR_ARGUMENT;
   hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(ctx->device);
-  smf_summary* d_sum = (smf_summary*)ctx->res.p;
+  smf_summary* d_sum = &((Results*)ctx->res.p)->sum;
   smf_summary sum;
-  smf_chunks ch;
-  int32_t* chunk_status = nullptr;
-  // entries for a stream whose chunks average 1 KiB or more; a stream of smaller chunks walks twice
-  size_t entries = std::max<size_t>(ctx->idx.cap / (kIndexMeta + 1), n / 1024 + 64);
+  IndexMeta ix;
+  // entries for a stream whose chunks average 1 KiB or more, or all the buffer already holds; a
+  // stream of smaller chunks walks twice
+  size_t entries = std::max<size_t>(ctx->idx.cap / kIndexEntryBound, n / 1024 + 64);
   entries = std::min<size_t>(entries, 0xffffffffu);
   for (int pass = 0;; ++pass) {
-    SMF_PASS(index_scratch(ctx, entries, ch, chunk_status));
-    SMF_CHECK(smf::launch_frame_index(d_in, n, &ch, (uint32_t)entries, d_sum, s));
-    SMF_CHECK(hipMemcpyAsync(&sum, d_sum, sizeof(sum), hipMemcpyDeviceToHost, s));
-    SMF_CHECK(hipStreamSynchronize(s));  // the documented synchronisation
+    SM_PASS(index_scratch(ctx, entries, ix));
+    SM_CHECK(smf::launch_frame_index(d_in, n, &ix.ch, (uint32_t)entries, d_sum, s));
+    SM_CHECK(hipMemcpyAsync(&sum, d_sum, sizeof(sum), hipMemcpyDeviceToHost, s));
+    SM_CHECK(hipStreamSynchronize(s));  // the documented synchronisation
     if (sum.status != SM_BUFFER_TOO_SMALL || pass) break;
     entries = sum.nchunks;
   }
   sm_status st = sum.status;
   if (st == SM_OK && sum.total_length > out_capacity) st = SM_BUFFER_TOO_SMALL;
   if (st != SM_OK) {
-    SMF_CHECK(smf::launch_frame_result(d_out_len, sum.total_length, nullptr, d_status, st, s));
+    SM_CHECK(smf::launch_frame_result(d_out_len, sum.total_length, nullptr, d_status, st, s));
     return st;
   }
   if (sum.nchunks && !d_out) return SM_ERR_ARGUMENT;
-  return smf_uncompress_chunks_device(ctx, d_in, &ch, sum.nchunks, d_out, out_capacity, chunk_status, d_out_len, d_status,
-                                      stream);
+  return smf_uncompress_chunks_device(ctx, d_in, &ix.ch, sum.nchunks, d_out, out_capacity, ix.chunk_status, d_out_len,
+                                      d_status, stream);
 }
 
 sm_status smf_compress(smf_ctx* ctx, const uint8_t* input, size_t n, uint8_t* framed, size_t* framed_length, int mode) {
@@ -363,21 +395,16 @@ sm_status smf_compress(smf_ctx* ctx, const uint8_t* input, size_t n, uint8_t* fr
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   hipStream_t s = ctx->stream;
-  SMF_CHECK(ctx->io_in.ensure(n));
-  SMF_CHECK(ctx->io_out.ensure(need));
-  if (n) SMF_CHECK(hipMemcpyAsync(ctx->io_in.p, input, n, hipMemcpyHostToDevice, s));
-  uint64_t* d_len = (uint64_t*)((uint8_t*)ctx->res.p + 64);
-  int32_t* d_st = (int32_t*)((uint8_t*)ctx->res.p + 72);
-  SMF_PASS(smf_compress_device(ctx, (const uint8_t*)ctx->io_in.p, n, (uint8_t*)ctx->io_out.p, need, d_len, d_st, mode, s));
-  struct {
-    uint64_t len;
-    int32_t st, pad;
-  } r;
-  SMF_CHECK(hipMemcpyAsync(&r, d_len, 16, hipMemcpyDeviceToHost, s));
-  SMF_CHECK(hipStreamSynchronize(s));
-  if (r.st != SM_OK) return r.st;
+  SM_CHECK(ctx->io_in.ensure(n));
+  SM_CHECK(ctx->io_out.ensure(need));
+  if (n) SM_CHECK(hipMemcpyAsync(ctx->io_in.p, input, n, hipMemcpyHostToDevice, s));
+  LenStatus* d = &((Results*)ctx->res.p)->io;
+  SM_PASS(smf_compress_device(ctx, (const uint8_t*)ctx->io_in.p, n, (uint8_t*)ctx->io_out.p, need, &d->len, &d->st, mode,
+                              s));
+  LenStatus r;
+  SM_PASS(read_back(d, r, s));
   if (r.len > need) return SM_ERR_DEVICE;
-  SMF_CHECK(hipMemcpy(framed, ctx->io_out.p, r.len, hipMemcpyDeviceToHost));
+  SM_CHECK(hipMemcpy(framed, ctx->io_out.p, r.len, hipMemcpyDeviceToHost));
   *framed_length = (size_t)r.len;
   return SM_OK;
 }
@@ -385,7 +412,7 @@ sm_status smf_compress(smf_ctx* ctx, const uint8_t* input, size_t n, uint8_t* fr
 // host index, upload, decode; output == null validates only (the decode goes to scratch)
 static sm_status uncompress_host(smf_ctx* ctx, const uint8_t* framed, size_t n, uint8_t* output, size_t* length) {
   smf_summary sum;
-  SMF_PASS(smf_index(framed, n, nullptr, 0, &sum));
+  SM_PASS(smf_index(framed, n, nullptr, 0, &sum));
   if (length && sum.total_length > *length) {
     *length = (size_t)sum.total_length;
     return SM_BUFFER_TOO_SMALL;
@@ -395,35 +422,22 @@ static sm_status uncompress_host(smf_ctx* ctx, const uint8_t* framed, size_t n, 
   std::vector<uint64_t> pay_off(nc);
   std::vector<uint32_t> pay_len(nc), crc(nc), ulen(nc);
   const smf_chunks h{type.data(), pay_off.data(), pay_len.data(), crc.data(), ulen.data()};
-  SMF_PASS(smf_index(framed, n, &h, nc, &sum));
+  SM_PASS(smf_index(framed, n, &h, nc, &sum));
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   hipStream_t s = ctx->stream;
-  smf_chunks d;
-  int32_t* chunk_status = nullptr;
-  SMF_PASS(index_scratch(ctx, nc, d, chunk_status));
-  SMF_CHECK(ctx->io_in.ensure(n));
-  SMF_CHECK(ctx->io_out.ensure((size_t)sum.total_length));
-  SMF_CHECK(hipMemcpyAsync(ctx->io_in.p, framed, n, hipMemcpyHostToDevice, s));
-  if (nc) {
-    SMF_CHECK(hipMemcpyAsync(d.type, h.type, nc, hipMemcpyHostToDevice, s));
-    SMF_CHECK(hipMemcpyAsync(d.pay_off, h.pay_off, 8 * (size_t)nc, hipMemcpyHostToDevice, s));
-    SMF_CHECK(hipMemcpyAsync(d.pay_len, h.pay_len, 4 * (size_t)nc, hipMemcpyHostToDevice, s));
-    SMF_CHECK(hipMemcpyAsync(d.crc, h.crc, 4 * (size_t)nc, hipMemcpyHostToDevice, s));
-    SMF_CHECK(hipMemcpyAsync(d.ulen, h.ulen, 4 * (size_t)nc, hipMemcpyHostToDevice, s));
-  }
-  uint64_t* d_len = (uint64_t*)((uint8_t*)ctx->res.p + 64);
-  int32_t* d_st = (int32_t*)((uint8_t*)ctx->res.p + 72);
-  SMF_PASS(smf_uncompress_chunks_device(ctx, (const uint8_t*)ctx->io_in.p, &d, nc, (uint8_t*)ctx->io_out.p,
-                                        sum.total_length, chunk_status, d_len, d_st, s));
-  struct {
-    uint64_t len;
-    int32_t st, pad;
-  } r;
-  SMF_CHECK(hipMemcpyAsync(&r, d_len, 16, hipMemcpyDeviceToHost, s));
-  SMF_CHECK(hipStreamSynchronize(s));
-  if (r.st != SM_OK) return r.st;
-  if (output && r.len) SMF_CHECK(hipMemcpy(output, ctx->io_out.p, r.len, hipMemcpyDeviceToHost));
+  IndexMeta ix;
+  SM_PASS(index_scratch(ctx, nc, ix));
+  SM_CHECK(ctx->io_in.ensure(n));
+  SM_CHECK(ctx->io_out.ensure((size_t)sum.total_length));
+  SM_CHECK(hipMemcpyAsync(ctx->io_in.p, framed, n, hipMemcpyHostToDevice, s));
+  SM_PASS(upload_chunks(ix.ch, h, 0, nc, s));
+  LenStatus* d = &((Results*)ctx->res.p)->io;
+  SM_PASS(smf_uncompress_chunks_device(ctx, (const uint8_t*)ctx->io_in.p, &ix.ch, nc, (uint8_t*)ctx->io_out.p,
+                                       sum.total_length, ix.chunk_status, &d->len, &d->st, s));
+  LenStatus r;
+  SM_PASS(read_back(d, r, s));
+  if (output && r.len) SM_CHECK(hipMemcpy(output, ctx->io_out.p, r.len, hipMemcpyDeviceToHost));
   if (length) *length = (size_t)r.len;
   return SM_OK;
 }
@@ -442,7 +456,7 @@ sm_status smf_uncompress_range(smf_ctx* ctx, const uint8_t* framed, size_t n, ui
                                uint8_t* output, size_t* out_len) {
   if (!ctx || !out_len || (n && !framed) || (*out_len && !output)) return SM_ERR_ARGUMENT;
   smf_summary sum;
-  SMF_PASS(smf_index(framed, n, nullptr, 0, &sum));
+  SM_PASS(smf_index(framed, n, nullptr, 0, &sum));
   if (lo + len < lo || lo + len > sum.total_length) return SM_ERR_ARGUMENT;
   if (len > *out_len) {
     *out_len = (size_t)len;
@@ -455,8 +469,8 @@ sm_status smf_uncompress_range(smf_ctx* ctx, const uint8_t* framed, size_t n, ui
   std::vector<uint64_t> pay_off(nc), chunk_off((size_t)nc + 1);
   std::vector<uint32_t> pay_len(nc), crc(nc), ulen(nc);
   const smf_chunks h{type.data(), pay_off.data(), pay_len.data(), crc.data(), ulen.data()};
-  SMF_PASS(smf_index(framed, n, &h, nc, &sum));
-  SMF_PASS(smf_chunk_offsets(ulen.data(), nc, chunk_off.data()));
+  SM_PASS(smf_index(framed, n, &h, nc, &sum));
+  SM_PASS(smf_chunk_offsets(ulen.data(), nc, chunk_off.data()));
   // the touched chunks [f, f + k), their bytes in the stream, and the index slice rebased to them
   const smf::RangeChunks rc = smf::range_chunks(chunk_off.data(), nc, lo, len);
   if (rc.status != SM_OK || rc.count == 0) return SM_ERR_ARGUMENT;
@@ -467,38 +481,25 @@ sm_status smf_uncompress_range(smf_ctx* ctx, const uint8_t* framed, size_t n, ui
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   hipStream_t s = ctx->stream;
-  smf_chunks d;
-  int32_t* chunk_status = nullptr;
-  SMF_PASS(index_scratch(ctx, k, d, chunk_status));
-  SMF_CHECK(ctx->roff.ensure(8 * ((size_t)k + 1)));
-  SMF_CHECK(ctx->io_in.ensure((size_t)span));
-  SMF_CHECK(ctx->io_out.ensure((size_t)len));
-  SMF_CHECK(hipMemcpyAsync(ctx->io_in.p, framed + span0, (size_t)span, hipMemcpyHostToDevice, s));
-  SMF_CHECK(hipMemcpyAsync(d.type, h.type + f, k, hipMemcpyHostToDevice, s));
-  SMF_CHECK(hipMemcpyAsync(d.pay_off, h.pay_off + f, 8 * (size_t)k, hipMemcpyHostToDevice, s));
-  SMF_CHECK(hipMemcpyAsync(d.pay_len, h.pay_len + f, 4 * (size_t)k, hipMemcpyHostToDevice, s));
-  SMF_CHECK(hipMemcpyAsync(d.crc, h.crc + f, 4 * (size_t)k, hipMemcpyHostToDevice, s));
-  SMF_CHECK(hipMemcpyAsync(d.ulen, h.ulen + f, 4 * (size_t)k, hipMemcpyHostToDevice, s));
-  SMF_CHECK(hipMemcpyAsync(ctx->roff.p, chunk_off.data() + f, 8 * ((size_t)k + 1), hipMemcpyHostToDevice, s));
-  // the range's words in ctx->res: lo, len, out_off | out_len, status
-  struct {
-    uint64_t lo, len, out_off;
-  } arg{lo - base, len, 0};
-  struct {
-    uint64_t len;
-    int32_t st, pad;
-  } r;
-  uint64_t* d_arg = (uint64_t*)((uint8_t*)ctx->res.p + 128);
-  uint64_t* d_len = (uint64_t*)((uint8_t*)ctx->res.p + 160);
-  int32_t* d_st = (int32_t*)((uint8_t*)ctx->res.p + 168);
-  SMF_CHECK(hipMemcpyAsync(d_arg, &arg, sizeof(arg), hipMemcpyHostToDevice, s));
-  SMF_PASS(smf_uncompress_ranges_device(ctx, (const uint8_t*)ctx->io_in.p, span, &d, (const uint64_t*)ctx->roff.p, k,
-                                        d_arg, d_arg + 1, 1, k, (uint8_t*)ctx->io_out.p, d_arg + 2, d_len, d_st, s));
-  SMF_CHECK(hipMemcpyAsync(&r, d_len, 16, hipMemcpyDeviceToHost, s));
-  SMF_CHECK(hipStreamSynchronize(s));  // (also: the pageable uploads above have left their host buffers)
-  if (r.st != SM_OK) return r.st;
+  IndexMeta ix;
+  SM_PASS(index_scratch(ctx, k, ix));
+  SM_CHECK(ctx->roff.ensure(8 * ((size_t)k + 1)));
+  SM_CHECK(ctx->io_in.ensure((size_t)span));
+  SM_CHECK(ctx->io_out.ensure((size_t)len));
+  SM_CHECK(hipMemcpyAsync(ctx->io_in.p, framed + span0, (size_t)span, hipMemcpyHostToDevice, s));
+  SM_PASS(upload_chunks(ix.ch, h, f, k, s));
+  SM_CHECK(hipMemcpyAsync(ctx->roff.p, chunk_off.data() + f, 8 * ((size_t)k + 1), hipMemcpyHostToDevice, s));
+  Results* res = (Results*)ctx->res.p;
+  const uint64_t arg[3] = {lo - base, len, 0};  // lo, len, out_off
+  uint64_t* d_arg = res->range;
+  LenStatus* d = &res->range_out;
+  SM_CHECK(hipMemcpyAsync(d_arg, arg, sizeof(arg), hipMemcpyHostToDevice, s));
+  SM_PASS(smf_uncompress_ranges_device(ctx, (const uint8_t*)ctx->io_in.p, span, &ix.ch, (const uint64_t*)ctx->roff.p, k,
+                                       d_arg, d_arg + 1, 1, k, (uint8_t*)ctx->io_out.p, d_arg + 2, &d->len, &d->st, s));
+  LenStatus r;
+  SM_PASS(read_back(d, r, s));  // (also: the pageable uploads above have left their host buffers)
   if (r.len != len) return SM_ERR_DEVICE;
-  SMF_CHECK(hipMemcpy(output, ctx->io_out.p, (size_t)len, hipMemcpyDeviceToHost));
+  SM_CHECK(hipMemcpy(output, ctx->io_out.p, (size_t)len, hipMemcpyDeviceToHost));
   *out_len = (size_t)len;
   return SM_OK;
 }

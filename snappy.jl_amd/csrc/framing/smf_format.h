@@ -6,12 +6,7 @@
 #include <stdint.h>
 
 #include "../../../include/snappy_mi355x_framing.h"
-
-#if defined(__HIPCC__)
-#define SMF_HD __host__ __device__
-#else
-#define SMF_HD
-#endif
+#include "../common/smc_layout.h"
 
 namespace smf {
 
@@ -20,7 +15,7 @@ constexpr uint32_t kBlock = 65536;       // uncompressed bytes per data chunk, a
 // the bytes of a chunk a walk step looks at: header (4), CRC (4), the payload's varint (<= 5)
 constexpr uint32_t kHeadBytes = 13;
 
-SMF_HD inline uint32_t mask(uint32_t crc) { return ((crc >> 15) | (crc << 17)) + 0xa282ead8u; }
+SMC_HD inline uint32_t mask(uint32_t crc) { return ((crc >> 15) | (crc << 17)) + 0xa282ead8u; }
 
 struct Walk {
   uint64_t total = 0;    // declared uncompressed bytes so far
@@ -39,7 +34,7 @@ struct Chunk {
 
 // One chunk at pos of an n-byte stream; h[0, have) = its first min(kHeadBytes, n - pos) bytes.
 // false: the walk is over -- at the end of the stream, or at an error (w.status).
-SMF_HD inline bool walk_step(Walk& w, const uint8_t* h, uint32_t have, uint64_t pos, uint64_t n, Chunk& c) {
+SMC_HD inline bool walk_step(Walk& w, const uint8_t* h, uint32_t have, uint64_t pos, uint64_t n, Chunk& c) {
   c.data = false;
   if (pos >= n) {
     if (w.first) w.status = SMF_ERR_NO_IDENTIFIER;  // (an empty stream)
@@ -136,7 +131,7 @@ SMF_HD inline bool walk_step(Walk& w, const uint8_t* h, uint32_t have, uint64_t 
 }
 
 // the walk's final status: its first structural error, else whether the entries fitted
-SMF_HD inline int32_t walk_status(const Walk& w, bool stored, uint32_t max_chunks) {
+SMC_HD inline int32_t walk_status(const Walk& w, bool stored, uint32_t max_chunks) {
   if (w.status != SM_OK) return w.status;
   return stored && w.nchunks > max_chunks ? SM_BUFFER_TOO_SMALL : SM_OK;
 }
@@ -156,7 +151,7 @@ struct CrcLut {
   uint32_t xpow2[32];  // x^(128 * 2^k) mod P: longer blocks, by square and multiply
 };
 
-SMF_HD inline uint32_t gf_mul(uint32_t a, uint32_t b) {
+SMC_HD inline uint32_t gf_mul(uint32_t a, uint32_t b) {
   uint32_t p = 0;
   for (uint32_t i = 0; i < 32; ++i) {
     p ^= (a & (0x80000000u >> i)) ? b : 0u;
@@ -166,7 +161,7 @@ SMF_HD inline uint32_t gf_mul(uint32_t a, uint32_t b) {
 }
 
 // x^(128 g) mod P
-SMF_HD inline uint32_t gf_xpow(const CrcLut* T, uint32_t g) {
+SMC_HD inline uint32_t gf_xpow(const CrcLut* T, uint32_t g) {
   if (g <= kCrcPow) return T->xpow[g];
   uint32_t r = 0x80000000u;
   for (uint32_t k = 0; g; ++k, g >>= 1)
@@ -176,7 +171,7 @@ SMF_HD inline uint32_t gf_xpow(const CrcLut* T, uint32_t g) {
 
 // one granule (16 bytes, little-endian dwords w[0..3]) behind register s, which is
 // kCrcThreads granules old
-SMF_HD inline uint32_t crc_granule(const uint32_t* tab, uint32_t s, const uint32_t* w) {
+SMC_HD inline uint32_t crc_granule(const uint32_t* tab, uint32_t s, const uint32_t* w) {
   uint32_t r = tab[16 * 256 + (s & 0xff)] ^ tab[17 * 256 + ((s >> 8) & 0xff)] ^ tab[18 * 256 + ((s >> 16) & 0xff)] ^
                tab[19 * 256 + (s >> 24)];
   for (uint32_t k = 0; k < 4; ++k) {

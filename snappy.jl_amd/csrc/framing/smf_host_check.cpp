@@ -2,13 +2,15 @@
 // -fsanitize=address,undefined by `make host_check`.  Every buffer is a heap block of exactly the
 // stream's size, so a walker that reads past a cut stream trips the sanitizer.  It also runs the
 // CRC kernel's arithmetic (k_crc32c: the tables, the per-lane granule steps, the x^(128 t)
-// multipliers) lane by lane on the CPU against the bytewise CRC.
+// multipliers) lane by lane on the CPU against the bytewise CRC, and the kernels' shared byte
+// mover (smc::copy_bytes) thread by thread.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "../common/smc_device.h"
 #include "smf_format.h"
 #include "smf_range.h"
 
@@ -323,6 +325,40 @@ void range_cases() {
           }
 }
 
+// ---- the shared byte mover (../common/smc_device.h), every tid one after another ----------------
+// The source is a heap block that ends exactly at src + n, so a read past the end trips the
+// sanitizer; the function's own assert (host build) holds every 16-byte load to an aligned address
+// not below src.  The destination lies between canary bytes.
+void copy_bytes_cases() {
+  std::vector<uint32_t> ns;
+  for (uint32_t n = 0; n <= 48; ++n) ns.push_back(n);
+  for (uint32_t n : {63u, 64u, 65u, 255u, 256u, 257u, 4095u, 4096u, 65535u, 65536u}) ns.push_back(n);
+  const uint32_t kCanary = 32;
+  for (uint32_t n : ns)
+    for (uint32_t sa = 0; sa < 16; ++sa) {
+      void* block = nullptr;
+      if (posix_memalign(&block, 16, sa + n ? sa + n : 1) != 0) std::abort();
+      uint8_t* const src = (uint8_t*)block + sa;
+      for (uint32_t i = 0; i < n; ++i) src[i] = (uint8_t)(i * 131u + 7u * sa + n);
+      std::vector<uint8_t> room(16 + kCanary + 16 + n + kCanary);
+      uint8_t* const base = room.data() + ((16 - ((uintptr_t)room.data() & 15)) & 15);
+      for (uint32_t da = 0; da < 16; ++da)
+        for (uint32_t nthreads : {1u, 64u, 256u, 1024u}) {
+          std::memset(room.data(), 0xa5, room.size());
+          uint8_t* const dst = base + kCanary + da;
+          for (uint32_t tid = 0; tid < nthreads; ++tid) smc::copy_bytes(src, n, dst, tid, nthreads);
+          bool ok = std::memcmp(dst, src, n) == 0;
+          for (const uint8_t* p = room.data(); p < room.data() + room.size(); ++p)
+            if ((p < dst || p >= dst + n) && *p != 0xa5) ok = false;
+          if (!ok) {
+            std::printf("FAIL copy_bytes: n %u, source align %u, destination align %u, %u threads\n", n, sa, da, nthreads);
+            ++failures;
+          }
+        }
+      std::free(block);
+    }
+}
+
 }  // namespace
 
 int main() {
@@ -427,6 +463,7 @@ int main() {
   }
   expect(smf::host_message(SMF_ERR_CRC) != nullptr && smf::host_message(SM_OK) == nullptr, "messages");
   range_cases();
+  copy_bytes_cases();
 
   if (failures) {
     std::printf("%d failure(s)\n", failures);

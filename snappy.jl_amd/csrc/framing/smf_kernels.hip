@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../common/smc_device.h"
 #include "smf_format.h"
 #include "smf_internal.h"
 
@@ -15,47 +16,14 @@ namespace smf {
 
 namespace {
 
-constexpr uint32_t kWave = 64;
+using smc::block_scan;
+using smc::copy_bytes;
+using smc::kWave;
+
 constexpr uint32_t kOutLenError = SM_OUT_LEN_ERROR;
 constexpr uint8_t kTypeNone = 0xff;  // k_frame_scan: the compressor left an error mark, nothing is packed
 
 __device__ inline uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
-// n bytes from src to dst, both at any alignment, by `nthreads` threads of which this is `tid`:
-// aligned 16-byte loads of the granules src wholly covers, bytes for the partial granules at both
-// ends (no byte outside [src, src + n) is read), stores at dst's alignment.
-__device__ inline void copy_bytes(const uint8_t* __restrict__ src, uint32_t n, uint8_t* __restrict__ dst, uint32_t tid,
-                                  uint32_t nthreads) {
-  const uint32_t head = min(n, (16u - (uint32_t)((uintptr_t)src & 15)) & 15u);
-  const uint32_t G = (n - head) / 16;
-  const uint4* g = reinterpret_cast<const uint4*>(src + head);
-  for (uint32_t u = tid; u < G; u += nthreads) {
-    const uint4 v = g[u];
-    __builtin_memcpy(dst + head + 16 * u, &v, 16);
-  }
-  const uint32_t edge = n - 16 * G;  // head bytes, then the tail's
-  for (uint32_t i = tid; i < edge; i += nthreads) {
-    const uint32_t j = i < head ? i : 16 * G + i;
-    dst[j] = src[j];
-  }
-}
-
-// exclusive scan of v over the workgroup's 256 threads (sh: 4 u64); total = the sum
-__device__ inline uint64_t block_scan(uint64_t v, uint64_t* sh, uint64_t& total) {
-  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint64_t inc = v;
-  for (uint32_t d = 1; d < kWave; d <<= 1) {
-    const uint64_t o = __shfl_up(inc, d, kWave);
-    if (lane >= d) inc += o;
-  }
-  __syncthreads();  // (sh is free again)
-  if (lane == kWave - 1) sh[w] = inc;
-  __syncthreads();
-  uint64_t pre = 0;
-  for (uint32_t k = 0; k < w; ++k) pre += sh[k];
-  total = sh[0] + sh[1] + sh[2] + sh[3];
-  return pre + inc - v;
-}
 
 }  // namespace
 

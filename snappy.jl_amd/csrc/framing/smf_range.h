@@ -20,7 +20,7 @@ constexpr uint64_t kEdgePitch = kBlock;            // an edge slot: one whole ch
 // How many of off[0, cnt) are <= v, for a non-decreasing off; any other array gives some value in
 // [0, cnt].  At most 32 steps, every read inside off[0, cnt).
 template <typename T>
-SMF_HD inline uint32_t upper_bound(const T* off, uint32_t cnt, T v) {
+SMC_HD inline uint32_t upper_bound(const T* off, uint32_t cnt, T v) {
   uint32_t lo = 0, hi = cnt;
   while (lo < hi) {
     const uint32_t mid = lo + (hi - lo) / 2;
@@ -39,7 +39,7 @@ struct RangeChunks {
 // lo + len - 1.  Taking the upper bound skips empty chunks at both ends (of equal offsets, the last
 // one is found, and that one is not empty); empty chunks in between keep a slot and are passed over.
 // chunk_off has nchunks + 1 entries.  first + count <= nchunks whatever chunk_off holds.
-SMF_HD inline RangeChunks range_chunks(const uint64_t* chunk_off, uint32_t nchunks, uint64_t lo, uint64_t len) {
+SMC_HD inline RangeChunks range_chunks(const uint64_t* chunk_off, uint32_t nchunks, uint64_t lo, uint64_t len) {
   RangeChunks r{0, 0, SM_OK};
   if (len == 0) return r;
   if (lo + len < lo || lo + len > chunk_off[nchunks] || nchunks == 0) {
@@ -60,7 +60,7 @@ SMF_HD inline RangeChunks range_chunks(const uint64_t* chunk_off, uint32_t nchun
 // The checks of a touched entry: chunk c of an n-byte stream, off0 / off1 = chunk_off[c], [c + 1].
 // SM_OK means: the payload lies inside the stream, the chunk's bytes are [off0, off0 + ulen)
 // without overflow, and ulen fits an edge slot.
-SMF_HD inline int32_t entry_check(uint32_t type, uint64_t pay_off, uint32_t pay_len, uint32_t ulen, uint64_t off0,
+SMC_HD inline int32_t entry_check(uint32_t type, uint64_t pay_off, uint32_t pay_len, uint32_t ulen, uint64_t off0,
                                   uint64_t off1, uint64_t n) {
   if (type > SMF_CHUNK_UNCOMPRESSED) return SM_ERR_ARGUMENT;
   if (ulen > kBlock) return SM_ERR_ARGUMENT;
@@ -82,7 +82,7 @@ struct Place {
 // to.  Wholly inside the range: direct.  Else it has to be the range's first or last chunk and to
 // meet the range -- with a consistent index every other chunk lies inside -- so a range never
 // needs more than its two edge slots.
-SMF_HD inline Place chunk_place(uint64_t a, uint32_t u, uint64_t lo, uint64_t len, bool is_first, bool is_last) {
+SMC_HD inline Place chunk_place(uint64_t a, uint32_t u, uint64_t lo, uint64_t len, bool is_first, bool is_last) {
   Place p{SM_OK, 0, 0, 0, 0};
   if (a >= lo && a - lo <= len && len - (a - lo) >= u) {
     p.dst = a - lo;
@@ -103,7 +103,7 @@ SMF_HD inline Place chunk_place(uint64_t a, uint32_t u, uint64_t lo, uint64_t le
 
 // Slot k of a range's `count`: chunk first + k.  skip: an empty chunk in between, not touched.
 // (The searches never end on an empty chunk of a consistent index: there it fails the range.)
-SMF_HD inline Place slot_place(const smf_chunks& ch, const uint64_t* chunk_off, uint64_t n, uint32_t c, uint64_t lo,
+SMC_HD inline Place slot_place(const smf_chunks& ch, const uint64_t* chunk_off, uint64_t n, uint32_t c, uint64_t lo,
                                uint64_t len, bool is_first, bool is_last, bool& skip) {
   const uint32_t u = ch.ulen[c];
   skip = u == 0 && !(is_first || is_last);
@@ -118,18 +118,7 @@ SMF_HD inline Place slot_place(const smf_chunks& ch, const uint64_t* chunk_off, 
   return chunk_place(chunk_off[c], u, lo, len, is_first, is_last);
 }
 
-// ---- scratch ---------------------------------------------------------------------------------
-// consecutive arrays of one buffer, each rounded up to 16 bytes (an integer base: null measures)
-struct RangeCarve {
-  uintptr_t p;
-  template <typename T>
-  T* take(size_t n) {
-    T* r = reinterpret_cast<T*>(p);
-    p += (n * sizeof(T) + 15) / 16 * 16;
-    return r;
-  }
-};
-
+// ---- scratch (smc::Carve: a null base measures) ------------------------------------------------
 struct RangeHeader {  // the plan's words for the kernels behind it
   uint32_t total;     // slots in use
   uint32_t over;      // the ranges touch more than max_range_chunks chunks: nothing is decoded
@@ -149,7 +138,7 @@ struct RangeScratch {
 };
 
 inline RangeScratch carve_range(uint8_t* buf, size_t nranges, size_t m) {
-  RangeCarve c{reinterpret_cast<uintptr_t>(buf)};
+  smc::Carve c{reinterpret_cast<uintptr_t>(buf)};
   RangeScratch s;
   s.hdr = c.take<RangeHeader>(1);
   s.in_off = c.take<uint64_t>(m);

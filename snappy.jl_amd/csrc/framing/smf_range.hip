@@ -1,12 +1,12 @@
 // smf_range.hip -- the seek index and the ranged decode of the framing library: gfx950 kernels and
 // their launchers (smf_range.h).  Plumbing around the raw codec's batched decoder and k_crc32c, as
 // smf_kernels.hip's decode is; the decisions are the shared rules of smf_range.h, taken per range
-// and per slot on the device, so a call needs no host synchronisation.  block_scan and copy_bytes
-// are this file's own copies of smf_kernels.hip's: the existing entry points' objects stay as
-// they were.
+// and per slot on the device, so a call needs no host synchronisation.  block_scan, copy_bytes
+// and sat32 are the shared ones of ../common/smc_device.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../common/smc_device.h"
 #include "smf_format.h"
 #include "smf_internal.h"
 #include "smf_range.h"
@@ -15,49 +15,12 @@ namespace smf {
 
 namespace {
 
-constexpr uint32_t kWave = 64;
-
-// n bytes from src to dst, both at any alignment, by `nthreads` threads of which this is `tid`:
-// aligned 16-byte loads of the granules src wholly covers, bytes for the partial granules at both
-// ends (no byte outside [src, src + n) is read), stores at dst's alignment (none outside
-// [dst, dst + n)).
-__device__ inline void copy_bytes(const uint8_t* __restrict__ src, uint32_t n, uint8_t* __restrict__ dst, uint32_t tid,
-                                  uint32_t nthreads) {
-  const uint32_t head = min(n, (16u - (uint32_t)((uintptr_t)src & 15)) & 15u);
-  const uint32_t G = (n - head) / 16;
-  const uint4* g = reinterpret_cast<const uint4*>(src + head);
-  for (uint32_t u = tid; u < G; u += nthreads) {
-    const uint4 v = g[u];
-    __builtin_memcpy(dst + head + 16 * u, &v, 16);
-  }
-  const uint32_t edge = n - 16 * G;  // head bytes, then the tail's
-  for (uint32_t i = tid; i < edge; i += nthreads) {
-    const uint32_t j = i < head ? i : 16 * G + i;
-    dst[j] = src[j];
-  }
-}
-
-// exclusive scan of v over the workgroup's 256 threads (sh: 4 u64); total = the sum
-__device__ inline uint64_t block_scan(uint64_t v, uint64_t* sh, uint64_t& total) {
-  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint64_t inc = v;
-  for (uint32_t d = 1; d < kWave; d <<= 1) {
-    const uint64_t o = __shfl_up(inc, d, kWave);
-    if (lane >= d) inc += o;
-  }
-  __syncthreads();  // (sh is free again)
-  if (lane == kWave - 1) sh[w] = inc;
-  __syncthreads();
-  uint64_t pre = 0;
-  for (uint32_t k = 0; k < w; ++k) pre += sh[k];
-  total = sh[0] + sh[1] + sh[2] + sh[3];
-  return pre + inc - v;
-}
+using smc::block_scan;
+using smc::copy_bytes;
+using smc::sat32;
 
 // base + off where off may stand for a place before base (the offsets of k_range_slots)
 __device__ inline uint8_t* at(uint8_t* base, uint64_t off) { return (uint8_t*)((uintptr_t)base + off); }
-
-__device__ inline uint32_t sat32(uint64_t v) { return v > 0xffffffffull ? 0xffffffffu : (uint32_t)v; }
 
 }  // namespace
 

@@ -9,6 +9,7 @@
 #include <new>
 #include <vector>
 
+#include "../common/smc_hip_host.h"
 #include "smm_plan.h"
 
 #ifndef SMM_VERSION_STR
@@ -16,38 +17,6 @@
 #endif
 
 namespace {
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t n) {  // (growing frees the old buffer: hipFree waits for the device)
-    if (n <= cap) return hipSuccess;
-    release();
-    const size_t want = n < 4096 ? 4096 : n;
-    const hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    else p = nullptr;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-bool valid_mode(int m) { return m == SM_MODE_REFERENCE || m == SM_MODE_FAST || m == SM_MODE_FAST_DENSE; }
 
 // any total_len above 16,384 gives the fragment call the 16,384-entry table (src/Snappy.jl:27):
 // the table of every fragment of a stream longer than 64 KiB
@@ -65,16 +34,6 @@ struct smm_ctx {
   bool called = false;           // an uncompress call has been made (smm_ctx_last_indexed)
   std::mutex mu;                 // serialises the host-buffer entry points
 };
-
-#define SMM_CHECK(x)                              \
-  do {                                            \
-    if ((x) != hipSuccess) return SM_ERR_DEVICE;  \
-  } while (0)
-#define SMM_PASS(x)                \
-  do {                             \
-    const sm_status st_ = (x);     \
-    if (st_ != SM_OK) return st_;  \
-  } while (0)
 
 extern "C" {
 
@@ -135,23 +94,23 @@ sm_status smm_compress_device(smm_ctx* ctx, const uint8_t* d_in, const uint64_t*
   hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(ctx->device);
   if (nstreams == 0) {
-    if (d_frag_first) SMM_CHECK(hipMemsetAsync(d_frag_first, 0, 4, s));
+    if (d_frag_first) SM_CHECK(hipMemsetAsync(d_frag_first, 0, 4, s));
     return SM_OK;
   }
   if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len || !d_status) return SM_ERR_ARGUMENT;
   const uint32_t n = nstreams, m = max_fragments;
-  SMM_CHECK(ctx->meta.ensure(smm::compress_meta_bytes(n, m)));
-  SMM_CHECK(ctx->slots.ensure((size_t)m * smm::kSlotPitch));
+  SM_CHECK(ctx->meta.ensure(smm::compress_meta_bytes(n, m)));
+  SM_CHECK(ctx->slots.ensure((size_t)m * smm::kSlotPitch));
   smm::CompressPlan p{d_in,   d_in_off,     d_in_len,   n, m, d_out, d_out_off, d_out_len,
                       d_status, d_frag_first, d_frag_pos, (const uint8_t*)ctx->slots.p,
                       smm::carve_compress((uint8_t*)ctx->meta.p, n, m), (smm::Header*)ctx->hdr.p};
-  SMM_CHECK(smm::launch_compress_plan(p, s));
-  SMM_PASS(sm_compress_batch_device(ctx->sm, d_in, d_in_off, p.s.s_in_len, n, d_out, p.s.s_out_off, p.s.s_comp_len, mode,
-                                    stream));
+  SM_CHECK(smm::launch_compress_plan(p, s));
+  SM_PASS(sm_compress_batch_device(ctx->sm, d_in, d_in_off, p.s.s_in_len, n, d_out, p.s.s_out_off, p.s.s_comp_len, mode,
+                                   stream));
   if (m)
-    SMM_PASS(sm_compress_fragments_device(ctx->sm, d_in, p.s.f_in_off, p.s.f_in_len, m, (uint8_t*)ctx->slots.p,
-                                          p.s.f_slot_off, p.s.f_comp_len, kLongTotal, mode, stream));
-  SMM_CHECK(smm::launch_pack(p, s));
+    SM_PASS(sm_compress_fragments_device(ctx->sm, d_in, p.s.f_in_off, p.s.f_in_len, m, (uint8_t*)ctx->slots.p,
+                                         p.s.f_slot_off, p.s.f_comp_len, kLongTotal, mode, stream));
+  SM_CHECK(smm::launch_pack(p, s));
   return SM_OK;
 }
 
@@ -168,7 +127,7 @@ sm_status smm_uncompress_device(smm_ctx* ctx, const uint8_t* d_in, const uint64_
   ctx->called = true;
   smm::Header* hdr = (smm::Header*)ctx->hdr.p;
   if (nstreams == 0 || !d_frag_first) {
-    SMM_CHECK(hipMemsetAsync(&hdr->indexed, 0, 4, s));
+    SM_CHECK(hipMemsetAsync(&hdr->indexed, 0, 4, s));
     if (nstreams == 0) return SM_OK;
     return sm_uncompress_batch_device(ctx->sm, d_in, d_in_off, d_in_len, nstreams, d_out, d_out_off, d_out_cap, d_out_len,
                                       d_status, stream);
@@ -176,34 +135,34 @@ sm_status smm_uncompress_device(smm_ctx* ctx, const uint8_t* d_in, const uint64_
   if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status)
     return SM_ERR_ARGUMENT;
   const uint32_t n = nstreams, m = max_fragments;
-  SMM_CHECK(ctx->meta.ensure(smm::decode_meta_bytes(n, m)));
+  SM_CHECK(ctx->meta.ensure(smm::decode_meta_bytes(n, m)));
   smm::DecodePlan p{d_in,     d_in_off, d_in_len,     n,          m, d_out_off, d_out_cap, d_out_len,
                     d_status, d_frag_first, d_frag_pos, smm::carve_decode((uint8_t*)ctx->meta.p, n, m), hdr};
-  SMM_CHECK(smm::launch_decode_plan(p, s));
+  SM_CHECK(smm::launch_decode_plan(p, s));
   if (m)
-    SMM_PASS(sm_uncompress_fragments_device(ctx->sm, d_in, p.s.f_in_off, p.s.f_in_len, m, d_out, p.s.f_out_off, p.s.f_len,
-                                            p.s.f_out_len, p.s.f_status, stream));
-  SMM_CHECK(smm::launch_reduce(p, s));
-  SMM_PASS(sm_uncompress_batch_device(ctx->sm, d_in, d_in_off, p.s.fb_in_len, n, d_out, d_out_off, p.s.fb_cap, d_out_len,
-                                      d_status, stream));
-  SMM_CHECK(smm::launch_merge(p, s));
+    SM_PASS(sm_uncompress_fragments_device(ctx->sm, d_in, p.s.f_in_off, p.s.f_in_len, m, d_out, p.s.f_out_off, p.s.f_len,
+                                           p.s.f_out_len, p.s.f_status, stream));
+  SM_CHECK(smm::launch_reduce(p, s));
+  SM_PASS(sm_uncompress_batch_device(ctx->sm, d_in, d_in_off, p.s.fb_in_len, n, d_out, d_out_off, p.s.fb_cap, d_out_len,
+                                     d_status, stream));
+  SM_CHECK(smm::launch_merge(p, s));
   return SM_OK;
 }
 
 // ---- host buffers ------------------------------------------------------------------------------
 
-namespace {
+namespace {  // (its functions are static: inside extern "C" the unnamed namespace alone still exports them)
 
 // the device copies of a host call's per-stream arrays, in ctx->io_meta
 struct HostArrays {
   uint64_t *in_off, *out_off;
   uint32_t *in_len, *cap, *out_len, *first, *pos;
   int32_t* status;
+  uintptr_t end;
 };
-sm_status host_arrays(smm_ctx* ctx, size_t n, size_t entries, HostArrays& a) {
-  const size_t bytes = 2 * (8 * n + 16) + 4 * (4 * n + 16) + (4 * (n + 1) + 16) + (4 * entries + 16);
-  SMM_CHECK(ctx->io_meta.ensure(bytes));
-  smm::Carve c{reinterpret_cast<uintptr_t>(ctx->io_meta.p)};
+static HostArrays carve_host(uintptr_t base, size_t n, size_t entries) {
+  smm::Carve c{base};
+  HostArrays a;
   a.in_off = c.take<uint64_t>(n);
   a.out_off = c.take<uint64_t>(n);
   a.in_len = c.take<uint32_t>(n);
@@ -212,6 +171,39 @@ sm_status host_arrays(smm_ctx* ctx, size_t n, size_t entries, HostArrays& a) {
   a.status = c.take<int32_t>(n);
   a.first = c.take<uint32_t>(n + 1);
   a.pos = c.take<uint32_t>(entries);
+  a.end = c.p;
+  return a;
+}
+
+// A host call's staging: the arrays, room for the streams' bytes, and the uploads both calls make
+// (the input up to in_total and the three per-stream arrays), on s.
+static sm_status upload_streams(smm_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                                const uint64_t* out_off, size_t n, size_t entries, size_t in_total, size_t out_total,
+                                HostArrays& a, hipStream_t s) {
+  SM_CHECK(ctx->io_meta.ensure(carve_host(0, n, entries).end));
+  a = carve_host((uintptr_t)ctx->io_meta.p, n, entries);
+  SM_CHECK(ctx->io_in.ensure(in_total + 16));
+  SM_CHECK(ctx->io_out.ensure(out_total + 16));
+  if (in_total) SM_CHECK(hipMemcpyAsync(ctx->io_in.p, in, in_total, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(a.in_off, in_off, 8 * n, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(a.out_off, out_off, 8 * n, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(a.in_len, in_len, 4 * n, hipMemcpyHostToDevice, s));
+  return SM_OK;
+}
+
+// Each stream's own bytes down from ctx->io_out, behind the results' read-back (s is idle).  The
+// most a stream can have written: out_cap[i], or without out_cap the compressor's bound for
+// in_len[i].  Synchronises s.
+static sm_status copy_out(smm_ctx* ctx, uint8_t* out, const uint64_t* out_off, const uint32_t* out_len,
+                          const int32_t* status, size_t n, const uint32_t* in_len, const uint32_t* out_cap,
+                          hipStream_t s) {
+  for (size_t i = 0; i < n; ++i) {
+    if (status[i] != SM_OK || out_len[i] == 0) continue;
+    if (out_len[i] > (out_cap ? out_cap[i] : smm::max_compressed_length(in_len[i]))) return SM_ERR_DEVICE;
+    SM_CHECK(hipMemcpyAsync(out + out_off[i], (const uint8_t*)ctx->io_out.p + out_off[i], out_len[i],
+                            hipMemcpyDeviceToHost, s));
+  }
+  SM_CHECK(hipStreamSynchronize(s));
   return SM_OK;
 }
 
@@ -242,31 +234,18 @@ sm_status smm_compress(smm_ctx* ctx, const uint8_t* in, const uint64_t* in_off, 
   DeviceGuard g(ctx->device);
   hipStream_t s = ctx->stream;
   HostArrays a;
-  SMM_PASS(host_arrays(ctx, n, entries, a));
-  SMM_CHECK(ctx->io_in.ensure(in_total + 16));
-  SMM_CHECK(ctx->io_out.ensure(out_total + 16));
-  if (in_total) SMM_CHECK(hipMemcpyAsync(ctx->io_in.p, in, in_total, hipMemcpyHostToDevice, s));
-  SMM_CHECK(hipMemcpyAsync(a.in_off, in_off, 8 * n, hipMemcpyHostToDevice, s));
-  SMM_CHECK(hipMemcpyAsync(a.out_off, out_off, 8 * n, hipMemcpyHostToDevice, s));
-  SMM_CHECK(hipMemcpyAsync(a.in_len, in_len, 4 * n, hipMemcpyHostToDevice, s));
-  SMM_PASS(smm_compress_device(ctx, (const uint8_t*)ctx->io_in.p, a.in_off, a.in_len, nstreams, (uint32_t)entries,
-                               (uint8_t*)ctx->io_out.p, a.out_off, a.out_len, a.status, frag_first ? a.first : nullptr,
-                               frag_first ? a.pos : nullptr, mode, s));
-  SMM_CHECK(hipMemcpyAsync(out_len, a.out_len, 4 * n, hipMemcpyDeviceToHost, s));
-  SMM_CHECK(hipMemcpyAsync(status, a.status, 4 * n, hipMemcpyDeviceToHost, s));
+  SM_PASS(upload_streams(ctx, in, in_off, in_len, out_off, n, entries, in_total, out_total, a, s));
+  SM_PASS(smm_compress_device(ctx, (const uint8_t*)ctx->io_in.p, a.in_off, a.in_len, nstreams, (uint32_t)entries,
+                              (uint8_t*)ctx->io_out.p, a.out_off, a.out_len, a.status, frag_first ? a.first : nullptr,
+                              frag_first ? a.pos : nullptr, mode, s));
+  SM_CHECK(hipMemcpyAsync(out_len, a.out_len, 4 * n, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(status, a.status, 4 * n, hipMemcpyDeviceToHost, s));
   if (frag_first) {
-    SMM_CHECK(hipMemcpyAsync(frag_first, a.first, 4 * (n + 1), hipMemcpyDeviceToHost, s));
-    if (entries) SMM_CHECK(hipMemcpyAsync(frag_pos, a.pos, 4 * (size_t)entries, hipMemcpyDeviceToHost, s));
+    SM_CHECK(hipMemcpyAsync(frag_first, a.first, 4 * (n + 1), hipMemcpyDeviceToHost, s));
+    if (entries) SM_CHECK(hipMemcpyAsync(frag_pos, a.pos, 4 * (size_t)entries, hipMemcpyDeviceToHost, s));
   }
-  SMM_CHECK(hipStreamSynchronize(s));
-  for (size_t i = 0; i < n; ++i) {  // each stream's own bytes
-    if (status[i] != SM_OK || out_len[i] == 0) continue;
-    if (out_len[i] > smm::max_compressed_length(in_len[i])) return SM_ERR_DEVICE;
-    SMM_CHECK(hipMemcpyAsync(out + out_off[i], (const uint8_t*)ctx->io_out.p + out_off[i], out_len[i],
-                             hipMemcpyDeviceToHost, s));
-  }
-  SMM_CHECK(hipStreamSynchronize(s));
-  return SM_OK;
+  SM_CHECK(hipStreamSynchronize(s));
+  return copy_out(ctx, out, out_off, out_len, status, n, in_len, nullptr, s);
 }
 
 sm_status smm_uncompress(smm_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
@@ -289,36 +268,21 @@ sm_status smm_uncompress(smm_ctx* ctx, const uint8_t* in, const uint64_t* in_off
   DeviceGuard g(ctx->device);
   hipStream_t s = ctx->stream;
   HostArrays a;
-  SMM_PASS(host_arrays(ctx, n, entries, a));
-  SMM_CHECK(ctx->io_in.ensure(in_total + 16));
-  SMM_CHECK(ctx->io_out.ensure(out_total + 16));
-  SMM_CHECK(hipMemcpyAsync(ctx->io_in.p, in, in_total, hipMemcpyHostToDevice, s));
-  SMM_CHECK(hipMemcpyAsync(a.in_off, in_off, 8 * n, hipMemcpyHostToDevice, s));
-  SMM_CHECK(hipMemcpyAsync(a.out_off, out_off, 8 * n, hipMemcpyHostToDevice, s));
-  SMM_CHECK(hipMemcpyAsync(a.in_len, in_len, 4 * n, hipMemcpyHostToDevice, s));
-  SMM_CHECK(hipMemcpyAsync(a.cap, out_cap, 4 * n, hipMemcpyHostToDevice, s));
+  SM_PASS(upload_streams(ctx, in, in_off, in_len, out_off, n, entries, in_total, out_total, a, s));
+  SM_CHECK(hipMemcpyAsync(a.cap, out_cap, 4 * n, hipMemcpyHostToDevice, s));
   if (frag_first) {
-    SMM_CHECK(hipMemcpyAsync(a.first, frag_first, 4 * (n + 1), hipMemcpyHostToDevice, s));
-    if (entries) SMM_CHECK(hipMemcpyAsync(a.pos, frag_pos, 4 * entries, hipMemcpyHostToDevice, s));
+    SM_CHECK(hipMemcpyAsync(a.first, frag_first, 4 * (n + 1), hipMemcpyHostToDevice, s));
+    if (entries) SM_CHECK(hipMemcpyAsync(a.pos, frag_pos, 4 * entries, hipMemcpyHostToDevice, s));
   }
-  SMM_PASS(smm_uncompress_device(ctx, (const uint8_t*)ctx->io_in.p, a.in_off, a.in_len, nstreams, (uint32_t)entries,
-                                 (uint8_t*)ctx->io_out.p, a.out_off, a.cap, a.out_len, a.status,
-                                 frag_first ? a.first : nullptr, frag_first ? a.pos : nullptr, s));
-  SMM_CHECK(hipMemcpyAsync(out_len, a.out_len, 4 * n, hipMemcpyDeviceToHost, s));
-  SMM_CHECK(hipMemcpyAsync(status, a.status, 4 * n, hipMemcpyDeviceToHost, s));
-  SMM_CHECK(hipStreamSynchronize(s));
-  for (size_t i = 0; i < n; ++i) {
-    if (status[i] != SM_OK) {
-      out_len[i] = 0;
-      continue;
-    }
-    if (out_len[i] > out_cap[i]) return SM_ERR_DEVICE;
-    if (out_len[i])
-      SMM_CHECK(hipMemcpyAsync(out + out_off[i], (const uint8_t*)ctx->io_out.p + out_off[i], out_len[i],
-                               hipMemcpyDeviceToHost, s));
-  }
-  SMM_CHECK(hipStreamSynchronize(s));
-  return SM_OK;
+  SM_PASS(smm_uncompress_device(ctx, (const uint8_t*)ctx->io_in.p, a.in_off, a.in_len, nstreams, (uint32_t)entries,
+                                (uint8_t*)ctx->io_out.p, a.out_off, a.cap, a.out_len, a.status,
+                                frag_first ? a.first : nullptr, frag_first ? a.pos : nullptr, s));
+  SM_CHECK(hipMemcpyAsync(out_len, a.out_len, 4 * n, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(status, a.status, 4 * n, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipStreamSynchronize(s));
+  for (size_t i = 0; i < n; ++i)
+    if (status[i] != SM_OK) out_len[i] = 0;
+  return copy_out(ctx, out, out_off, out_len, status, n, in_len, out_cap, s);
 }
 
 }  // extern "C"

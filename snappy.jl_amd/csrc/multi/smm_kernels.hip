@@ -9,52 +9,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../common/smc_device.h"
 #include "smm_plan.h"
 
 namespace smm {
 
 namespace {
 
-constexpr uint32_t kWave = 64;
+using smc::block_scan;
+using smc::copy_bytes;
+using smc::sat32;
+
 constexpr uint32_t kThreads = 256;
-
-// n bytes from src to dst, both at any alignment, by `nthreads` threads of which this is `tid`:
-// aligned 16-byte loads of the granules src wholly covers, bytes for the partial granules at both
-// ends (no byte outside [src, src + n) is read), stores at dst's alignment.
-__device__ inline void copy_bytes(const uint8_t* __restrict__ src, uint32_t n, uint8_t* __restrict__ dst, uint32_t tid,
-                                  uint32_t nthreads) {
-  const uint32_t head = min(n, (16u - (uint32_t)((uintptr_t)src & 15)) & 15u);
-  const uint32_t G = (n - head) / 16;
-  const uint4* g = reinterpret_cast<const uint4*>(src + head);
-  for (uint32_t u = tid; u < G; u += nthreads) {
-    const uint4 v = g[u];
-    __builtin_memcpy(dst + head + 16 * u, &v, 16);
-  }
-  const uint32_t edge = n - 16 * G;  // head bytes, then the tail's
-  for (uint32_t i = tid; i < edge; i += nthreads) {
-    const uint32_t j = i < head ? i : 16 * G + i;
-    dst[j] = src[j];
-  }
-}
-
-// exclusive scan of v over the workgroup's 256 threads (sh: 4 u64); total = the sum
-__device__ inline uint64_t block_scan(uint64_t v, uint64_t* sh, uint64_t& total) {
-  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint64_t inc = v;
-  for (uint32_t d = 1; d < kWave; d <<= 1) {
-    const uint64_t o = __shfl_up(inc, d, kWave);
-    if (lane >= d) inc += o;
-  }
-  __syncthreads();  // (sh is free again)
-  if (lane == kWave - 1) sh[w] = inc;
-  __syncthreads();
-  uint64_t pre = 0;
-  for (uint32_t k = 0; k < w; ++k) pre += sh[k];
-  total = sh[0] + sh[1] + sh[2] + sh[3];
-  return pre + inc - v;
-}
-
-__device__ inline uint32_t sat32(uint64_t v) { return v > 0xffffffffull ? 0xffffffffu : (uint32_t)v; }
 
 // the stream that owns slot j: the largest s < n with first[s] <= j (first: an exclusive scan from
 // 0, n + 1 entries, j < first[n]) -- a stream with no slots is never the largest

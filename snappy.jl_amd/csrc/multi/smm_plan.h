@@ -9,33 +9,31 @@
 #include <stdint.h>
 
 #include "../../../include/snappy_mi355x_multi.h"
+#include "../common/smc_layout.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
-#define SMM_HD __host__ __device__
-#else
-#define SMM_HD
 #endif
 
 namespace smm {
 
+using smc::max_compressed_length;
+
 constexpr uint32_t kBlock = SM_BLOCK_SIZE;
 constexpr uint32_t kMaxInput = 0x7fffffffu;   // a longer stream: SM_ERR_INPUT_TOO_LARGE, unread
 constexpr uint32_t kNoStream = 0xffffffffu;   // a fragment slot no stream owns
-// a fragment's slot: sm_max_compressed_length(65536) + 8 = 76,498, rounded up to 256 (sm_compress's)
-constexpr uint64_t kSlotPitch = 76544;
+constexpr uint64_t kSlotPitch = smc::kMultiSlotPitch;  // a fragment's slot
 constexpr uint32_t kDummy = 64;               // a long stream's slot in the short-stream call: "00", with the
                                               // room an empty input's slot has (sm_max_compressed_length(0) = 32)
 
-SMM_HD inline uint32_t fragment_count(uint64_t len) { return (uint32_t)((len + kBlock - 1) / kBlock); }
-SMM_HD inline uint32_t varint_len(uint32_t v) {
+SMC_HD inline uint32_t fragment_count(uint64_t len) { return (uint32_t)((len + kBlock - 1) / kBlock); }
+SMC_HD inline uint32_t varint_len(uint32_t v) {
   return 1u + (v >= 1u << 7) + (v >= 1u << 14) + (v >= 1u << 21) + (v >= 1u << 28);
 }
-SMM_HD inline uint64_t max_compressed_length(uint64_t n) { return 32 + n + n / 6; }  // src/Snappy.jl:80-82
 
 // varint32 header of p[0..n) (src/varint.jl:12-37): false for a truncated header, more than 5
 // bytes or a 5th byte >= 0x10.  Reads at most min(n, 5) bytes.
-SMM_HD inline bool parse_varint(const uint8_t* p, uint32_t n, uint32_t& value, uint32_t& hv) {
+SMC_HD inline bool parse_varint(const uint8_t* p, uint32_t n, uint32_t& value, uint32_t& hv) {
   value = 0;
   for (uint32_t i = 0; i < 5 && i < n; ++i) {
     const uint32_t b = p[i];
@@ -56,7 +54,7 @@ SMM_HD inline bool parse_varint(const uint8_t* p, uint32_t n, uint32_t& value, u
 
 // ---- the index rules (include/snappy_mi355x_multi.h, smm_uncompress_device) ------------------
 // The rule on d_frag_first at element s < nstreams: from 0, non-decreasing, the last <= max_fragments.
-SMM_HD inline bool first_rule(const uint32_t* first, uint32_t s, uint32_t nstreams, uint32_t max_fragments) {
+SMC_HD inline bool first_rule(const uint32_t* first, uint32_t s, uint32_t nstreams, uint32_t max_fragments) {
   if (s == 0 && first[0] != 0) return false;
   if (first[s] > first[s + 1]) return false;
   return s + 1 < nstreams || first[nstreams] <= max_fragments;
@@ -68,7 +66,7 @@ struct Candidate {
 
 // Stream-level rules, everything but the positions: p[0..n) is the stream, cap its output room,
 // [e0, e1) its entries.  Bounds first: a candidate's entries lie inside d_frag_pos.
-SMM_HD inline bool stream_candidate(const uint8_t* p, uint32_t n, uint32_t cap, uint32_t e0, uint32_t e1,
+SMC_HD inline bool stream_candidate(const uint8_t* p, uint32_t n, uint32_t cap, uint32_t e0, uint32_t e1,
                                     uint32_t max_fragments, Candidate& c) {
   if (e0 > e1 || e1 > max_fragments) return false;
   if (n >= SM_OUT_LEN_ERROR) return false;  // (an error mark, not a length: the decoder's business)
@@ -82,7 +80,7 @@ SMM_HD inline bool stream_candidate(const uint8_t* p, uint32_t n, uint32_t cap, 
 // Fragment f of a candidate: its bytes [lo, hi) in the stream.  pos: the stream's `count` entries.
 // True for every f exactly when the first position is hv, the positions increase strictly and the
 // last is below n; and a fragment that passes alone lies inside the stream whatever the others hold.
-SMM_HD inline bool fragment_range(const uint32_t* pos, uint32_t f, uint32_t count, uint32_t hv, uint32_t n,
+SMC_HD inline bool fragment_range(const uint32_t* pos, uint32_t f, uint32_t count, uint32_t hv, uint32_t n,
                                   uint32_t& lo, uint32_t& hi) {
   lo = pos[f];
   hi = f + 1 < count ? pos[f + 1] : n;
@@ -91,21 +89,12 @@ SMM_HD inline bool fragment_range(const uint32_t* pos, uint32_t f, uint32_t coun
 }
 
 // what fragment f of `count` must decode to
-SMM_HD inline uint32_t fragment_length(uint32_t D, uint32_t f, uint32_t count) {
+SMC_HD inline uint32_t fragment_length(uint32_t D, uint32_t f, uint32_t count) {
   return f + 1 < count ? kBlock : D - kBlock * (count - 1);
 }
 
-// ---- scratch ---------------------------------------------------------------------------------
-// consecutive arrays of one buffer, each rounded up to 16 bytes
-struct Carve {
-  uintptr_t p;  // (an integer: a null base measures the layout)
-  template <typename T>
-  T* take(size_t n) {
-    T* r = reinterpret_cast<T*>(p);
-    p += (n * sizeof(T) + 15) / 16 * 16;
-    return r;
-  }
-};
+// ---- scratch (smc::Carve: a null base measures) ------------------------------------------------
+using smc::Carve;
 
 struct Header {  // the plans' words for the kernels behind them
   uint32_t nlong;     // compress: fragments of the long streams; uncompress: of the candidates

@@ -15,32 +15,13 @@
 #include <vector>
 
 #include "../../include/snappy_mi355x.h"
+#include "common/smc_hip_host.h"
 #include "sm_device.h"
 #include "sm_internal.h"
 
 #ifndef SM_VERSION_STR
 #define SM_VERSION_STR "dev"
 #endif
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = n < 4096 ? 4096 : n;
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
 
 // Host staging: page-aligned ordinary memory registered for DMA (hipHostRegister), so the CPU
 // reads it through its caches -- the host walks the index records and scatters batch outputs
@@ -119,20 +100,6 @@ struct sm_ctx {
 #endif
 
 namespace {
-
-bool valid_mode(int m) { return m == SM_MODE_REFERENCE || m == SM_MODE_FAST || m == SM_MODE_FAST_DENSE; }
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -568,11 +535,6 @@ int small_uncompress(sm_ctx* ctx, const uint8_t* comp, uint32_t n, uint32_t ip0,
 }
 
 }  // namespace
-
-#define SM_CHECK(x)                 \
-  do {                              \
-    if ((x) != hipSuccess) return SM_ERR_DEVICE; \
-  } while (0)
 
 namespace {
 // Shard [b0, b1) of a host batch, rebased so the single-context call copies only the shard's

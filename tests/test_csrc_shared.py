@@ -1,0 +1,59 @@
+"""The helpers the three libraries share (snappy.jl_amd/csrc/common/) exist once: a second copy of
+the byte mover, the block scan, the device buffer or the scratch carver under csrc/ fails here, and
+so does a scratch size kept as a constant beside its carve.  Reads sources only."""
+import functools
+import os
+import re
+
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "snappy.jl_amd", "csrc")
+
+
+@functools.lru_cache(maxsize=None)
+def _sources():
+    out = {}
+    for d, _, files in os.walk(CSRC):
+        if os.path.basename(d).startswith("build"):
+            continue
+        for f in files:
+            if f.endswith((".hip", ".h", ".cpp", ".mk")) or f == "Makefile":
+                p = os.path.join(d, f)
+                text = open(p).read()
+                text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+                out[os.path.relpath(p, CSRC)] = re.sub(r"//[^\n]*", "", text)
+    return out
+
+
+def _definitions(pattern):
+    return sorted(f for f, text in _sources().items() for _ in re.finditer(pattern, text))
+
+
+def test_shared_directory_is_read():
+    names = set(_sources())
+    assert {"sm_api.hip", "framing/smf_kernels.hip", "framing/smf_range.hip", "multi/smm_kernels.hip",
+            "common/companion.mk"} <= names
+
+
+def test_device_helpers_have_one_definition():
+    for name in ("copy_bytes", "block_scan", "sat32"):
+        # a function definition: a return type before the name, a body behind the parameters
+        found = _definitions(r"\b[\w:]+[\s\*&]+%s\s*\([^;{}]*\)\s*\{" % name)
+        assert len(found) == 1 and found[0].startswith("common/"), (name, found)
+
+
+def test_host_helpers_have_one_definition():
+    for pattern in (r"\bstruct\s+DevBuf\b\s*\{", r"\bstruct\s+DeviceGuard\b\s*\{", r"\bstruct\s+\w*Carve\w*\s*\{",
+                    r"\b[\w:]+\s+valid_mode\s*\([^;{}]*\)\s*\{", r"#\s*define\s+\w*_CHECK\s*\(", r"#\s*define\s+\w*_PASS\s*\("):
+        found = _definitions(pattern)
+        assert len(found) == 1 and found[0].startswith("common/"), (pattern, found)
+    assert _definitions(r"\bstruct\s+\w*Carve\w*\s*\{") == _definitions(r"\bstruct\s+Carve\s*\{")
+
+
+def test_no_scratch_size_beside_its_carve():
+    for name in ("RangeCarve", "kCompressMeta", "kDecodeMeta", "kIndexMeta"):
+        found = _definitions(r"\b%s\b" % name)
+        assert not found, (name, found)
+    # (the function of that name; sm_api.hip has locals called meta_bytes)
+    found = _definitions(r"\bmeta_bytes\s*\([^;{}]*\)\s*\{")
+    assert not found, found
