@@ -66,6 +66,24 @@ struct HostBuf {
   }
 };
 
+// A single-buffer call's result in that staging, by the convention above: the last kernel writes
+// the bytes at 0 and its verdict words behind them at the next multiple of 256, and the host reads
+// both after the stream's synchronisation, the words through a volatile pointer.
+struct PinnedResult {
+  HostBuf& st;
+  size_t w_off = 0;
+  bool ensure(size_t nbytes, size_t wbytes = 64) {  // false: no mapped staging of that size
+    w_off = (nbytes + 255) / 256 * 256;
+    return st.ensure(w_off + wbytes) == hipSuccess && st.dp;
+  }
+  uint8_t* d_bytes() const { return (uint8_t*)st.dp; }  // the launch's pointers
+  template <typename T = uint32_t>
+  T* d_words() const { return (T*)((uint8_t*)st.dp + w_off); }
+  template <typename T = uint32_t>
+  volatile T* words() const { return (volatile T*)((uint8_t*)st.p + w_off); }  // the host's
+  const void* bytes() const { return st.p; }
+};
+
 struct sm_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -95,13 +113,9 @@ struct sm_ctx {
   std::atomic<int> last_parts{0};  // sm_ctx_last_batch_parts
 };
 
-#ifndef SM_SMALL_BODY8  // path 4 when the body is at most SM_SMALL_BODY8/8 of the output
-#define SM_SMALL_BODY8 8
-#endif
-
 namespace {
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+using sm::PathChunk;
 
 #ifdef SM_HOST_TRACE  // diagnostic builds: phase times of the single-buffer entry points on stderr
 #include <chrono>
@@ -122,7 +136,6 @@ struct HostTrace {
 #define HT(what)
 #endif
 
-constexpr uint32_t kParallelMinOutput = 4 * 65536;  // smaller streams: one wave is as fast
 constexpr size_t kOrgKeep = 256u << 20;  // origin-pointer scratch a context keeps after a decode
 constexpr size_t kPipeMinInput = 32u << 20;  // sm_compress: inputs this large upload in pieces
 constexpr size_t kSmallCompressMax = 4u << 20;  // sm_compress: inputs up to this size (64 fragments) synchronise once
@@ -132,8 +145,48 @@ constexpr uint32_t kPieceFrags = 256;        // 16 MiB per piece
 #endif
 constexpr uint32_t kOutPieceFrags = SM_OUT_PIECE;  // sm_uncompress: output pieces (128 MiB)
 
-constexpr size_t kPinnedInMin = 32u << 10;  // host inputs from this size up go through stage_in
-constexpr size_t kPinnedInMax = 16u << 20;  // ... up to this size
+constexpr size_t kPinnedInMin = 32u << 10;  // host inputs from this size up (to sm::kPinnedInMax) go through stage_in
+
+// A HIP failure behind launches that may read the pinned input staging: nothing stays queued
+// when the call returns, so no later call can free pages the device still reads.
+sm_status device_failure(hipStream_t s) {
+  (void)hipStreamSynchronize(s);
+  return SM_ERR_DEVICE;
+}
+
+// One call's use of the context's pinned, device-mapped input staging (ctx->stage_in): acquire()
+// waits until the device is done with the previous contents (in_ev, recorded behind the last
+// launch that read them) before the buffer may grow -- growing unregisters and frees the old
+// pages -- and copies the caller's bytes in; finish() goes behind the last launch that reads the
+// staging and records that event, once (an event between the launches costs each call ~4 us).
+// When a launch or the record failed it synchronises the stream instead, and so does the
+// destructor on any exit that did not reach finish(): no return leaves a reader queued.
+struct StagedInput {
+  sm_ctx* const ctx;
+  const hipStream_t s;
+  const uint8_t* dp = nullptr;  // the staged bytes for the device; null: nothing a launch may read
+  StagedInput(sm_ctx* c, hipStream_t st) : ctx(c), s(st) {}
+  StagedInput(const StagedInput&) = delete;
+  ~StagedInput() {
+    if (dp) (void)hipStreamSynchronize(s);
+  }
+  bool acquire(const void* src, size_t n) {  // false: no staging
+    if (ctx->in_ev && hipEventSynchronize(ctx->in_ev) != hipSuccess) return false;
+    if (ctx->stage_in.ensure(n + 16) != hipSuccess || !ctx->stage_in.dp) return false;
+    memcpy(ctx->stage_in.p, src, n);
+    dp = (const uint8_t*)ctx->stage_in.dp;
+    return true;
+  }
+  hipError_t finish(hipError_t le) {  // le: the result of the launches that read the staging
+    if (le == hipSuccess && !ctx->in_ev && (le = hipEventCreateWithFlags(&ctx->in_ev, hipEventDisableTiming)) != hipSuccess)
+      ctx->in_ev = nullptr;
+    if (le == hipSuccess) le = hipEventRecord(ctx->in_ev, s);
+    if (le != hipSuccess) (void)hipStreamSynchronize(s);
+    dp = nullptr;
+    return le;
+  }
+  void drained() { dp = nullptr; }  // the caller synchronised the stream behind the readers
+};
 
 // A host input of a single-buffer call into ctx->in.  Inputs of 32 KiB to 16 MiB are copied on
 // the host into the context's pinned, device-mapped staging and moved to the device by a copy
@@ -141,93 +194,40 @@ constexpr size_t kPinnedInMax = 16u << 20;  // ... up to this size
 // 70 -> 67, 64 KiB compress 52 -> 48 (profiles/r06_upload_ab.txt).  Smaller inputs stay with the
 // runtime's pageable copy, which is 2-4 us faster there than the staging (its event and the
 // extra launch), and so does an upload through the copy engine from the staging at every size.
-// The staging is reused by the next call only after the previous upload's event.
-// the pinned input staging for n bytes, once the device is done with its previous contents (the
-// event recorded behind the last launch that read it); false: no staging
-bool stage_in_acquire(sm_ctx* ctx, size_t n) {
-  if (ctx->stage_in.ensure(n + 16) != hipSuccess || !ctx->stage_in.dp) return false;
-  return !ctx->in_ev || hipEventSynchronize(ctx->in_ev) == hipSuccess;
-}
-// after the launches that read the staging: their completion event
-hipError_t stage_in_release(sm_ctx* ctx, hipStream_t s) {
-  if (!ctx->in_ev) {
-    const hipError_t e = hipEventCreateWithFlags(&ctx->in_ev, hipEventDisableTiming);
-    if (e != hipSuccess) {
-      ctx->in_ev = nullptr;
-      return e;
-    }
-  }
-  return hipEventRecord(ctx->in_ev, s);
-}
-
 hipError_t upload_input(sm_ctx* ctx, const void* src, size_t n, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  if (n >= kPinnedInMin && n <= kPinnedInMax && stage_in_acquire(ctx, n)) {
-    memcpy(ctx->stage_in.p, src, n);
-    const hipError_t e = sm::launch_to_host((const uint8_t*)ctx->stage_in.dp, (uint32_t)n, (uint8_t*)ctx->in.p,
-                                            nullptr, 0, nullptr, s);
-    if (e != hipSuccess) return e;
-    return stage_in_release(ctx, s);
-  }
+  StagedInput in(ctx, s);
+  if (n >= kPinnedInMin && n <= sm::kPinnedInMax && in.acquire(src, n))
+    return in.finish(sm::launch_to_host(in.dp, (uint32_t)n, (uint8_t*)ctx->in.p, nullptr, 0, nullptr, s));
   return hipMemcpyAsync(ctx->in.p, src, n, hipMemcpyHostToDevice, s);
 }
 
-// sm_uncompress path 5: are the stream's tags literals only?  At most kLitSpans of them (an
-// incompressible input's stream has one literal per 64 KiB block), each with at most 3 length
-// bytes, inside the input and the declared length, together covering both exactly.  Then the
-// reference's decode (internal.jl:411-527: every tag starts before the input's last byte, and
-// copy_literal!'s checks pass) is those literals' bytes in order, and Snappy.jl:50's length check
-// holds.  Anything else -- a copy tag, a 4-byte length, more tags, a stream that ends early or
-// late -- is not path 5, and the other paths reproduce the reference's accept/reject.  Reads the
-// tag headers only (at most 4 bytes a tag); the bytes move on the device.
-bool literal_only(const uint8_t* c, size_t n, size_t hdr, uint32_t size, sm::LitSpans& sp) {
-  size_t p = hdr;
-  uint64_t o = 0;
-  sp.n = 0;
-  while (p < n) {
-    if (sp.n == sm::kLitSpans) return false;
-    const uint32_t t = c[p];
-    if (t & 3) return false;  // a copy
-    uint64_t len = (t >> 2) + 1;
-    size_t q = p + 1;
-    if ((t >> 2) >= 60) {
-      const uint32_t nb = (t >> 2) - 59;
-      if (nb > 3 || q + nb > n) return false;
-      uint32_t v = 0;
-      for (uint32_t k = 0; k < nb; ++k) v |= (uint32_t)c[q + k] << (8 * k);
-      len = (uint64_t)v + 1;
-      q += nb;
-    }
-    if (q + len > n || o + len > size) return false;
-    sp.src[sp.n] = (uint32_t)q;
-    sp.dst[sp.n] = (uint32_t)o;
-    ++sp.n;
-    o += len;
-    p = q + len;
-  }
-  sp.dst[sp.n] = (uint32_t)o;
-  return sp.n > 0 && o == size;
-}
+// What a decode path of sm_uncompress did.
+struct PathResult {
+  enum Kind { kTaken, kFallBack, kDeviceError, kStreamError } kind;
+  int path = 0;             // kTaken, kStreamError: what sm_ctx_last_path reports
+  int32_t status = SM_OK;   // kStreamError: the stream's first error (the reference throws: no output)
+  bool in_ctx_out = false;  // kTaken: the output is in ctx->out (else already in the caller's buffer)
+};
+constexpr PathResult kFallBack{PathResult::kFallBack}, kDeviceError{PathResult::kDeviceError};
 
 // path 5: the input into the pinned staging on the host, the literals to the pinned output by
-// k_literal_spans reading and writing the mapped pages, then the bytes to the caller.  1: done,
-// 0: not taken (no mapped staging), -1: a device error.
-int literal_uncompress(sm_ctx* ctx, const uint8_t* comp, size_t n, uint32_t size, const sm::LitSpans& ls,
-                       uint8_t* host_out) {
+// k_literal_spans reading and writing the mapped pages, then the bytes to the caller.  Falls back
+// when there is no mapped staging.
+PathResult literal_uncompress(sm_ctx* ctx, const uint8_t* comp, size_t n, uint32_t size, const sm::LitSpans& ls,
+                              uint8_t* host_out) {
   hipStream_t s = ctx->stream;
-  const size_t w_off = align_up(size, 256);
-  if (ctx->stage.ensure(w_off + 64) != hipSuccess || !ctx->stage.dp) return 0;
-  if (!stage_in_acquire(ctx, n)) return 0;
-  memcpy(ctx->stage_in.p, comp, n);
-  uint8_t* const sdp = (uint8_t*)ctx->stage.dp;
-  volatile uint32_t* const w = (volatile uint32_t*)((uint8_t*)ctx->stage.p + w_off);
+  PinnedResult res{ctx->stage};
+  StagedInput in(ctx, s);
+  if (!res.ensure(size) || !in.acquire(comp, n)) return kFallBack;
+  volatile uint32_t* const w = res.words();
   w[1] = 0xffffffffu;  // (the kernel writes SM_OK)
-  if (sm::launch_literal_spans((const uint8_t*)ctx->stage_in.dp, ls, sdp, (uint32_t*)(sdp + w_off), s) != hipSuccess)
-    return -1;
-  if (hipStreamSynchronize(s) != hipSuccess) return -1;
-  if (w[1] != 0 || w[0] != size) return -1;
-  memcpy(host_out, ctx->stage.p, size);
-  return 1;
+  if (sm::launch_literal_spans(in.dp, ls, res.d_bytes(), res.d_words(), s) != hipSuccess) return kDeviceError;
+  if (hipStreamSynchronize(s) != hipSuccess) return kDeviceError;
+  in.drained();
+  if (w[1] != 0 || w[0] != size) return kDeviceError;
+  memcpy(host_out, res.bytes(), size);
+  return {PathResult::kTaken, 5};
 }
 
 // the context's copy stream and at least n events (created on first use)
@@ -248,321 +248,163 @@ hipError_t ensure_copy_stream(sm_ctx* ctx, size_t n) {
   return hipSuccess;
 }
 
-// Host tag walk over [p, lim) of a stream (zero-padded lookahead, internal.jl:426-462): where it
-// leaves the range and how much output the tags make.  Used when a chunk is entered deeper than
-// the entry offsets the index kernel covers.
-void host_walk(const uint8_t* comp, uint32_t n, uint64_t p, uint64_t lim, uint64_t* exit_pos, uint64_t* produced) {
-  uint64_t o = 0;
-  while (p < lim) {
-    const uint32_t c = comp[p];
-    const uint32_t entry = sm::char_entry(c);
-    const uint32_t taglen = entry >> 11;
-    uint32_t tr = 0;
-    for (uint32_t k = 0; k < 4; ++k) tr |= (p + 1 + k < n ? (uint32_t)comp[p + 1 + k] : 0u) << (8 * k);
-    const uint32_t trailer = taglen >= 4 ? tr : (tr & ((1u << (8 * taglen)) - 1u));
-    if (c & 3) {
-      p += 1 + taglen;
-      o += entry & 0xff;
-    } else {
-      const uint32_t lit = (entry & 0xff) + trailer;
-      p += 1ull + taglen + lit;
-      o += lit;
-    }
-  }
-  *exit_pos = p;
-  *produced = o;
-}
-
 // The first error of a stream whose tag path is known: one wave per path element checks its tags
 // (k_path_check), and the first failing element in path order holds the reference's status.  With
-// no failing tag the stream is short of its declared length (Snappy.jl:50).  Returns 3 with *err
-// set, 0 to fall back to the in-order decode, -1 on a device error.
-struct PathChunk {
-  uint64_t y, O, out, ex;
-};
-int path_first_error(sm_ctx* ctx, uint32_t n, uint32_t size, const std::vector<PathChunk>& path, int32_t* err) {
-  if (n >= 0x80000000u || path.empty()) return 0;
+// no failing tag the stream is short of its declared length (Snappy.jl:50).  Path 3 with that
+// status, or a fall back to the in-order decode.
+PathResult path_first_error(sm_ctx* ctx, uint32_t n, uint32_t size, const std::vector<PathChunk>& path) {
+  if (n >= 0x80000000u || path.empty()) return kFallBack;
   hipStream_t s = ctx->stream;
   const size_t npath = path.size();
-  std::vector<sm::OriginPath> op(npath);
-  for (size_t e = 0; e < npath; ++e) {
-    // an element past 2^32 of output is past any declared size: its O saturates (it fails its checks)
-    const uint64_t O = std::min<uint64_t>(path[e].O, 0xffffffffull), out = std::min<uint64_t>(path[e].out, 0xffffffffull - O);
-    op[e] = {(uint32_t)path[e].y, (uint32_t)std::min<uint64_t>(path[e].ex, 0xffffffffull), (uint32_t)O, (uint32_t)out};
-  }
-  const size_t st_off = align_up(npath * sizeof(sm::OriginPath), 256);
-  if (ctx->org.ensure(st_off + npath * 4) != hipSuccess) return 0;
-  sm::OriginPath* d_path = (sm::OriginPath*)ctx->org.p;
-  int32_t* d_st = (int32_t*)((uint8_t*)ctx->org.p + st_off);
-  if (hipMemcpyAsync(d_path, op.data(), npath * sizeof(sm::OriginPath), hipMemcpyHostToDevice, s) != hipSuccess)
-    return -1;
-  if (sm::launch_path_check((const uint8_t*)ctx->in.p, n, size, d_path, (uint32_t)npath, d_st, s) != hipSuccess)
-    return -1;
+  const std::vector<sm::OriginPath> op = sm::origin_path(path, true);
+  if (ctx->org.ensure(sm::carve_origin(nullptr, 0, npath).end) != hipSuccess) return kFallBack;
+  const sm::OriginScratch sc = sm::carve_origin(ctx->org.p, 0, npath);
+  if (hipMemcpyAsync(sc.path, op.data(), npath * sizeof(sm::OriginPath), hipMemcpyHostToDevice, s) != hipSuccess)
+    return kDeviceError;
+  if (sm::launch_path_check((const uint8_t*)ctx->in.p, n, size, sc.path, (uint32_t)npath, sc.st, s) != hipSuccess)
+    return kDeviceError;
   std::vector<int32_t> st(npath);
-  if (hipMemcpyAsync(st.data(), d_st, npath * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-  if (hipStreamSynchronize(s) != hipSuccess) return -1;
+  if (hipMemcpyAsync(st.data(), sc.st, npath * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return kDeviceError;
+  if (hipStreamSynchronize(s) != hipSuccess) return kDeviceError;
   for (int32_t v : st) {
     if (v == sm::kOk) continue;
-    if (v == sm::kErrCross) return 0;  // the tags do not tile an element: let the in-order decode decide
-    *err = v;
-    return 3;
+    if (v == sm::kErrCross) return kFallBack;  // the tags do not tile an element: let the in-order decode decide
+    return {PathResult::kStreamError, 3, v};
   }
   const PathChunk& last = path.back();
-  if (last.O + last.out == size) return 0;  // no failing tag and the right length: not an error after all
-  *err = sm::kErrInvalid;  // Snappy.jl:50
-  return 3;
+  if (last.O + last.out == size) return kFallBack;  // no failing tag and the right length: not an error after all
+  return {PathResult::kStreamError, 3, sm::kErrInvalid};  // Snappy.jl:50
 }
 
 // One large stream in parallel (sm_decompress.hip, "one large stream"): index pass, true path
-// on the host, one wave per 64 KiB fragment.  The compressed bytes are in ctx->in.  Returns
-// 1 (or 2, origin pointers) with the output in ctx->out, 3 with *err when the stream has an
-// error (its first one in stream order), 0 to fall back to the in-order decode, -1 on a device
-// error.  With host_out, a large output goes down in pieces on the copy stream as the fragment
-// decode finishes them (*copied = true: host_out holds the result when 1 is returned).
-int parallel_uncompress(sm_ctx* ctx, const uint8_t* comp, uint32_t n, uint32_t ip0, uint32_t size,
-                        uint8_t* host_out, bool* copied, int32_t* err) {
-  *copied = false;
-  using sm::kIdxChunk;
-  using sm::kIdxEntries;
-  const uint32_t nchunks = (n - ip0 + kIdxChunk - 1) / kIdxChunk;
+// on the host, one wave per 64 KiB fragment.  The compressed bytes are in ctx->in.  Path 1 (or 2,
+// origin pointers) with the output in ctx->out, path 3 when the stream has an error (its first
+// one in stream order), or a fall back to the in-order decode.  With host_out, a large output
+// goes down in pieces on the copy stream as the fragment decode finishes them (then host_out
+// holds the result of path 1).
+PathResult parallel_uncompress(sm_ctx* ctx, const uint8_t* comp, uint32_t n, uint32_t ip0, uint32_t size,
+                               uint8_t* host_out) {
+  const uint32_t nchunks = (n - ip0 + sm::kIdxChunk - 1) / sm::kIdxChunk;
   const uint32_t nfrag = (uint32_t)(((uint64_t)size + 65535) / 65536);
-  const size_t rec_n = (size_t)nchunks * kIdxEntries;
-  const size_t frag_off = align_up(2 * rec_n * 4, 16);
-  const size_t st_off = frag_off + (size_t)nfrag * sizeof(sm::StreamFrag);
-  if (ctx->idx.ensure(st_off + (size_t)nfrag * 4) != hipSuccess) return 0;  // (the in-order decode needs no scratch)
+  const size_t rec_bytes = sm::parallel_rec_words(nchunks) * 4;
+  if (ctx->idx.ensure(sm::carve_parallel(nullptr, nchunks, nfrag).end) != hipSuccess) return kFallBack;  // (the in-order decode needs no scratch)
   hipStream_t s = ctx->stream;
   HT_DECL
-  uint32_t* d_rec = (uint32_t*)ctx->idx.p;
+  const sm::ParallelScratch sc = sm::carve_parallel(ctx->idx.p, nchunks, nfrag);
   const uint8_t* d_in = (const uint8_t*)ctx->in.p;
-  if (sm::launch_stream_index(d_in, n, ip0, nchunks, d_rec, s) != hipSuccess) return -1;
+  if (sm::launch_stream_index(d_in, n, ip0, nchunks, sc.rec, s) != hipSuccess) return kDeviceError;
   HT("index kernel")
   // the index records (8 B per entry, ~9 MB per 64 MiB of stream) come back through the
   // context's pinned staging: one DMA, no page faults, no zero fill
-  if (ctx->stage.ensure(2 * rec_n * 4) != hipSuccess) return 0;
-  const uint32_t* rec = (const uint32_t*)ctx->stage.p;
-  if (hipMemcpyAsync(ctx->stage.p, d_rec, 2 * rec_n * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-  if (hipStreamSynchronize(s) != hipSuccess) return -1;
+  if (ctx->stage.ensure(rec_bytes) != hipSuccess) return kFallBack;
+  if (hipMemcpyAsync(ctx->stage.p, sc.rec, rec_bytes, hipMemcpyDeviceToHost, s) != hipSuccess) return kDeviceError;
+  if (hipStreamSynchronize(s) != hipSuccess) return kDeviceError;
   HT("index records D2H")
-  // true path: chunk entries y, output before them O, output of their tags
   std::vector<PathChunk> path;
-  path.reserve(nchunks + 16);
-  uint64_t y = ip0, O = 0;
-  while (y < (uint64_t)n - 1) {  // internal.jl:416
-    const uint64_t c = (y - ip0) / kIdxChunk, base = ip0 + c * kIdxChunk, l = y - base;
-    // the walk enters a chunk a few bytes in: the head of a record a few chunks ahead
-    if (c + 8 < nchunks) __builtin_prefetch(&rec[2 * (c + 8) * kIdxEntries]);
-    uint64_t ex, ot;
-    if (l < kIdxEntries) {
-      ex = rec[2 * (c * kIdxEntries + l)];
-      ot = rec[2 * (c * kIdxEntries + l) + 1];
-    } else {
-      host_walk(comp, n, y, std::min<uint64_t>(base + kIdxChunk, (uint64_t)n - 1), &ex, &ot);
-    }
-    path.push_back({y, O, ot, ex});
-    O += ot;
-    if (ex <= y) return 0;
-    y = ex;
-    if (O > size) break;  // a tag of this element (or an earlier one) fails: find the first
-  }
-  if (O != size) return path_first_error(ctx, n, size, path, err);
-  std::vector<sm::StreamFrag> frags(nfrag);
-  size_t k = 0;
-  for (uint32_t f = 0; f < nfrag; ++f) {
-    const uint64_t F = (uint64_t)f * 65536;
-    while (k + 1 < path.size() && path[k].O + path[k].out <= F) ++k;
-    frags[f] = {(uint32_t)path[k].y, (uint32_t)path[k].O, (uint32_t)F,
-                f + 1 == nfrag ? 0xffffffffu : (uint32_t)(F + 65536)};
-  }
+  const sm::PathEnd end = sm::true_path(comp, n, ip0, size, (const uint32_t*)ctx->stage.p, path);
+  if (end == sm::PathEnd::kFallBack) return kFallBack;
+  if (end == sm::PathEnd::kFirstError) return path_first_error(ctx, n, size, path);
+  const std::vector<sm::StreamFrag> frags = sm::path_frags(path, size);
   HT("host path + fragments")
-  sm::StreamFrag* d_frags = (sm::StreamFrag*)((uint8_t*)ctx->idx.p + frag_off);
-  int32_t* d_st = (int32_t*)((uint8_t*)ctx->idx.p + st_off);
-  if (hipMemcpyAsync(d_frags, frags.data(), frags.size() * sizeof(sm::StreamFrag), hipMemcpyHostToDevice, s) !=
+  if (hipMemcpyAsync(sc.frags, frags.data(), frags.size() * sizeof(sm::StreamFrag), hipMemcpyHostToDevice, s) !=
       hipSuccess)
-    return -1;
+    return kDeviceError;
   const uint32_t nfp = (nfrag + kOutPieceFrags - 1) / kOutPieceFrags;
   const uint32_t npiece = (host_out && nfp > 1 && ensure_copy_stream(ctx, nfp) == hipSuccess) ? nfp : 1;
   uint8_t* out = (uint8_t*)ctx->out.p;
   for (uint32_t pc = 0; pc < npiece; ++pc) {
     const uint32_t f0 = pc * kOutPieceFrags, f1 = npiece == 1 ? nfrag : std::min(nfrag, f0 + kOutPieceFrags);
-    if (sm::launch_decompress_frags(d_in, n, size, out, d_frags + f0, f1 - f0, d_st + f0, s) != hipSuccess) return -1;
-    if (npiece > 1 && hipEventRecord(ctx->ev[pc], s) != hipSuccess) return -1;
+    if (sm::launch_decompress_frags(d_in, n, size, out, sc.frags + f0, f1 - f0, sc.st + f0, s) != hipSuccess)
+      return kDeviceError;
+    if (npiece > 1 && hipEventRecord(ctx->ev[pc], s) != hipSuccess) return kDeviceError;
   }
   if (npiece > 1) {  // each piece's output goes down while the later pieces decode
     for (uint32_t pc = 0; pc < npiece; ++pc) {
       const size_t b0 = (size_t)pc * kOutPieceFrags * 65536;
       const size_t b1 = std::min((size_t)size, b0 + (size_t)kOutPieceFrags * 65536);
-      if (hipStreamWaitEvent(ctx->copy, ctx->ev[pc], 0) != hipSuccess) return -1;
-      if (hipMemcpyAsync(host_out + b0, out + b0, b1 - b0, hipMemcpyDeviceToHost, ctx->copy) != hipSuccess) return -1;
+      if (hipStreamWaitEvent(ctx->copy, ctx->ev[pc], 0) != hipSuccess) return kDeviceError;
+      if (hipMemcpyAsync(host_out + b0, out + b0, b1 - b0, hipMemcpyDeviceToHost, ctx->copy) != hipSuccess)
+        return kDeviceError;
     }
-    if (hipStreamSynchronize(ctx->copy) != hipSuccess) return -1;
+    if (hipStreamSynchronize(ctx->copy) != hipSuccess) return kDeviceError;
   }
   std::vector<int32_t> st(nfrag);
-  if (hipMemcpyAsync(st.data(), d_st, nfrag * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-  if (hipStreamSynchronize(s) != hipSuccess) return -1;
+  if (hipMemcpyAsync(st.data(), sc.st, nfrag * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return kDeviceError;
+  if (hipStreamSynchronize(s) != hipSuccess) return kDeviceError;
   HT("fragment decode")
   bool cross = false;
   for (int32_t v : st) {
     if (v == sm::kErrCross) cross = true;
-    else if (v != sm::kOk) return path_first_error(ctx, n, size, path, err);  // the first error, in parallel
+    else if (v != sm::kOk) return path_first_error(ctx, n, size, path);  // the first error, in parallel
   }
-  if (!cross) {
-    *copied = npiece > 1;
-    return 1;
-  }
+  if (!cross) return {PathResult::kTaken, 1, SM_OK, npiece == 1};
   // Not block-structured (a copy reaches into an earlier block): origin pointers per output
   // byte, resolved by pointer jumping (sm_decompress.hip, "any large stream").
-  if (n >= 0x80000000u || size >= 0x80000000u) return 0;  // 31-bit positions
+  if (n >= 0x80000000u || size >= 0x80000000u) return kFallBack;  // 31-bit positions
   const size_t npath = path.size();
-  std::vector<sm::OriginPath> op(npath);
-  for (size_t e = 0; e < npath; ++e)
-    op[e] = {(uint32_t)path[e].y, (uint32_t)path[e].ex, (uint32_t)path[e].O, (uint32_t)path[e].out};
-  const size_t p_off = 0, path_off = align_up((size_t)size * 4, 256), st2_off = align_up(path_off + npath * 16, 256);
-  const size_t pend_off = align_up(st2_off + npath * 4, 256);
-  if (ctx->org.ensure(pend_off + 16) != hipSuccess) return 0;  // (4 B per output byte: the in-order decode needs none)
-  uint8_t* ob = (uint8_t*)ctx->org.p;
-  uint32_t* d_P = (uint32_t*)(ob + p_off);
-  sm::OriginPath* d_path = (sm::OriginPath*)(ob + path_off);
-  int32_t* d_st2 = (int32_t*)(ob + st2_off);
-  uint32_t* d_pend = (uint32_t*)(ob + pend_off);
-  if (hipMemcpyAsync(d_path, op.data(), npath * sizeof(sm::OriginPath), hipMemcpyHostToDevice, s) != hipSuccess)
-    return -1;
-  if (sm::launch_origin_fill(d_in, n, size, d_path, (uint32_t)npath, d_P, d_st2, s) != hipSuccess) return -1;
+  const std::vector<sm::OriginPath> op = sm::origin_path(path, false);
+  if (ctx->org.ensure(sm::carve_origin(nullptr, size, npath).end) != hipSuccess) return kFallBack;  // (4 B per output byte: the in-order decode needs none)
+  const sm::OriginScratch og = sm::carve_origin(ctx->org.p, size, npath);
+  if (hipMemcpyAsync(og.path, op.data(), npath * sizeof(sm::OriginPath), hipMemcpyHostToDevice, s) != hipSuccess)
+    return kDeviceError;
+  if (sm::launch_origin_fill(d_in, n, size, og.path, (uint32_t)npath, og.P, og.st, s) != hipSuccess) return kDeviceError;
   std::vector<int32_t> st2(npath);
-  if (hipMemcpyAsync(st2.data(), d_st2, npath * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-  if (hipStreamSynchronize(s) != hipSuccess) return -1;
+  if (hipMemcpyAsync(st2.data(), og.st, npath * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return kDeviceError;
+  if (hipStreamSynchronize(s) != hipSuccess) return kDeviceError;
   for (int32_t v : st2)
-    if (v != sm::kOk) return path_first_error(ctx, n, size, path, err);
+    if (v != sm::kOk) return path_first_error(ctx, n, size, path);
   // round k moves every unresolved pointer >= 2^k chain steps: 32 rounds cover any size
   bool done = false;
   for (int round = 0; round < 32 && !done; ++round) {
     uint32_t pend = 0;
-    if (hipMemsetAsync(d_pend, 0, 4, s) != hipSuccess) return -1;
-    if (sm::launch_origin_resolve(d_P, size, d_pend, s) != hipSuccess) return -1;
-    if (hipMemcpyAsync(&pend, d_pend, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-    if (hipStreamSynchronize(s) != hipSuccess) return -1;
+    if (hipMemsetAsync(og.pend, 0, 4, s) != hipSuccess) return kDeviceError;
+    if (sm::launch_origin_resolve(og.P, size, og.pend, s) != hipSuccess) return kDeviceError;
+    if (hipMemcpyAsync(&pend, og.pend, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return kDeviceError;
+    if (hipStreamSynchronize(s) != hipSuccess) return kDeviceError;
     done = pend == 0;
   }
-  if (!done) return 0;
-  if (sm::launch_origin_gather(d_in, d_P, size, (uint8_t*)ctx->out.p, s) != hipSuccess) return -1;
+  if (!done) return kFallBack;
+  if (sm::launch_origin_gather(d_in, og.P, size, (uint8_t*)ctx->out.p, s) != hipSuccess) return kDeviceError;
   if (ctx->org.cap > kOrgKeep) {  // 4 B per output byte: do not keep gigabytes in the context
-    if (hipStreamSynchronize(s) != hipSuccess) return -1;
+    if (hipStreamSynchronize(s) != hipSuccess) return kDeviceError;
     ctx->org.release();
   }
-  return 2;
+  return {PathResult::kTaken, 2, SM_OK, true};
 }
 
 // A small stream entirely on the device (sm_decompress.hip, "a small stream"): index, chain,
-// origin pointers, resolve, gather, then one synchronisation with the output's download.
-// Returns 4 with the output in host_out, 0 to fall back (an error or anything unexpected: the
-// old paths find the reference's first error), -1 on a device error.
-#ifndef SM_SMALL_MIN
-#define SM_SMALL_MIN 4096
-#endif
-constexpr uint32_t kSmallMinOutput = SM_SMALL_MIN;  // smaller streams: the one-wave decode
-constexpr uint32_t kSmallMaxChunks = (1u << 20) / sm::kSmallChunk;  // compressed bodies up to 1 MiB
-// Index chunk size for path 4: 512-byte chunks halve the index and fill kernels' per-chunk walk
-// (both latency chains of 256-byte windows) but double the chain's elements and split more long
-// literals into deep entries.  Measured single calls (fast streams, r05): html (body 0.22 of the
-// output) 83 -> 70 us, alice29.txt (0.56) 82 -> 74, paper-100k.pdf (0.82, long literals) 145 ->
-// 184, urls.10K (0.48, 336 KB body) 150 -> 156.  So: fine chunks for bodies up to 0.6 of the
-// output and 256 KiB.
-#ifndef SM_SMALL_FINE_BODY10
-#define SM_SMALL_FINE_BODY10 6
-#endif
-#ifndef SM_SMALL_TINY_BODY
-#define SM_SMALL_TINY_BODY 16384  // bodies up to this size ...
-#endif
-#ifndef SM_SMALL_TINY_BODY10
-#define SM_SMALL_TINY_BODY10 9    // ... and at most this many tenths of the output: 128-byte chunks
-#endif
-// path 4's index chunk: 128 bytes for small bodies with copies (sample-tweet.json 52 -> 45 us, 4-16
-// KiB of text 51-56 -> 45-48 us), 512 for bodies of mostly copies, else 1024 (literal-rich
-// streams, where finer chunks lengthen the chain: paper-100k.pdf 137 -> 168 us at 512)
-uint32_t small_chunk(uint32_t body, uint32_t size) {
-  if (body <= SM_SMALL_TINY_BODY && (uint64_t)body * 10 <= (uint64_t)size * SM_SMALL_TINY_BODY10)
-    return sm::kSmallChunkTiny;
-  if ((uint64_t)body * 10 > (uint64_t)size * SM_SMALL_FINE_BODY10 || body > (256u << 10)) return sm::kSmallChunk;
-  return sm::kSmallChunkFine;
-}
-constexpr uint32_t kSmallMaxOutput = 64u << 20;    // 4 B of origin pointer per output byte
-constexpr uint32_t kPinnedOutMax = 16u << 20;      // outputs the last kernel writes into the pinned staging
-
-// comp: the call's input on the host.  It goes to the device through the index launch (the pinned
-// staging read there, the device copy written there); 0 returns before any launch leave
-// ctx->in without it.
-int small_uncompress(sm_ctx* ctx, const uint8_t* comp, uint32_t n, uint32_t ip0, uint32_t size, uint8_t* host_out) {
-  using sm::kIdxEntries;
-  const uint32_t chunk = small_chunk(n - ip0, size);
-  const uint32_t nchunks = (n - ip0 + chunk - 1) / chunk;
-  uint32_t rounds = 1;  // kSmallHops^rounds >= size: every chain (at most size steps) resolves
-  uint32_t hops = sm::kSmallHops;
-  if (size <= sm::kOneLaunchHops)
-    hops = std::max(hops, size);  // one launch of size hops (up to 256 KiB of output: one dispatch fewer)
-  else
-    for (uint64_t reach = sm::kSmallHops; reach < size; reach *= sm::kSmallHops) ++rounds;
-  const size_t path_off = align_up((size_t)nchunks * kIdxEntries * 8 + (size_t)nchunks * sm::kDeepChains * sm::kDeepLevels * 16, 256);  // records, deep records
-  const size_t ctl_off = align_up(path_off + (size_t)nchunks * sizeof(sm::OriginPath), 256);
-  const size_t ctl_n = 4 + rounds;
-  if (ctx->idx.ensure(ctl_off + ctl_n * 4) != hipSuccess) return 0;
-  if (ctx->org.ensure((size_t)size * 4) != hipSuccess) return 0;
+// origin pointers, resolve, gather, then one synchronisation with the output's download.  Path 4
+// with the output in host_out, or a fall back (an error or anything unexpected: the old paths
+// find the reference's first error).  comp: the call's input on the host.  It goes to the device
+// through the index launch (the pinned staging read there, the device copy written there); a fall
+// back before any launch leaves ctx->in without it.
+PathResult small_uncompress(sm_ctx* ctx, const uint8_t* comp, uint32_t n, uint32_t ip0, uint32_t size, uint8_t* host_out) {
+  const sm::SmallPlan pl = sm::small_plan(n - ip0, size);
+  if (ctx->idx.ensure(sm::carve_small(nullptr, pl.nchunks, pl.rounds).end) != hipSuccess) return kFallBack;
+  if (ctx->org.ensure((size_t)size * 4) != hipSuccess) return kFallBack;
   // the output and the verdict words straight into the pinned staging (a large output: the words
   // only, the output by a copy into host_out)
-  const bool pin_out = size <= kPinnedOutMax;
-  const size_t w_off = pin_out ? align_up(size, 256) : 0;
-  if (ctx->stage.ensure(w_off + 64) != hipSuccess || !ctx->stage.dp) return 0;
+  const bool pin_out = size <= sm::kPinnedOutMax;
+  PinnedResult res{ctx->stage};
+  if (!res.ensure(pin_out ? size : 0)) return kFallBack;
   hipStream_t s = ctx->stream;
-  uint8_t* ib = (uint8_t*)ctx->idx.p;
-  uint32_t* d_ctl = (uint32_t*)(ib + ctl_off);
-  uint8_t* const sdp = (uint8_t*)ctx->stage.dp;
-  if (!stage_in_acquire(ctx, n)) return 0;
-  memcpy(ctx->stage_in.p, comp, n);
-  // the third verdict word is written by the device only when a pointer stays unresolved
-  ((volatile uint32_t*)((uint8_t*)ctx->stage.p + w_off))[2] = 0;
-  const hipError_t le = sm::launch_small_decode((const uint8_t*)ctx->in.p, (const uint8_t*)ctx->stage_in.dp, n, ip0,
-                                                size, chunk, nchunks, (uint32_t*)ib, (sm::OriginPath*)(ib + path_off),
-                                                d_ctl, (uint32_t*)ctx->org.p, rounds, hops,
-                                                pin_out ? sdp : (uint8_t*)ctx->out.p, (uint32_t*)(sdp + w_off), s);
-  if (le != hipSuccess || stage_in_release(ctx, s) != hipSuccess) {
-    (void)hipStreamSynchronize(s);  // (no launch may still read the staging when the call returns)
-    return -1;
-  }
-  if (!pin_out && hipMemcpyAsync(host_out, ctx->out.p, size, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-  if (hipStreamSynchronize(s) != hipSuccess) return -1;
-  const volatile uint32_t* w = (const volatile uint32_t*)((uint8_t*)ctx->stage.p + w_off);
-  if (w[0] || w[1] || w[2]) return 0;  // (w[2]: never, by the round count -- checked, not assumed)
-  if (pin_out) memcpy(host_out, ctx->stage.p, size);
-  return 4;
+  const sm::SmallScratch sc = sm::carve_small(ctx->idx.p, pl.nchunks, pl.rounds);
+  StagedInput in(ctx, s);
+  if (!in.acquire(comp, n)) return kFallBack;
+  volatile uint32_t* const w = res.words();
+  w[2] = 0;  // the third verdict word is written by the device only when a pointer stays unresolved
+  if (in.finish(sm::launch_small_decode((const uint8_t*)ctx->in.p, in.dp, n, ip0, size, pl.chunk, pl.nchunks, sc.rec,
+                                        sc.path, sc.ctl, (uint32_t*)ctx->org.p, pl.rounds, pl.hops,
+                                        pin_out ? res.d_bytes() : (uint8_t*)ctx->out.p, res.d_words(), s)) != hipSuccess)
+    return kDeviceError;
+  if (!pin_out && hipMemcpyAsync(host_out, ctx->out.p, size, hipMemcpyDeviceToHost, s) != hipSuccess) return kDeviceError;
+  if (hipStreamSynchronize(s) != hipSuccess) return kDeviceError;
+  if (w[0] || w[1] || w[2]) return kFallBack;  // (w[2]: never, by the round count -- checked, not assumed)
+  if (pin_out) memcpy(host_out, res.bytes(), size);
+  return {PathResult::kTaken, 4};
 }
 
-}  // namespace
-
-namespace {
-// Shard [b0, b1) of a host batch, rebased so the single-context call copies only the shard's
-// bytes: offsets relative to the shard's lowest input / output offset.
-struct Shard {
-  uint32_t b0 = 0, n = 0;
-  uint64_t in_base = 0, out_base = 0;
-  std::vector<uint64_t> in_off, out_off;
-};
-
-std::vector<Shard> make_shards(int nctx, uint32_t nblk, const uint64_t* in_off, const uint64_t* out_off) {
-  std::vector<Shard> sh((size_t)nctx);
-  for (int i = 0; i < nctx; ++i) {
-    Shard& s = sh[(size_t)i];
-    s.b0 = (uint32_t)((uint64_t)nblk * (uint64_t)i / (uint64_t)nctx);
-    s.n = (uint32_t)((uint64_t)nblk * (uint64_t)(i + 1) / (uint64_t)nctx) - s.b0;
-    if (s.n == 0) continue;
-    s.in_base = *std::min_element(in_off + s.b0, in_off + s.b0 + s.n);
-    s.out_base = *std::min_element(out_off + s.b0, out_off + s.b0 + s.n);
-    s.in_off.resize(s.n);
-    s.out_off.resize(s.n);
-    for (uint32_t k = 0; k < s.n; ++k) {
-      s.in_off[k] = in_off[s.b0 + k] - s.in_base;
-      s.out_off[k] = out_off[s.b0 + k] - s.out_base;
-    }
-  }
-  return sh;
-}
+using sm::Shard;
 
 template <typename F>
 sm_status run_shards(int nctx, F&& shard_fn) {
@@ -605,14 +447,23 @@ sm_status gather_to_host(sm_ctx* ctx, const uint8_t* d_src, const uint64_t* d_sr
   return SM_OK;
 }
 
-// The compressor's lengths as the host receives them: a length above the block's bound is an
-// error mark (SM_OUT_LEN_ERROR | k: a bounded wait inside the kernel gave up; 0xffffffff: a block
-// over 64 KiB, rejected before the launch here).  Checked before any length is summed, allocated
-// or gathered, so a mark never becomes a copy size.
-sm_status check_compressed_lengths(const uint32_t* out_len, const uint32_t* in_len, uint32_t nblk) {
-  for (uint32_t b = 0; b < nblk; ++b)
-    if (out_len[b] > sm::max_compressed_length(in_len[b])) return out_len[b] >= SM_OUT_LEN_ERROR ? SM_ERR_DEVICE : SM_ERR_ARGUMENT;
-  return SM_OK;
+// A host batch on its way up: ctx->in, ctx->out and the tables *t in ctx->meta made large enough,
+// then the input and the caller's tables copied (out_cap: the decode's; null for compress).
+hipError_t upload_batch(sm_ctx* ctx, const uint8_t* in, size_t in_total, size_t out_total, const uint64_t* in_off,
+                        const uint64_t* out_off, const uint32_t* in_len, const uint32_t* out_cap, uint32_t nblk,
+                        sm::BatchTables* t) {
+  hipStream_t s = ctx->stream;
+  hipError_t e = ctx->in.ensure(in_total + 16);
+  if (e == hipSuccess) e = ctx->out.ensure(out_total + 16);
+  if (e == hipSuccess) e = ctx->meta.ensure(sm::carve_batch(nullptr, nblk, out_cap != nullptr).end);
+  if (e != hipSuccess) return e;
+  *t = sm::carve_batch(ctx->meta.p, nblk, out_cap != nullptr);
+  e = hipMemcpyAsync(ctx->in.p, in, in_total, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(t->in_off, in_off, 8 * (size_t)nblk, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(t->out_off, out_off, 8 * (size_t)nblk, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(t->in_len, in_len, 4 * (size_t)nblk, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && out_cap) e = hipMemcpyAsync(t->out_cap, out_cap, 4 * (size_t)nblk, hipMemcpyHostToDevice, s);
+  return e;
 }
 
 bool valid_ctxs(sm_ctx* const* ctxs, int nctx) {
@@ -665,41 +516,13 @@ const char* sm_status_message(sm_status st) {
 
 const char* sm_version(void) { return "snappy_mi355x gfx950 " SM_VERSION_STR; }
 
-size_t sm_max_compressed_length(size_t n) { return 32 + n + n / 6; }
+size_t sm_max_compressed_length(size_t n) { return smc::max_compressed_length(n); }
 
 sm_status sm_parse32(const uint8_t* buf, size_t len, size_t off, uint32_t* value, size_t* next) {
-  uint32_t result = 0;
-  for (int i = 0; i < 5; ++i) {
-    if (off + i >= len) return SM_ERR_VARINT;
-    uint32_t b = buf[off + i];
-    if (i < 4) {
-      result |= (b & 0x7f) << (7 * i);
-      if (b < 0x80) {
-        if (value) *value = result;
-        if (next) *next = off + i + 1;
-        return SM_OK;
-      }
-    } else {
-      result |= (b & 0x7f) << 28;
-      if (b < 0x10) {
-        if (value) *value = result;
-        if (next) *next = off + 5;
-        return SM_OK;
-      }
-    }
-  }
-  return SM_ERR_VARINT;
+  return sm::parse32(buf, len, off, value, next);
 }
 
-size_t sm_encode32(uint8_t* buf, uint32_t v) {
-  size_t i = 0;
-  while (v >= 0x80) {
-    buf[i++] = (uint8_t)(v | 0x80);
-    v >>= 7;
-  }
-  buf[i++] = (uint8_t)v;
-  return i;
-}
+size_t sm_encode32(uint8_t* buf, uint32_t v) { return sm::encode32(buf, v); }
 
 sm_status sm_find_match_length(const uint8_t* buf, size_t len, size_t i1, size_t i2, size_t limit,
                                size_t* matched) {
@@ -917,28 +740,16 @@ sm_status sm_compress_batch(sm_ctx* ctx, const uint8_t* in, const uint64_t* in_o
   std::lock_guard<std::mutex> lk(ctx->mu);
   DeviceGuard g(ctx->device);
   hipStream_t s = ctx->stream;
-  size_t meta_bytes = (size_t)nblk * (8 + 4 + 8 + 4);
-  SM_CHECK(ctx->in.ensure(in_total + 16));
-  SM_CHECK(ctx->out.ensure(out_total + 16));
-  SM_CHECK(ctx->meta.ensure(meta_bytes + 64));
-  uint8_t* m = (uint8_t*)ctx->meta.p;
-  uint64_t* d_in_off = (uint64_t*)m;
-  uint64_t* d_out_off = (uint64_t*)(m + 8 * (size_t)nblk);
-  uint32_t* d_in_len = (uint32_t*)(m + 16 * (size_t)nblk);
-  uint32_t* d_out_len = (uint32_t*)(m + 20 * (size_t)nblk);
-  SM_CHECK(hipMemcpyAsync(ctx->in.p, in, in_total, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d_in_off, in_off, 8 * (size_t)nblk, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d_out_off, out_off, 8 * (size_t)nblk, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d_in_len, in_len, 4 * (size_t)nblk, hipMemcpyHostToDevice, s));
-  sm::CompressArgs a{(const uint8_t*)ctx->in.p, d_in_off, d_in_len, (uint8_t*)ctx->out.p, d_out_off, d_out_len,
+  sm::BatchTables t;
+  SM_CHECK(upload_batch(ctx, in, in_total, out_total, in_off, out_off, in_len, nullptr, nblk, &t));
+  sm::CompressArgs a{(const uint8_t*)ctx->in.p, t.in_off, t.in_len, (uint8_t*)ctx->out.p, t.out_off, t.out_len,
                      nblk, 0, 1};
   SM_CHECK(sm::launch_compress(a, mode, s));
-  SM_CHECK(hipMemcpyAsync(out_len, d_out_len, 4 * (size_t)nblk, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(out_len, t.out_len, 4 * (size_t)nblk, hipMemcpyDeviceToHost, s));
   SM_CHECK(hipStreamSynchronize(s));
-  const sm_status lst = check_compressed_lengths(out_len, in_len, nblk);
-  if (lst != SM_OK) return lst;
+  SM_PASS(sm::check_compressed_lengths(out_len, in_len, nblk));
   // copy back only each block's bytes
-  return gather_to_host(ctx, (const uint8_t*)ctx->out.p, d_out_off, d_out_len, out_len, nblk, out_off, out);
+  return gather_to_host(ctx, (const uint8_t*)ctx->out.p, t.out_off, t.out_len, out_len, nblk, out_off, out);
 }
 
 sm_status sm_uncompress_batch(sm_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
@@ -957,31 +768,17 @@ sm_status sm_uncompress_batch(sm_ctx* ctx, const uint8_t* in, const uint64_t* in
   std::lock_guard<std::mutex> lk(ctx->mu);
   DeviceGuard g(ctx->device);
   hipStream_t s = ctx->stream;
-  size_t meta_bytes = (size_t)nblk * (8 + 8 + 4 + 4 + 4 + 4);
-  SM_CHECK(ctx->in.ensure(in_total + 16));
-  SM_CHECK(ctx->out.ensure(out_total + 16));
-  SM_CHECK(ctx->meta.ensure(meta_bytes + 64));
-  uint8_t* m = (uint8_t*)ctx->meta.p;
-  uint64_t* d_in_off = (uint64_t*)m;
-  uint64_t* d_out_off = (uint64_t*)(m + 8 * (size_t)nblk);
-  uint32_t* d_in_len = (uint32_t*)(m + 16 * (size_t)nblk);
-  uint32_t* d_out_cap = (uint32_t*)(m + 20 * (size_t)nblk);
-  uint32_t* d_out_len = (uint32_t*)(m + 24 * (size_t)nblk);
-  int32_t* d_status = (int32_t*)(m + 28 * (size_t)nblk);
-  SM_CHECK(hipMemcpyAsync(ctx->in.p, in, in_total, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d_in_off, in_off, 8 * (size_t)nblk, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d_out_off, out_off, 8 * (size_t)nblk, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d_in_len, in_len, 4 * (size_t)nblk, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d_out_cap, out_cap, 4 * (size_t)nblk, hipMemcpyHostToDevice, s));
-  sm::DecompressArgs a{(const uint8_t*)ctx->in.p, d_in_off, d_in_len, (uint8_t*)ctx->out.p, d_out_off,
-                       d_out_cap, d_out_len, d_status, nblk};
+  sm::BatchTables t;
+  SM_CHECK(upload_batch(ctx, in, in_total, out_total, in_off, out_off, in_len, out_cap, nblk, &t));
+  sm::DecompressArgs a{(const uint8_t*)ctx->in.p, t.in_off, t.in_len, (uint8_t*)ctx->out.p, t.out_off,
+                       t.out_cap, t.out_len, t.status, nblk};
   SM_CHECK(sm::launch_decompress(a, 0, s));
-  SM_CHECK(hipMemcpyAsync(out_len, d_out_len, 4 * (size_t)nblk, hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipMemcpyAsync(status, d_status, 4 * (size_t)nblk, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(out_len, t.out_len, 4 * (size_t)nblk, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(status, t.status, 4 * (size_t)nblk, hipMemcpyDeviceToHost, s));
   SM_CHECK(hipStreamSynchronize(s));
   for (uint32_t b = 0; b < nblk; ++b)
     if (status[b] != SM_OK) out_len[b] = 0;  // (the kernel already reports 0 for failed blocks)
-  return gather_to_host(ctx, (const uint8_t*)ctx->out.p, d_out_off, d_out_len, out_len, nblk, out_off, out);
+  return gather_to_host(ctx, (const uint8_t*)ctx->out.p, t.out_off, t.out_len, out_len, nblk, out_off, out);
 }
 
 sm_status sm_validate_batch_device(sm_ctx* ctx, const uint8_t* d_in, const uint64_t* d_in_off,
@@ -1013,7 +810,7 @@ sm_status sm_compress_batch_sharded(sm_ctx* const* ctxs, int nctx, const uint8_t
   if (!in || !in_off || !in_len || !out || !out_off || !out_len) return SM_ERR_ARGUMENT;
   for (uint32_t b = 0; b < nblk; ++b)
     if (in_len[b] > SM_BLOCK_SIZE) return SM_ERR_ARGUMENT;
-  const std::vector<Shard> sh = make_shards(nctx, nblk, in_off, out_off);
+  const std::vector<Shard> sh = sm::make_shards(nctx, nblk, in_off, out_off);
   return run_shards(nctx, [&](int i) -> sm_status {
     const Shard& s = sh[(size_t)i];
     if (s.n == 0) return SM_OK;
@@ -1028,7 +825,7 @@ sm_status sm_uncompress_batch_sharded(sm_ctx* const* ctxs, int nctx, const uint8
   if (!valid_ctxs(ctxs, nctx)) return SM_ERR_ARGUMENT;
   if (nblk == 0) return SM_OK;
   if (!in || !in_off || !in_len || !out || !out_off || !out_cap || !out_len || !status) return SM_ERR_ARGUMENT;
-  const std::vector<Shard> sh = make_shards(nctx, nblk, in_off, out_off);
+  const std::vector<Shard> sh = sm::make_shards(nctx, nblk, in_off, out_off);
   return run_shards(nctx, [&](int i) -> sm_status {
     const Shard& s = sh[(size_t)i];
     if (s.n == 0) return SM_OK;
@@ -1044,19 +841,16 @@ sm_status sm_validate_compressed_buffer(sm_ctx* ctx, const char* compressed, siz
   DeviceGuard g(ctx->device);
   hipStream_t s = ctx->stream;
   SM_CHECK(ctx->in.ensure(n + 16));
-  SM_CHECK(ctx->meta.ensure(64));
-  uint8_t* m = (uint8_t*)ctx->meta.p;
-  uint64_t* d_off = (uint64_t*)m;
-  uint32_t* d_len = (uint32_t*)(m + 8);
-  int32_t* d_status = (int32_t*)(m + 12);
+  SM_CHECK(ctx->meta.ensure(sm::carve_single(nullptr).end));
+  const sm::SingleMeta m = sm::carve_single(ctx->meta.p);
   const uint64_t zero = 0;
   const uint32_t len32 = (uint32_t)n;
   int32_t st = SM_ERR_DEVICE;
   SM_CHECK(upload_input(ctx, compressed, n, s));
-  SM_CHECK(hipMemcpyAsync(d_off, &zero, 8, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d_len, &len32, 4, hipMemcpyHostToDevice, s));
-  SM_CHECK(sm::launch_validate((const uint8_t*)ctx->in.p, d_off, d_len, 1, d_status, s));
-  SM_CHECK(hipMemcpyAsync(&st, d_status, 4, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(m.off, &zero, 8, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(m.in_len, &len32, 4, hipMemcpyHostToDevice, s));
+  if (sm::launch_validate((const uint8_t*)ctx->in.p, m.off, m.in_len, 1, m.status, s) != hipSuccess) return device_failure(s);
+  SM_CHECK(hipMemcpyAsync(&st, m.status, 4, hipMemcpyDeviceToHost, s));
   SM_CHECK(hipStreamSynchronize(s));
   return st;
 }
@@ -1078,7 +872,7 @@ sm_status sm_compress(sm_ctx* ctx, const char* input, size_t n, char* compressed
     return SM_OK;
   }
   const uint32_t nfrag = (uint32_t)((n + SM_BLOCK_SIZE - 1) / SM_BLOCK_SIZE);
-  const size_t slot = align_up(sm_max_compressed_length(SM_BLOCK_SIZE) + 8, 256);
+  const size_t slot = smc::kMultiSlotPitch;  // a fragment's bound + 8, rounded up to 256
   std::vector<uint64_t> in_off(nfrag), out_off(nfrag), dst_off(nfrag);
   std::vector<uint32_t> in_len(nfrag), out_len(nfrag);
   for (uint32_t i = 0; i < nfrag; ++i) {
@@ -1094,81 +888,67 @@ sm_status sm_compress(sm_ctx* ctx, const char* input, size_t n, char* compressed
   SM_CHECK(ctx->in.ensure(n + 16));
   SM_CHECK(ctx->out.ensure((size_t)nfrag * slot));
   SM_CHECK(ctx->out2.ensure(sm_max_compressed_length(n) + 16));
-  SM_CHECK(ctx->meta.ensure((size_t)nfrag * 32 + 64 + 4 * 256));
-  uint8_t* m = (uint8_t*)ctx->meta.p;
-  uint64_t* d_in_off = (uint64_t*)m;
-  uint64_t* d_out_off = (uint64_t*)(m + 8 * (size_t)nfrag);
-  uint64_t* d_dst_off = (uint64_t*)(m + 16 * (size_t)nfrag);
-  uint32_t* d_in_len = (uint32_t*)(m + 24 * (size_t)nfrag);
-  uint32_t* d_out_len = (uint32_t*)(m + 28 * (size_t)nfrag);
-  uint32_t* d_part_len = (uint32_t*)(m + 32 * (size_t)nfrag + 64);
+  SM_CHECK(ctx->meta.ensure(sm::carve_frags(nullptr, nfrag).end));
+  const sm::FragTables t = sm::carve_frags(ctx->meta.p, nfrag);
   HT_DECL
   // Small inputs: one synchronisation -- the fragment table and the gather (with the lengths'
   // prefix sums) on the device; the gather kernel writes the stream body into the context's
   // pinned staging (device-mapped: no copy engine behind the kernels), copied out on the host.
   // The fast modes parse each fragment in parts on their own workgroups (k_compress_sc_span: the
   // same bytes, a fraction of one block's latency; up to 256 parts in all, one per CU).
-  const size_t t_off = align_up(sm_max_compressed_length(n) + 16, 256);
-  if (n <= kSmallCompressMax && ctx->stage.ensure(t_off + 16) == hipSuccess && ctx->stage.dp) {
+  PinnedResult res{ctx->stage};  // the body, then (length, error) as two 64-bit words
+  if (n <= kSmallCompressMax && res.ensure(sm_max_compressed_length(n) + 16, 16)) {
     uint32_t parts = 1;
     if (mode != SM_MODE_REFERENCE && ctx->split) {
       uint32_t p2 = 1;
       while (p2 < nfrag) p2 <<= 1;
-      parts = std::min<uint32_t>(sm::kWave, 256 / p2);  // nfrag * parts <= 256 gather units
+      parts = std::min<uint32_t>(sm::kWave, sm::kMaxParts / p2);  // nfrag * parts <= 256 gather units
     }
     const uint32_t span = (uint32_t)((SM_BLOCK_SIZE / 1024 + parts - 1) / parts);
     const size_t sl = parts > 1 ? std::max<size_t>(slot, (size_t)parts * span * sm::kSpanSlot) : slot;
     SM_CHECK(ctx->out.ensure((size_t)nfrag * sl));
-    sm::CompressArgs a{(const uint8_t*)ctx->in.p, d_in_off, d_in_len, (uint8_t*)ctx->out.p, d_out_off, d_out_len,
+    sm::CompressArgs a{(const uint8_t*)ctx->in.p, t.in_off, t.in_len, (uint8_t*)ctx->out.p, t.out_off, t.out_len,
                        nfrag, sm::hashtable_size(n), 0};
     // fast modes: the screen (the first kernel) reads the input from the pinned staging and leaves
     // the device copy the parse reads -- no separate upload
-    const bool staged = mode != SM_MODE_REFERENCE && stage_in_acquire(ctx, n);
-    if (staged) {
-      memcpy(ctx->stage_in.p, input, n);
-      a.in_host = (const uint8_t*)ctx->stage_in.dp;
+    StagedInput in(ctx, s);
+    if (mode != SM_MODE_REFERENCE && in.acquire(input, n)) {
+      a.in_host = in.dp;
     } else {
       SM_CHECK(upload_input(ctx, input, n, s));
     }
     if (mode == SM_MODE_REFERENCE) {
-      SM_CHECK(sm::launch_frag_plan(n, nfrag, sl, d_in_off, d_in_len, d_out_off, s));
+      SM_CHECK(sm::launch_frag_plan(n, nfrag, sl, t.in_off, t.in_len, t.out_off, s));
     } else {  // (the screen, the fast modes' first kernel, writes the fragment table)
       a.plan_n = n;
       a.plan_slot = sl;
     }
     // the gather writes the body and its (length, error) pair straight into the pinned staging
-    uint8_t* const sdp = (uint8_t*)ctx->stage.dp;
-    const sm::ScSpan sp{parts, span, (uint64_t)span * sm::kSpanSlot, d_part_len};
+    const sm::ScSpan sp{parts, span, (uint64_t)span * sm::kSpanSlot, t.part_len};
     hipError_t le = parts > 1 ? sm::launch_compress_span(a, mode, sp, s) : sm::launch_compress(a, mode, s);
     if (le == hipSuccess)
-      le = parts > 1 ? sm::launch_parts_gather((const uint8_t*)ctx->out.p, d_out_off, sp, (const uint8_t*)ctx->in.p,
-                                               d_in_off, d_in_len, nfrag, (uint64_t*)(sdp + t_off), sdp, s)
-                     : sm::launch_frag_gather((const uint8_t*)ctx->out.p, d_out_off, d_out_len, d_in_len, nfrag,
-                                              (uint64_t*)(sdp + t_off), sdp, s);
-    // the staging's release after the last launch (an event between the launches costs each call
-    // ~4 us), and recorded even when a launch failed: the screen, its only reader, may be queued
-    if (staged) {
-      const hipError_t re = stage_in_release(ctx, s);
-      if (le == hipSuccess) le = re;
-    }
-    if (le != hipSuccess) {
-      (void)hipStreamSynchronize(s);
-      return SM_ERR_DEVICE;
-    }
+      le = parts > 1 ? sm::launch_parts_gather((const uint8_t*)ctx->out.p, t.out_off, sp, (const uint8_t*)ctx->in.p,
+                                               t.in_off, t.in_len, nfrag, res.d_words<uint64_t>(), res.d_bytes(), s)
+                     : sm::launch_frag_gather((const uint8_t*)ctx->out.p, t.out_off, t.out_len, t.in_len, nfrag,
+                                              res.d_words<uint64_t>(), res.d_bytes(), s);
+    // the staging's release behind the last launch; a failed launch synchronises instead (the
+    // screen, the staging's only reader, may be queued)
+    if (in.dp) le = in.finish(le);
+    if (le != hipSuccess) return device_failure(s);
     SM_CHECK(hipStreamSynchronize(s));
     HT("compress (small): all")
-    const volatile uint64_t* tot = (const volatile uint64_t*)((uint8_t*)ctx->stage.p + t_off);
+    const volatile uint64_t* tot = res.words<uint64_t>();
     const uint64_t len = tot[0];
     if (tot[1]) return SM_ERR_DEVICE;  // a block's error mark (SM_OUT_LEN_ERROR), never expected
     if (hl + len > *compressed_length) return SM_BUFFER_TOO_SMALL;
-    memcpy(compressed + hl, ctx->stage.p, len);
+    memcpy(compressed + hl, res.bytes(), len);
     *compressed_length = hl + len;
     ctx->last_split = parts > 1;
     return SM_OK;
   }
-  SM_CHECK(hipMemcpyAsync(d_in_off, in_off.data(), 8 * (size_t)nfrag, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d_out_off, out_off.data(), 8 * (size_t)nfrag, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d_in_len, in_len.data(), 4 * (size_t)nfrag, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(t.in_off, in_off.data(), 8 * (size_t)nfrag, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(t.out_off, out_off.data(), 8 * (size_t)nfrag, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(t.in_len, in_len.data(), 4 * (size_t)nfrag, hipMemcpyHostToDevice, s));
   // Large inputs go up in pieces on the copy stream, and each piece's fragments compress as
   // soon as it lands, so the kernels run under the rest of the upload.
   uint32_t npiece = n >= kPipeMinInput ? (nfrag + kPieceFrags - 1) / kPieceFrags : 1;
@@ -1183,26 +963,23 @@ sm_status sm_compress(sm_ctx* ctx, const char* input, size_t n, char* compressed
       SM_CHECK(hipEventRecord(ctx->ev[pc], ctx->copy));
       SM_CHECK(hipStreamWaitEvent(s, ctx->ev[pc], 0));
     }
-    sm::CompressArgs a{(const uint8_t*)ctx->in.p, d_in_off + f0, d_in_len + f0, (uint8_t*)ctx->out.p,
-                       d_out_off + f0, d_out_len + f0, f1 - f0, sm::hashtable_size(n), 0};
+    sm::CompressArgs a{(const uint8_t*)ctx->in.p, t.in_off + f0, t.in_len + f0, (uint8_t*)ctx->out.p,
+                       t.out_off + f0, t.out_len + f0, f1 - f0, sm::hashtable_size(n), 0};
     SM_CHECK(sm::launch_compress(a, mode, s));
   }
   HT("compress: H2D input + kernels")
-  SM_CHECK(hipMemcpyAsync(out_len.data(), d_out_len, 4 * (size_t)nfrag, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(out_len.data(), t.out_len, 4 * (size_t)nfrag, hipMemcpyDeviceToHost, s));
   SM_CHECK(hipStreamSynchronize(s));
   HT("compress: kernels + lengths")
-  {
-    const sm_status lst = check_compressed_lengths(out_len.data(), in_len.data(), nfrag);
-    if (lst != SM_OK) return lst;
-  }
+  SM_PASS(sm::check_compressed_lengths(out_len.data(), in_len.data(), nfrag));
   size_t total = 0;
   for (uint32_t i = 0; i < nfrag; ++i) {
     dst_off[i] = total;
     total += out_len[i];
   }
   if (hl + total > *compressed_length) return SM_BUFFER_TOO_SMALL;
-  SM_CHECK(hipMemcpyAsync(d_dst_off, dst_off.data(), 8 * (size_t)nfrag, hipMemcpyHostToDevice, s));
-  SM_CHECK(sm::launch_gather((const uint8_t*)ctx->out.p, d_out_off, d_out_len, d_dst_off, (uint8_t*)ctx->out2.p,
+  SM_CHECK(hipMemcpyAsync(t.dst_off, dst_off.data(), 8 * (size_t)nfrag, hipMemcpyHostToDevice, s));
+  SM_CHECK(sm::launch_gather((const uint8_t*)ctx->out.p, t.out_off, t.out_len, t.dst_off, (uint8_t*)ctx->out2.p,
                              nfrag, s));
   HT("compress: gather")
   SM_CHECK(hipMemcpyAsync(compressed + hl, ctx->out2.p, total, hipMemcpyDeviceToHost, s));
@@ -1228,99 +1005,65 @@ sm_status sm_uncompress(sm_ctx* ctx, const char* compressed, size_t n, char* unc
   hipStream_t s = ctx->stream;
   SM_CHECK(ctx->in.ensure(n + 16));
   SM_CHECK(ctx->out.ensure((size_t)size + 16));
-  SM_CHECK(ctx->meta.ensure(64));
-  uint8_t* m = (uint8_t*)ctx->meta.p;
-  uint64_t* d_off = (uint64_t*)m;           // in_off = out_off = 0
-  uint32_t* d_in_len = (uint32_t*)(m + 8);
-  uint32_t* d_cap = (uint32_t*)(m + 12);
-  uint32_t* d_out_len = (uint32_t*)(m + 16);
-  int32_t* d_status = (int32_t*)(m + 20);
-  uint32_t hv[2] = {(uint32_t)n, size};
+  SM_CHECK(ctx->meta.ensure(sm::carve_single(nullptr).end));
+  const sm::SingleMeta m = sm::carve_single(ctx->meta.p);
   HT_DECL
   size_t hdr = 0;
   (void)sm_parse32((const uint8_t*)compressed, n, 0, &size, &hdr);
-  // path 5: literal tags only (an incompressible input) -- one copy kernel from the pinned input
-  // staging to the pinned output staging, one synchronisation
-  {
-    sm::LitSpans ls;
-    if (ctx->small && size <= kPinnedOutMax && n <= kPinnedInMax && literal_only((const uint8_t*)compressed, n, hdr, size, ls)) {
-      const int r = literal_uncompress(ctx, (const uint8_t*)compressed, n, size, ls, (uint8_t*)uncompressed);
-      if (r < 0) return SM_ERR_DEVICE;
-      if (r == 1) {
-        ctx->last_path = 5;
-        *uncompressed_length = size;
-        return SM_OK;
-      }
-    }
+  const uint8_t* const comp = (const uint8_t*)compressed;
+  uint8_t* const host_out = (uint8_t*)uncompressed;
+  // The paths in turn, each falling back to the next.  Path 5: literal tags only (an
+  // incompressible input) -- one copy kernel from the pinned input staging to the pinned output
+  // staging, one synchronisation.  Path 4: a small stream entirely on the device.  Then a large
+  // stream's fragments in parallel when it is block-structured (Snappy.jl, libsnappy and this
+  // library all write such streams); otherwise, or on any error, the in-order decode (path 0).
+  PathResult r = kFallBack;
+  sm::LitSpans ls;
+  if (ctx->small && size <= sm::kPinnedOutMax && n <= sm::kPinnedInMax && sm::literal_only(comp, n, hdr, size, ls))
+    r = literal_uncompress(ctx, comp, n, size, ls, host_out);
+  if (r.kind == PathResult::kFallBack && ctx->small && sm::small_candidate(n, hdr, size))
+    r = small_uncompress(ctx, comp, (uint32_t)n, (uint32_t)hdr, size, host_out);
+  if (r.kind == PathResult::kFallBack) {
+    // (path 4 uploads through its index launch; every other path from here)
+    SM_CHECK(upload_input(ctx, compressed, n, s));
+    HT("uncompress: H2D input")
+    if (sm::parallel_candidate(n, hdr, size)) r = parallel_uncompress(ctx, comp, (uint32_t)n, (uint32_t)hdr, size, host_out);
   }
-  // a large stream: fragments in parallel when it is block-structured (Snappy.jl, libsnappy
-  // and this library all write such streams); otherwise, or on any error, the in-order decode
-  // (a body longer than its output is all literals, which the in-order engine copies HBM to HBM at
-  // bandwidth: path 0 is faster there -- fireworks.jpeg 59 us against ~100; a body just under
-  // its output is random data with short copies sprinkled in, which path 0 walks in small batches
-  // of one wave: alice29.snappy's fast stream 573 us there, 114 us in path 4, so path 4 takes
-  // everything up to body == output; round 4's bound was 7/8)
-  if (ctx->small && size >= kSmallMinOutput && size <= kSmallMaxOutput && n > hdr &&
-      (uint64_t)(n - hdr) * 8 <= (uint64_t)size * SM_SMALL_BODY8 &&
-      (n - hdr + sm::kSmallChunk - 1) / sm::kSmallChunk <= kSmallMaxChunks) {
-    const int r = small_uncompress(ctx, (const uint8_t*)compressed, (uint32_t)n, (uint32_t)hdr, size,
-                                   (uint8_t*)uncompressed);
-    if (r < 0) return SM_ERR_DEVICE;
-    if (r == 4) {
-      ctx->last_path = 4;
-      *uncompressed_length = size;
-      return SM_OK;
+  if (r.kind == PathResult::kDeviceError) return device_failure(s);
+  ctx->last_path = r.path;  // (a fall back: 0, the in-order decode below)
+  if (r.kind == PathResult::kStreamError) return r.status;
+  if (r.kind == PathResult::kTaken) {
+    if (r.in_ctx_out) {
+      SM_CHECK(hipMemcpyAsync(uncompressed, ctx->out.p, size, hipMemcpyDeviceToHost, s));
+      SM_CHECK(hipStreamSynchronize(s));
     }
+    HT("uncompress: D2H output")
+    *uncompressed_length = size;
+    return SM_OK;
   }
-  // (path 4 uploads through its index launch; every other path from here)
-  SM_CHECK(upload_input(ctx, compressed, n, s));
-  HT("uncompress: H2D input")
-  if (size >= kParallelMinOutput && n - hdr >= 2 * sm::kIdxChunk) {
-    bool copied = false;
-    int32_t err = SM_OK;
-    const int r = parallel_uncompress(ctx, (const uint8_t*)compressed, (uint32_t)n, (uint32_t)hdr, size,
-                                      (uint8_t*)uncompressed, &copied, &err);
-    if (r < 0) return SM_ERR_DEVICE;
-    if (r == 3) {  // the stream's first error, found in parallel (the reference throws: no output)
-      ctx->last_path = 3;
-      return err;
-    }
-    if (r >= 1) {
-      ctx->last_path = r;
-      if (!copied) {
-        SM_CHECK(hipMemcpyAsync(uncompressed, ctx->out.p, size, hipMemcpyDeviceToHost, s));
-        SM_CHECK(hipStreamSynchronize(s));
-      }
-      HT("uncompress: D2H output")
-      *uncompressed_length = size;
-      return SM_OK;
-    }
-  }
-  ctx->last_path = 0;
-  sm::DecompressArgs a{(const uint8_t*)ctx->in.p, d_off, d_in_len, (uint8_t*)ctx->out.p, d_off, d_cap, d_out_len,
-                       d_status, 1};
-  a.one_n = hv[0];  // (n >= 1 here: the header parsed) -- the stream's length and capacity as arguments
-  a.one_cap = hv[1];
-  SM_CHECK(sm::launch_decompress(a, size > SM_BLOCK_SIZE, s));
+  sm::DecompressArgs a{(const uint8_t*)ctx->in.p, m.off, m.in_len, (uint8_t*)ctx->out.p, m.off, m.cap, m.out_len,
+                       m.status, 1};
+  a.one_n = (uint32_t)n;  // (n >= 1 here: the header parsed) -- the stream's length and capacity as arguments
+  a.one_cap = size;
+  if (sm::launch_decompress(a, size > SM_BLOCK_SIZE, s) != hipSuccess) return device_failure(s);
   // the output (whatever the status) and (out_len, status) into the pinned staging by a kernel
-  const size_t w_off = align_up(size, 256);
-  if (size <= kPinnedOutMax && ctx->stage.ensure(w_off + 64) == hipSuccess && ctx->stage.dp) {
-    uint8_t* const sdp = (uint8_t*)ctx->stage.dp;
-    SM_CHECK(sm::launch_to_host((const uint8_t*)ctx->out.p, size, sdp, d_out_len, 2, (uint32_t*)(sdp + w_off), s));
+  PinnedResult res{ctx->stage};
+  if (size <= sm::kPinnedOutMax && res.ensure(size)) {
+    SM_CHECK(sm::launch_to_host((const uint8_t*)ctx->out.p, size, res.d_bytes(), m.out_len, 2, res.d_words(), s));
     SM_CHECK(hipStreamSynchronize(s));
-    const volatile uint32_t* w = (const volatile uint32_t*)((uint8_t*)ctx->stage.p + w_off);
+    const volatile uint32_t* w = res.words();
     const uint32_t dlen = w[0];
     const int32_t dst = (int32_t)w[1];
     if (dst != SM_OK) return dst;
     if (dlen > size) return SM_ERR_DEVICE;  // (never: the kernel's bound)
-    if (dlen) memcpy(uncompressed, ctx->stage.p, dlen);  // (uncompressed may be NULL when dlen == 0)
+    if (dlen) memcpy(uncompressed, res.bytes(), dlen);  // (uncompressed may be NULL when dlen == 0)
     *uncompressed_length = dlen;
     return SM_OK;
   }
   int32_t dst = 0;
   uint32_t dlen = 0;
-  SM_CHECK(hipMemcpyAsync(&dst, d_status, 4, hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipMemcpyAsync(&dlen, d_out_len, 4, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(&dst, m.status, 4, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(&dlen, m.out_len, 4, hipMemcpyDeviceToHost, s));
   SM_CHECK(hipStreamSynchronize(s));
   if (dst != SM_OK) return dst;
   if (dlen) {

@@ -1,0 +1,522 @@
+// sm_host_check.cpp -- stand-alone driver of sm_host_rules.h (no device, no HIP): what the main
+// library's host side decides from bytes it does not trust, on heap buffers of exactly the
+// documented sizes, so that AddressSanitizer and UBSan (make host_check) see one byte of over-read.
+// Expected values come from the CPU oracle (oracle/snappy_oracle.c), from a byte-at-a-time tag
+// walker written here, or from the construction of the case -- never from the code under test.
+//   sm_host_check <text file of at least 150000 bytes>   (tests/golden/testdata/alice29.txt)
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <memory>
+#include <set>
+#include <vector>
+
+#include "../../oracle/snappy_oracle.h"
+#include "sm_host_rules.h"
+
+namespace {
+
+int failures = 0;
+
+#define EXPECT(cond)                                              \
+  do {                                                            \
+    if (!(cond)) {                                                \
+      ++failures;                                                 \
+      fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond);  \
+    }                                                             \
+  } while (0)
+
+typedef std::vector<uint8_t> Bytes;
+
+template <typename T>
+std::unique_ptr<T[]> exact(const std::vector<T>& v) {  // a heap array of exactly v.size() elements
+  std::unique_ptr<T[]> p(new T[v.size()]);
+  if (!v.empty()) memcpy(p.get(), v.data(), v.size() * sizeof(T));
+  return p;
+}
+
+void put_varint(Bytes& o, uint32_t v) {
+  while (v >= 0x80) {
+    o.push_back((uint8_t)(v | 0x80));
+    v >>= 7;
+  }
+  o.push_back((uint8_t)v);
+}
+
+// the header of a stream, parsed here: false when it is not a whole varint32
+bool header(const Bytes& s, uint32_t* size, size_t* hdr) {
+  uint64_t v = 0;
+  for (size_t i = 0; i < 5 && i < s.size(); ++i) {
+    v |= (uint64_t)(s[i] & 0x7f) << (7 * i);
+    if (s[i] < 0x80) {
+      *size = (uint32_t)v;
+      *hdr = i + 1;
+      return v <= 0xffffffffull;
+    }
+  }
+  return false;
+}
+
+uint8_t filler(size_t i) { return (uint8_t)(i * 131 + 7); }
+
+// a literal of len bytes with nb length bytes behind its tag (0: the length in the tag, len <= 60)
+void put_literal(Bytes& o, uint32_t len, uint32_t nb) {
+  if (nb == 0) {
+    o.push_back((uint8_t)((len - 1) << 2));
+  } else {
+    o.push_back((uint8_t)((59 + nb) << 2));
+    for (uint32_t k = 0; k < nb; ++k) o.push_back((uint8_t)((len - 1) >> (8 * k)));
+  }
+  for (uint32_t k = 0; k < len; ++k) o.push_back(filler(o.size()));
+}
+
+Bytes oracle_compress(const Bytes& in) {
+  Bytes out(smo_max_compressed_length(in.size()));
+  size_t n = out.size();
+  EXPECT(smo_compress(in.data(), in.size(), out.data(), &n, 0) == SMO_OK);
+  out.resize(n);
+  return out;
+}
+
+// ---- literal_only -----------------------------------------------------------------------------
+
+// Runs literal_only on an exact copy of s against the oracle's decode; returns whether it accepted.
+bool literal_case(const Bytes& s) {
+  uint32_t size = 0;
+  size_t hdr = 0;
+  if (!header(s, &size, &hdr)) return false;
+  const auto c = exact(s);
+  sm::LitSpans sp;
+  const bool ok = sm::literal_only(c.get(), s.size(), hdr, size, sp);
+  // (a tag makes at most 64 bytes of output: a larger declared length fails under any capacity)
+  Bytes out((size_t)std::min<uint64_t>(size, 64 * (uint64_t)s.size()) + 1);
+  size_t got = 0;
+  const int st = smo_uncompress(c.get(), s.size(), out.data(), out.size(), &got);
+  if (st != SMO_OK) EXPECT(!ok);
+  if (ok) {
+    EXPECT(st == SMO_OK && got == size);
+    EXPECT(sp.n >= 1 && sp.n <= sm::kLitSpans && sp.dst[0] == 0 && sp.dst[sp.n] == size);
+    Bytes cat;
+    for (uint32_t k = 0; k < sp.n && failures == 0; ++k) {
+      const uint32_t len = sp.dst[k + 1] - sp.dst[k];
+      EXPECT(sp.dst[k + 1] > sp.dst[k] && (size_t)sp.src[k] + len <= s.size());
+      if (failures == 0) cat.insert(cat.end(), s.begin() + sp.src[k], s.begin() + sp.src[k] + len);
+    }
+    EXPECT(st == SMO_OK && cat.size() == got && memcmp(cat.data(), out.data(), got) == 0);
+  }
+  return ok;
+}
+
+Bytes literal_stream(uint32_t declared, const std::vector<std::pair<uint32_t, uint32_t>>& lits) {
+  Bytes s;
+  put_varint(s, declared);
+  for (const auto& l : lits) put_literal(s, l.first, l.second);
+  return s;
+}
+
+void check_literal_only() {
+  for (uint32_t k = 1; k <= 17; ++k) {  // 1 to 16 literals; 17 must refuse
+    std::vector<std::pair<uint32_t, uint32_t>> lits(k, {5u, 0u});
+    EXPECT(literal_case(literal_stream(5 * k, lits)) == (k <= 16));
+  }
+  const uint32_t lens[5] = {60, 200, 300, 70000, 70000};
+  for (uint32_t nb = 0; nb <= 4; ++nb)  // 0 to 3 length bytes; 4 must refuse
+    EXPECT(literal_case(literal_stream(lens[nb] + 7, {{7u, 0u}, {lens[nb], nb}})) == (nb <= 3));
+  const std::vector<std::pair<uint32_t, uint32_t>> mixed = {{9u, 0u}, {100u, 1u}, {1000u, 2u}, {12u, 3u}};
+  const uint32_t sum = 9 + 100 + 1000 + 12;
+  const Bytes valid = literal_stream(sum, mixed);
+  EXPECT(literal_case(valid));
+  for (size_t at = 0; at <= mixed.size(); ++at) {  // a copy tag at every tag position
+    Bytes s;
+    put_varint(s, sum + 4);
+    for (size_t k = 0; k <= mixed.size(); ++k) {
+      if (k == at) {
+        s.push_back(0x01);  // copy, 1 offset byte: length 4
+        s.push_back(0x01);
+      }
+      if (k < mixed.size()) put_literal(s, mixed[k].first, mixed[k].second);
+    }
+    EXPECT(!literal_case(s));
+  }
+  for (size_t n = 0; n < valid.size(); ++n) EXPECT(!literal_case(Bytes(valid.begin(), valid.begin() + n)));  // every truncation
+  EXPECT(!literal_case(literal_stream(sum - 1, mixed)));
+  EXPECT(!literal_case(literal_stream(sum + 1, mixed)));
+  EXPECT(!literal_case(literal_stream(0, {})));  // an empty body
+  EXPECT(!literal_case(literal_stream(5, {})));
+  Bytes wrap;  // a length of 2^32 (q + len wraps at 32 bits), and the longest 3-byte length in a short stream
+  put_varint(wrap, 0xffffffffu);
+  wrap.insert(wrap.end(), {(uint8_t)(63 << 2), 0xff, 0xff, 0xff, 0xff, 1, 2, 3});
+  EXPECT(!literal_case(wrap));
+  Bytes big;
+  put_varint(big, 1u << 24);
+  big.insert(big.end(), {(uint8_t)(62 << 2), 0xff, 0xff, 0xff, 1, 2, 3});
+  EXPECT(!literal_case(big));
+}
+
+// ---- the tag walker of this check (byte at a time, bytes past n read as zero) ---------------------
+
+struct Walk {
+  uint64_t exit, out;
+};
+Walk ref_walk(const Bytes& s, uint64_t p, uint64_t lim, std::vector<uint64_t>* tags = nullptr,
+              std::vector<uint64_t>* before = nullptr) {  // tags: every tag start; before: the output before it
+  uint64_t o = 0;
+  while (p < lim) {
+    if (tags) tags->push_back(p);
+    if (before) before->push_back(o);
+    const uint32_t tag = s[p], kind = tag & 3, up = tag >> 2;
+    if (kind == 0) {
+      uint64_t len = up + 1, extra = 0;
+      if (up >= 60) {
+        extra = up - 59;
+        len = 1;
+        for (uint64_t k = 0; k < extra; ++k) len += (uint64_t)(p + 1 + k < s.size() ? s[p + 1 + k] : 0) << (8 * k);
+      }
+      p += 1 + extra + len;
+      o += len;
+    } else {
+      p += kind == 1 ? 2 : kind == 2 ? 3 : 5;
+      o += kind == 1 ? 4 + (up & 7) : up + 1;
+    }
+  }
+  return {p, o};
+}
+
+// literals with 2 and 3 length bytes and the three copy kinds (the walk reads no copy offset's meaning)
+Bytes hand_stream(uint32_t* declared) {
+  Bytes b;
+  put_literal(b, 300, 2);
+  b.insert(b.end(), {(uint8_t)(1 | (3 << 2)), 0x10});                     // copy 1: 7 bytes
+  put_literal(b, 70000, 3);
+  b.insert(b.end(), {(uint8_t)(2 | (39 << 2)), 0x00, 0x01});              // copy 2: 40 bytes
+  put_literal(b, 33, 0);
+  b.insert(b.end(), {(uint8_t)(3 | (63 << 2)), 0x00, 0x01, 0x00, 0x00});  // copy 4: 64 bytes
+  put_literal(b, 61, 1);
+  *declared = 300 + 7 + 70000 + 40 + 33 + 64 + 61;
+  Bytes s;
+  put_varint(s, *declared);
+  s.insert(s.end(), b.begin(), b.end());
+  return s;
+}
+
+void walk_case(const Bytes& s) {
+  uint32_t size = 0;
+  size_t hdr = 0;
+  EXPECT(header(s, &size, &hdr));
+  const uint32_t n = (uint32_t)s.size();
+  const auto c = exact(s);
+  std::vector<uint64_t> tags, before;
+  const Walk all = ref_walk(s, hdr, n, &tags, &before);
+  EXPECT(all.exit == n && all.out == size);  // (the case is a valid stream)
+  uint64_t ex = 0, out = 0;
+  sm::host_walk(c.get(), n, hdr, n, &ex, &out);
+  EXPECT(ex == n && out == size);
+  tags.push_back(n);
+  before.push_back(size);
+  for (size_t k = 0; k < tags.size(); ++k) {  // in two pieces split at every tag boundary
+    uint64_t e1, o1, e2, o2;
+    sm::host_walk(c.get(), n, hdr, tags[k], &e1, &o1);
+    sm::host_walk(c.get(), n, tags[k], n, &e2, &o2);
+    EXPECT(e1 == tags[k] && e2 == n && o1 + o2 == size && o1 == before[k]);
+  }
+  for (uint32_t k = 1; k <= 4 && k < n; ++k) {  // entering just before the end: nothing past n is read
+    sm::host_walk(c.get(), n, n - k, n, &ex, &out);
+    const Walk w = ref_walk(s, n - k, n);
+    EXPECT(ex == w.exit && out == w.out);
+  }
+}
+
+// ---- the true path and the fragment table ----------------------------------------------------------
+
+// the index records of s as the index kernel defines them, by the walker above
+std::vector<uint32_t> records(const Bytes& s, uint32_t ip0) {
+  const uint32_t n = (uint32_t)s.size(), nchunks = (n - ip0 + sm::kIdxChunk - 1) / sm::kIdxChunk;
+  std::vector<uint32_t> rec(2 * (size_t)nchunks * sm::kIdxEntries);
+  for (uint32_t c = 0; c < nchunks; ++c)
+    for (uint32_t l = 0; l < sm::kIdxEntries; ++l) {
+      const uint64_t base = ip0 + (uint64_t)c * sm::kIdxChunk, lim = std::min<uint64_t>(base + sm::kIdxChunk, (uint64_t)n - 1);
+      const Walk w = ref_walk(s, base + l, lim);
+      rec[2 * ((size_t)c * sm::kIdxEntries + l)] = (uint32_t)w.exit;
+      rec[2 * ((size_t)c * sm::kIdxEntries + l) + 1] = (uint32_t)w.out;
+    }
+  return rec;
+}
+
+struct PathRun {
+  sm::PathEnd end;
+  std::vector<sm::PathChunk> path;
+  uint32_t nchunks;
+};
+PathRun path_case(const Bytes& s, const std::vector<uint32_t>* rec_in = nullptr) {
+  uint32_t size = 0;
+  size_t hdr = 0;
+  EXPECT(header(s, &size, &hdr));
+  const std::vector<uint32_t> rec = rec_in ? *rec_in : records(s, (uint32_t)hdr);
+  const auto c = exact(s);
+  const auto r = exact(rec);
+  PathRun run;
+  run.nchunks = (uint32_t)(rec.size() / (2 * sm::kIdxEntries));
+  run.end = sm::true_path(c.get(), (uint32_t)s.size(), (uint32_t)hdr, size, r.get(), run.path);
+  return run;
+}
+
+// an exact path against the walker: every element starts at a tag, with the output before it
+void expect_exact(const Bytes& s, const PathRun& run) {
+  uint32_t size = 0;
+  size_t hdr = 0;
+  EXPECT(header(s, &size, &hdr) && run.end == sm::PathEnd::kExact && !run.path.empty());
+  std::vector<uint64_t> tags;
+  ref_walk(s, hdr, s.size(), &tags);
+  const std::set<uint64_t> starts(tags.begin(), tags.end());
+  for (const sm::PathChunk& e : run.path) EXPECT(starts.count(e.y) && ref_walk(s, hdr, e.y).out == e.O && e.ex > e.y);
+  const std::vector<sm::StreamFrag> frags = sm::path_frags(run.path, size);
+  EXPECT(frags.size() == ((uint64_t)size + 65535) / 65536);
+  for (size_t f = 0; f < frags.size(); ++f) {
+    EXPECT(starts.count(frags[f].y) && frags[f].O <= frags[f].F && frags[f].F == f * 65536);
+    EXPECT(ref_walk(s, hdr, frags[f].y).out == frags[f].O);
+    for (const sm::PathChunk& e : run.path)  // the last element that starts at or before F: it reaches past F
+      if (e.y == frags[f].y) EXPECT(e.O + e.out > frags[f].F || &e == &run.path.back());
+    EXPECT(frags[f].lim == (f + 1 == frags.size() ? 0xffffffffu : (uint32_t)(f + 1) * 65536));
+  }
+}
+
+Bytes redeclared(const Bytes& s, uint32_t size) {  // the same body under another declared length
+  uint32_t old = 0;
+  size_t hdr = 0;
+  EXPECT(header(s, &old, &hdr));
+  Bytes o;
+  put_varint(o, size);
+  o.insert(o.end(), s.begin() + hdr, s.end());
+  return o;
+}
+
+void check_paths(const Bytes& text) {
+  Bytes five(text.begin(), text.begin() + 150000);
+  five.insert(five.end(), text.begin(), text.begin() + 150000);  // 300000 bytes: 5 fragments
+  const Bytes s5 = oracle_compress(five);
+  const PathRun r5 = path_case(s5);
+  EXPECT(r5.nchunks > 9);
+  expect_exact(s5, r5);
+  EXPECT(sm::path_frags(r5.path, 300000).size() == 5);
+  EXPECT(path_case(redeclared(s5, 300001)).end == sm::PathEnd::kFirstError);
+  EXPECT(path_case(redeclared(s5, 299999)).end == sm::PathEnd::kFirstError);
+  {  // a record that makes no progress
+    uint32_t size = 0;
+    size_t hdr = 0;
+    EXPECT(header(s5, &size, &hdr));
+    std::vector<uint32_t> rec = records(s5, (uint32_t)hdr);
+    rec[0] = (uint32_t)hdr;
+    EXPECT(path_case(s5, &rec).end == sm::PathEnd::kFallBack);
+  }
+  {  // literals that end deep inside the next chunk: entries past kIdxEntries (the host_walk branch)
+    Bytes s;
+    put_varint(s, 4000 + 300 + 5000 + 10);
+    put_literal(s, 4000, 2);
+    put_literal(s, 300, 2);
+    put_literal(s, 5000, 2);
+    put_literal(s, 10, 0);
+    const PathRun r = path_case(s);
+    expect_exact(s, r);
+    bool deep = false;
+    for (const sm::PathChunk& e : r.path) deep = deep || (e.y - 2) % sm::kIdxChunk >= sm::kIdxEntries;
+    EXPECT(deep);
+  }
+  bool one = false, nine = false;  // one chunk, nine chunks (the prefetched record stays inside the array)
+  for (uint32_t len = 2000; len <= 150000 && !(one && nine); len += 1000) {
+    const Bytes s = oracle_compress(Bytes(text.begin(), text.begin() + len));
+    const PathRun r = path_case(s);
+    if ((r.nchunks == 1 && !one) || (r.nchunks == 9 && !nine)) {
+      expect_exact(s, r);
+      (r.nchunks == 1 ? one : nine) = true;
+    }
+  }
+  EXPECT(one && nine);
+  // the saturating conversion: O and out at and beyond 2^32
+  const uint64_t G = 1ull << 32;
+  const std::vector<sm::PathChunk> far = {{5, 100, 50, 9}, {9, G - 1, 5, 11}, {11, G, G, 12}, {12, 2 * G, 1, G + 7}, {13, 100, G, 14}};
+  const std::vector<sm::OriginPath> sat = sm::origin_path(far, true);
+  EXPECT(sat.size() == far.size());
+  for (size_t e = 0; e < sat.size(); ++e) {
+    EXPECT((uint64_t)sat[e].O + sat[e].out <= 0xffffffffull && sat[e].y == far[e].y);
+    EXPECT(sat[e].O == std::min<uint64_t>(far[e].O, G - 1) && sat[e].ex == std::min<uint64_t>(far[e].ex, G - 1));
+    EXPECT(sat[e].out == std::min<uint64_t>(far[e].out, G - 1 - sat[e].O));
+  }
+  const std::vector<sm::OriginPath> plain = sm::origin_path({far[0]}, false);
+  EXPECT(plain.size() == 1 && plain[0].y == 5 && plain[0].ex == 9 && plain[0].O == 100 && plain[0].out == 50);
+}
+
+// ---- host batches -----------------------------------------------------------------------------
+
+void check_shards() {
+  for (uint32_t nblk : {0u, 1u, 7u})
+    for (int nctx : {1, 3, 8}) {
+      std::vector<uint64_t> in_off(nblk), out_off(nblk);
+      for (uint32_t b = 0; b < nblk; ++b) {  // unsorted
+        in_off[b] = (uint64_t)((b * 5) % 7) * 1000 + 17;
+        out_off[b] = (uint64_t)((b * 3) % 7) * 4096 + 5;
+      }
+      const auto i = exact(in_off), o = exact(out_off);
+      const std::vector<sm::Shard> sh = sm::make_shards(nctx, nblk, i.get(), o.get());
+      EXPECT(sh.size() == (size_t)nctx);
+      uint32_t next = 0;
+      for (const sm::Shard& s : sh) {
+        if (s.n == 0) continue;
+        EXPECT(s.b0 == next && s.in_off.size() == s.n && s.out_off.size() == s.n);  // each block once, in order
+        for (uint32_t k = 0; k < s.n && s.b0 + k < nblk; ++k) {
+          EXPECT(s.in_base <= in_off[s.b0 + k] && s.out_base <= out_off[s.b0 + k]);  // rebased offsets >= 0
+          EXPECT(s.in_base + s.in_off[k] == in_off[s.b0 + k] && s.out_base + s.out_off[k] == out_off[s.b0 + k]);
+        }
+        next = s.b0 + s.n;
+      }
+      EXPECT(next == nblk);
+    }
+}
+
+void check_lengths() {
+  const std::vector<uint32_t> in_len = {0, 1, 100, 65535, 65536};
+  std::vector<uint32_t> bound;
+  for (uint32_t n : in_len) bound.push_back(32 + n + n / 6);  // include/snappy_mi355x.h
+  const auto il = exact(in_len);
+  EXPECT(sm::check_compressed_lengths(exact(bound).get(), il.get(), (uint32_t)in_len.size()) == SM_OK);
+  EXPECT(sm::check_compressed_lengths(exact(bound).get(), il.get(), 0) == SM_OK);
+  for (size_t b = 0; b < in_len.size(); ++b) {
+    const struct {
+      uint32_t len;
+      sm_status want;
+    } cases[] = {{bound[b] + 1, SM_ERR_ARGUMENT}, {SM_OUT_LEN_ERROR, SM_ERR_DEVICE}, {0xffffffffu, SM_ERR_DEVICE}};
+    for (const auto& cs : cases) {
+      std::vector<uint32_t> ol = bound;
+      ol[b] = cs.len;
+      EXPECT(sm::check_compressed_lengths(exact(ol).get(), il.get(), (uint32_t)in_len.size()) == cs.want);
+    }
+  }
+}
+
+void check_varint() {
+  for (uint32_t v : {0u, 1u, 127u, 128u, 16383u, 16384u, 300000u, (1u << 28) - 1, 1u << 28, 0xffffffffu}) {
+    uint8_t a[5], b[5];
+    const size_t na = sm::encode32(a, v), nb = smo_encode32(b, v);
+    EXPECT(na == nb && memcmp(a, b, na) == 0);
+    for (size_t len = 0; len <= na; ++len) {  // every truncation, on an exact buffer
+      const auto c = exact(Bytes(a, a + len));
+      uint32_t got = 0, want = 0;
+      size_t next = 0, wnext = 0;
+      const sm_status st = sm::parse32(c.get(), len, 0, &got, &next);
+      EXPECT((int)st == smo_parse32(c.get(), len, 0, &want, &wnext));
+      if (st == SM_OK) EXPECT(len == na && got == v && next == na && want == v && wnext == na);
+    }
+  }
+  const uint8_t over[5] = {0xff, 0xff, 0xff, 0xff, 0x10};  // a fifth byte >= 0x10
+  EXPECT(sm::parse32(over, 5, 0, nullptr, nullptr) == SM_ERR_VARINT);
+}
+
+// ---- scratch layouts --------------------------------------------------------------------------
+
+struct Array {
+  const void* p;
+  size_t need;  // the bytes the kernels' interfaces (sm_internal.h) document
+};
+void expect_layout(const uint8_t* base, size_t end, const std::vector<Array>& arrays) {
+  for (size_t i = 0; i < arrays.size(); ++i) {
+    const uint8_t* p = (const uint8_t*)arrays[i].p;
+    EXPECT(((uintptr_t)p & 15) == 0 && p >= base && p + arrays[i].need <= base + end);
+    for (size_t j = 0; j < i; ++j) {
+      const uint8_t* q = (const uint8_t*)arrays[j].p;
+      EXPECT(arrays[i].need == 0 || arrays[j].need == 0 || p + arrays[i].need <= q || q + arrays[j].need <= p);
+    }
+  }
+}
+
+// carve(base) returns the layout's arrays and its end; a null base must measure the same end
+template <typename F>
+void layout_case(F&& carve) {
+  std::vector<Array> arrays;
+  const size_t end = carve(nullptr, &arrays);
+  uint8_t* base = (uint8_t*)aligned_alloc(16, end + 16);
+  arrays.clear();
+  EXPECT(carve(base, &arrays) == end && end % 16 == 0);
+  expect_layout(base, end, arrays);
+  free(base);
+}
+
+void check_carves() {
+  for (size_t n : {(size_t)0, (size_t)1, (size_t)3, (size_t)1000}) {
+    for (bool decode : {false, true})
+      layout_case([&](void* b, std::vector<Array>* a) {
+        const sm::BatchTables t = sm::carve_batch(b, n, decode);
+        *a = {{t.in_off, 8 * n}, {t.out_off, 8 * n}, {t.in_len, 4 * n}, {t.out_len, 4 * n}};
+        if (decode) a->insert(a->end(), {{t.out_cap, 4 * n}, {t.status, 4 * n}});
+        return t.end;
+      });
+    layout_case([&](void* b, std::vector<Array>* a) {
+      const sm::FragTables t = sm::carve_frags(b, n);
+      *a = {{t.in_off, 8 * n}, {t.out_off, 8 * n}, {t.dst_off, 8 * n}, {t.in_len, 4 * n}, {t.out_len, 4 * n}, {t.part_len, 4 * 256}};
+      return t.end;
+    });
+    layout_case([&](void* b, std::vector<Array>* a) {  // (n chunks, n fragments)
+      const sm::ParallelScratch t = sm::carve_parallel(b, n, n);
+      *a = {{t.rec, n * 64 * 8}, {t.frags, n * 16}, {t.st, n * 4}};
+      return t.end;
+    });
+    for (size_t size : {(size_t)0, n})  // (size 0: path_first_error's use)
+      layout_case([&](void* b, std::vector<Array>* a) {
+        const sm::OriginScratch t = sm::carve_origin(b, size, n);
+        *a = {{t.P, size * 4}, {t.path, n * 16}, {t.st, n * 4}, {t.pend, 4}};
+        return t.end;
+      });
+    for (size_t rounds : {(size_t)1, (size_t)3})
+      layout_case([&](void* b, std::vector<Array>* a) {
+        const sm::SmallScratch t = sm::carve_small(b, n, rounds);
+        *a = {{t.rec, n * 64 * 8 + n * 4 * 4 * 16}, {t.path, n * 16}, {t.ctl, 4 * (4 + rounds)}};
+        return t.end;
+      });
+  }
+  layout_case([&](void* b, std::vector<Array>* a) {
+    const sm::SingleMeta t = sm::carve_single(b);
+    *a = {{t.off, 8}, {t.in_len, 4}, {t.cap, 4}, {t.out_len, 8}};
+    EXPECT((const void*)t.status == (const void*)(t.out_len + 1));  // the pair launch_to_host reads
+    return t.end;
+  });
+  static_assert(sizeof(sm::StreamFrag) == 16 && sizeof(sm::OriginPath) == 16, "the kernels' element sizes");
+  static_assert(sm::kIdxEntries == 64 && sm::kDeepChains * sm::kDeepLevels == 16 && sm::kMaxParts == 256, "as counted above");
+}
+
+Bytes read_file(const char* path) {
+  Bytes b;
+  FILE* f = fopen(path, "rb");
+  if (!f) return b;
+  uint8_t buf[65536];
+  for (size_t k; (k = fread(buf, 1, sizeof buf, f)) > 0;) b.insert(b.end(), buf, buf + k);
+  fclose(f);
+  return b;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  const Bytes text = argc > 1 ? read_file(argv[1]) : Bytes();
+  if (text.size() < 150000) {
+    fprintf(stderr, "usage: sm_host_check <text file of at least 150000 bytes>\n");
+    return 2;
+  }
+  check_literal_only();
+  walk_case(oracle_compress(Bytes(text.begin(), text.begin() + 70000)));
+  Bytes random(70000);
+  uint32_t x = 12345;
+  for (uint8_t& b : random) b = (uint8_t)((x = x * 1664525u + 1013904223u) >> 24);
+  walk_case(oracle_compress(random));
+  uint32_t declared = 0;
+  walk_case(hand_stream(&declared));
+  check_paths(text);
+  check_shards();
+  check_lengths();
+  check_varint();
+  check_carves();
+  if (failures) {
+    fprintf(stderr, "sm_host_check: %d failure(s)\n", failures);
+    return 1;
+  }
+  printf("sm_host_check: ok\n");
+  return 0;
+}

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sm_host_rules.h"  // the HIP-free part: the types and constants the host rules share
+
 namespace sm {
 
 // Batch descriptor: block b is in[in_off[b] .. +in_len[b]) -> out[out_off[b] ..).
@@ -52,30 +54,7 @@ hipError_t launch_compress_fast(const CompressArgs& a, int mode, hipStream_t s);
 hipError_t launch_compress_sc(const CompressArgs& a, int mode, hipStream_t s);  // sm_compress_sc.hip (after the screen)
 hipError_t launch_decompress(const DecompressArgs& a, int large, hipStream_t s);
 
-// One large stream decoded in parallel (sm_uncompress): an index pass over 4 KiB chunks of the
-// compressed body, then one wave per 64 KiB output fragment (see sm_decompress.hip).
-constexpr uint32_t kIdxChunk = 4096;  // compressed bytes per index chunk
-constexpr uint32_t kIdxEntries = 64;  // entry offsets 0..63 covered per chunk
-// path 4 (a small stream on the device): bytes per index chunk -- kSmallChunkFine for bodies of
-// mostly copies (shorter index and fill latency per chunk), kSmallChunk when literals are long or
-// the body large (fewer chain elements).  sm_api.hip small_chunk() picks.
-constexpr uint32_t kSmallChunk = 1024;
-constexpr uint32_t kSmallChunkFine = 512;
-constexpr uint32_t kSmallChunkTiny = 128;  // small bodies of mostly copies (sm_api.hip small_chunk)
-#ifndef SM_SMALL_HOPS
-#define SM_SMALL_HOPS 1024
-#endif
-constexpr uint32_t kSmallHops = SM_SMALL_HOPS;  // path 4: chain steps per pointer per resolve launch
-constexpr uint32_t kOneLaunchHops = 256u << 10;  // path 4: outputs up to this size resolve in one launch of size hops
-constexpr uint32_t kDeepLevels = 4;     // path 4: deep-entry records per chain (consecutive long literals)
-constexpr uint32_t kDeepChains = 4;     // path 4: deep-record chains per chunk (distinct entry-lane exits)
 constexpr uint32_t kIdxPad = 288;     // staged bytes past a chunk: +16 entry slack, a 256-byte walk window + 16
-struct StreamFrag {
-  uint32_t y;    // a true tag start at or before the fragment's first tag (chunk entry)
-  uint32_t O;    // output position of the tag at y
-  uint32_t F;    // the fragment's first output position (a multiple of 65536)
-  uint32_t lim;  // output limit (0xffffffff for the last fragment: parse to the end)
-};
 hipError_t launch_validate(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t nblk,
                            int32_t* status, hipStream_t s);
 hipError_t launch_uncompressed_length(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
@@ -85,12 +64,6 @@ hipError_t launch_stream_index(const uint8_t* in, uint32_t N, uint32_t ip0, uint
                                hipStream_t s);
 hipError_t launch_decompress_frags(const uint8_t* in, uint32_t N, uint32_t size, uint8_t* out,
                                    const StreamFrag* frags, uint32_t nfrag, int32_t* status, hipStream_t s);
-// Any large stream (copies may reach into earlier blocks): origin pointers per output byte,
-// resolved by pointer jumping (sm_decompress.hip).  Path element = the tags starting in [y, ex),
-// whose out bytes of output start at O.
-struct OriginPath {
-  uint32_t y, ex, O, out;
-};
 hipError_t launch_origin_fill(const uint8_t* in, uint32_t N, uint32_t size, const OriginPath* path, uint32_t npath,
                               uint32_t* P, int32_t* status, hipStream_t s);
 // The same walk without the pointers: per path element, the reference's exact status of its first
@@ -117,16 +90,8 @@ hipError_t launch_small_decode(const uint8_t* in, const uint8_t* in_host, uint32
 // the device's).  src, dst 16-byte aligned; nw <= 256.
 hipError_t launch_to_host(const uint8_t* src, uint32_t n, uint8_t* dst, const uint32_t* wsrc, uint32_t nw,
                           uint32_t* words, hipStream_t s);
-// sm_uncompress path 5: a stream of at most kLitSpans literal tags.  Literal s's bytes are at
-// in + src[s] (any alignment) and go to out + dst[s], dst[s + 1] = dst[s] + its length, dst[n] the
-// stream's length (the declared one, which the literals cover exactly); words[0..1] = (length,
-// SM_OK) behind the bytes.  in and out may be device-mapped host memory.
-constexpr uint32_t kLitSpans = 16;
-struct LitSpans {
-  uint32_t src[kLitSpans];
-  uint32_t dst[kLitSpans + 1];
-  uint32_t n;
-};
+// sm_uncompress path 5: the literals of sp (LitSpans) from in to out; words[0..1] = (length, SM_OK)
+// behind the bytes.  in and out may be device-mapped host memory.
 hipError_t launch_literal_spans(const uint8_t* in, const LitSpans& sp, uint8_t* out, uint32_t* words, hipStream_t s);
 hipError_t launch_origin_gather(const uint8_t* in, const uint32_t* P, uint32_t size, uint8_t* out, hipStream_t s);
 // sm_compress, small inputs (at most 64 fragments), without host round trips: the fragments'

@@ -54,6 +54,15 @@ def test_no_scratch_size_beside_its_carve():
     for name in ("RangeCarve", "kCompressMeta", "kDecodeMeta", "kIndexMeta"):
         found = _definitions(r"\b%s\b" % name)
         assert not found, (name, found)
-    # (the function of that name; sm_api.hip has locals called meta_bytes)
-    found = _definitions(r"\bmeta_bytes\s*\([^;{}]*\)\s*\{")
+    found = _definitions(r"\bmeta_bytes\b")
     assert not found, found
+
+
+def test_host_rules_have_one_definition_without_hip():
+    """What sm_api.hip decides from untrusted bytes lives in sm_host_rules.h, which (with
+    sm_format.h) the host compiler alone builds for the sanitizer driver."""
+    for name in ("literal_only", "host_walk", "make_shards", "small_chunk", "check_compressed_lengths"):
+        found = _definitions(r"\b[\w:<>]+[\s\*&]+%s\s*\([^;{}]*\)\s*\{" % name)
+        assert found == ["sm_host_rules.h"], (name, found)
+    for f in ("sm_host_rules.h", "sm_format.h"):
+        assert not re.search(r"#\s*include\s*[<\"]hip/", _sources()[f]), f

@@ -1159,6 +1159,43 @@ def test_single_calls_through_pinned_staging(sm, oracle, gpu_available):
             assert _status(sm, bad) == oracle.uncompress_status(bad)
 
 
+def test_single_calls_grow_the_pinned_staging(sm, oracle, gpu_available, monkeypatch):
+    """The pinned input and result stagings of a context (sm_api.hip StagedInput, PinnedResult)
+    start at 1 MiB and grow in whole calls: a fresh context runs single calls of rising and
+    falling sizes, twice over, so a call grows a staging the call before it has just used, and
+    every result is the oracle's.  Valid calls only."""
+    fresh = sm.lib().sm_ctx_create(0)
+    assert fresh
+    monkeypatch.setitem(sm._ctx, 0, fresh)
+    try:
+        rng = np.random.default_rng(0x57A6)
+        text = read_testfile("alice29.txt")
+        small = sm.compress(text[:40000], mode="fast")
+        mid = (text * 11)[:3 << 19]   # 1.5 MiB
+        big = (text * 21)[:3 << 20]   # 3 MiB
+        rnd = rng.integers(0, 256, 1258291, dtype=np.uint8).tobytes()  # 1.2 MiB
+        # (a compressor's stream of it has 20 literals, over path 5's 16: three by hand)
+        lit = _lit_stream(len(rnd), [rnd[:70001], rnd[70001:900000], rnd[900000:]])
+        val = oracle.compress(rng.integers(0, 256, 5 << 19, dtype=np.uint8).tobytes())  # a 2.5 MiB stream
+        assert oracle.uncompress(small) == text[:40000] and oracle.uncompress(lit) == rnd
+        assert oracle.uncompress_status(val)[0] == 0
+        for rep in range(2):
+            assert sm.uncompress(small) == text[:40000] and sm.last_uncompress_path() == 4
+            c_mid = sm.compress(mid, mode="fast")
+            assert oracle.uncompress(c_mid) == mid
+            assert sm.uncompress(c_mid) == mid
+            assert sm.last_uncompress_path() == (4 if small_path(sm, c_mid) else 1)
+            assert sm.uncompress(lit) == rnd and sm.last_uncompress_path() == 5
+            c_big = sm.compress(big, mode="dense")
+            assert oracle.uncompress(c_big) == big and not small_path(sm, c_big)
+            assert sm.uncompress(c_big) == big and sm.last_uncompress_path() == 1
+            assert sm.validate(val) == 0
+            assert sm.uncompress(small) == text[:40000] and sm.last_uncompress_path() == 4
+    finally:
+        monkeypatch.undo()
+        sm.lib().sm_ctx_destroy(fresh)
+
+
 @pytest.mark.parametrize("mode", FAST_MODES)
 def test_fast_mode_periodic_blocks(sm, oracle, gpu_available, mode):
     """Periodic blocks (sm_compress_sc.hip's resync on long matches: every row's first walk ends
