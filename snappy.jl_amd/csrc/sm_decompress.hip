@@ -15,8 +15,10 @@
 //  * every lane computes, for its 4 positions of the current slot, the size a tag starting
 //    there would have (packed u8, 255 = literal too long for a batch); a pointer-doubling walk
 //    gives lane t the t-th tag directly;
-//  * up to 64 tags per batch decode one per lane, output offsets from a wave scan, the
-//    reference's error checks per tag -- the lowest failing lane decides the status;
+//  * up to 64 tags per batch decode one per lane, output offsets from a wave scan; the
+//    reference's length checks are settled by one uniform test per batch where that decides them
+//    (a batch that ends inside the declared size and the input), else run per tag -- the lowest
+//    failing lane decides the status;
 //  * tags execute lane-parallel in 16-byte pieces into a linear LDS output window (sources in
 //    the window or, older, in HBM), the few copies whose source overlaps the batch's own
 //    output (or offset < 16) in stream order after them; whole 16-byte blocks go to HBM when
@@ -289,11 +291,19 @@ __device__ inline uint32_t walk_window(uint64_t cw, uint32_t rlim, uint16_t* jt1
 // kLit: 16-byte loads per lane in flight in a long literal's bulk copy (4 in the batch kernels,
 // whose VGPR budget sets their occupancy; 16 in the lone-stream kernel, where one wave's copy is
 // latency-bound)
-template <uint32_t kLit = 4>
+// kWhole: the whole stream from its first tag (ip_end = N, frag_lo = 0, no output limit; those
+// three arguments are not read): no copy can cross a fragment and no batch is cut at a limit, so
+// e_cross, every op_lim test and both kErrCross returns are not in the instantiation.
+template <uint32_t kLit = 4, bool kWhole = false>
 __device__ int32_t decode_stream_batch(const uint8_t* __restrict__ in, uint32_t N, uint32_t ip, uint32_t ip_end,
                                        uint32_t size, uint8_t* out, uint32_t op0, uint32_t frag_lo, uint8_t* ring,
                                        uint16_t* jt, uint8_t* win, uint32_t lane, uint32_t& op_end,
                                        uint32_t op_lim = 0xffffffffu) {
+  if (kWhole) {
+    ip_end = N;
+    frag_lo = 0;
+    op_lim = 0xffffffffu;
+  }
   // ring holds stream bytes [wb, wb+768); pre1 = [wb+768, wb+1024) (loaded a batch ago),
   // pre2 = [wb+1024, wb+1280) issued at the end of the previous batch -- so a round's fence
   // (s_waitcnt vmcnt(0)) never waits for a freshly issued prefetch.
@@ -312,7 +322,10 @@ __device__ int32_t decode_stream_batch(const uint8_t* __restrict__ in, uint32_t 
   // every batch consumes input (ip strictly increases): more than N batches means the wave is
   // not whole (a caller that split it) -- a status, never a hang
   uint32_t guard = N + 1;
-  while ((int64_t)ip < Nm1 && op < op_lim) {
+  // streams of 2 GiB and more, and declared lengths within 64 KiB of 2^32, take every batch
+  // through the full checks (no reasoning about wrap: a batch makes at most 64 * 200 bytes)
+  const bool narrow = N < 0x80000000u && size <= 0xffff0000u;
+  while ((int64_t)ip < Nm1 && (kWhole || op < op_lim)) {
     if (__builtin_expect(--guard == 0, 0)) return kErrDevice;
     if (ip >= wb + 256) {
       if (__builtin_expect(ip < wb + 512, 1)) {
@@ -345,55 +358,76 @@ __device__ int32_t decode_stream_batch(const uint8_t* __restrict__ in, uint32_t 
 
     if (__builtin_expect(ntok != 0, 1)) {
       const bool mine = lane < ntok;
-      // one tag per lane: its fields, output offset (wave scan) and the reference's checks as
-      // selects (no exec branches), in the same first-failing order
-      struct TagDec {
-        uint32_t len, taglen, offset, litlen, osat, incl, opt, lsrc;
-        bool iscopy;
-        int32_t err;
-      };
-      auto tag_decode = [&](uint32_t tp) -> TagDec {
-        TagDec d;
-        const uint64_t hv = ring_get8(ring, mine ? tp : wb);
-        const uint32_t c = (uint32_t)hv & 0xff;
-        const uint32_t entry = char_entry(c);  // (a 512-byte table in global memory instead: 1.510 against 1.455 ms)
-        d.len = entry & 0xff;
-        d.taglen = entry >> 11;
-        const uint32_t tr_raw = (uint32_t)(hv >> 8);
-        // the low taglen bytes (0..4) of tr_raw: the low dword of ~0 << 8 taglen (64-bit: 0 for 4)
-        // clears them in a mask, one v_bfi_b32 keeps them
-        uint64_t hm;
-        asm("v_lshlrev_b64 %0, %1, -1" : "=v"(hm) : "v"(8 * d.taglen));
-        const uint32_t trailer = tr_raw & ~(uint32_t)hm;
-        d.iscopy = (c & 3) != 0;
-        d.offset = (entry & 0x700) + trailer;
-        d.litlen = d.len + trailer;
-        const uint32_t olen = d.iscopy ? d.len : d.litlen;
-        d.osat = mine ? min(olen, 65537u) : 0u;
-        d.incl = scan_dpp(d.osat);
-        d.opt = op + d.incl - d.osat;
-        d.lsrc = tp + 1 + d.taglen;
-        const int64_t avail_out = (int64_t)size - (int64_t)d.opt;
-        const int64_t avail_in = (int64_t)N - (int64_t)d.lsrc;
-        const bool e_off = (int64_t)d.opt <= (int64_t)(uint32_t)(d.offset - 1u);                                // :499
-        const bool e_cross = d.opt - d.offset < frag_lo;
-        const bool e_len = !((d.len <= 16) & (d.offset >= 8) & (avail_out >= 16)) & (avail_out < (int64_t)d.len);  // :505
-        const bool e_lit = (avail_out < (int64_t)d.litlen) | (avail_in < (int64_t)d.litlen);                     // :518
+      // one tag per lane: its fields and its output offset (wave scan).  A tag the walk hands to a
+      // lane has size != 255, so it is a copy (<= 64 B) or a literal of <= kMaxBatchLit bytes
+      // (tools/check_tag_lengths.c proves it for every (tag byte, next byte)): no length saturates,
+      // and a batch makes at most 64 * kMaxBatchLit bytes.
+      const uint64_t hv = ring_get8(ring, mine ? tpos : wb);
+      const uint32_t c = (uint32_t)hv & 0xff;
+      // The walk's size of the tag already fixes what char_entry's select tree would work out
+      // again (the same check proves both): a copy has csz - 1 trailer bytes, and a batch literal,
+      // whose tag has a length byte only as 0xf0, makes csz - 1 - (that byte) bytes -- its trailer
+      // is not needed.  What is left of the table entry (a 512-byte table in global memory
+      // instead: 1.510 against 1.455 ms) is a copy's length and the high offset bits of kind 1.
+      const uint32_t kind = c & 3, hi = c >> 2;
+      const bool iscopy = kind != 0, k1 = kind == 1;
+      const uint32_t len = k1 ? 4 + (hi & 7) : hi + 1;     // (a copy's; a literal lane's is not read)
+      const uint32_t offhi = k1 ? (c << 3) & 0x700u : 0u;
+      const uint32_t tl = (c + 16) >> 8;                   // a batch literal's length bytes: 1 for 0xf0
+      const uint32_t tr_raw = (uint32_t)(hv >> 8);
+      // the low taglen bytes (0..4) of tr_raw: the low dword of ~0 << 8 taglen (64-bit: 0 for 4)
+      // clears them in a mask, one v_bfi_b32 keeps them
+      uint64_t hm;
+      asm("v_lshlrev_b64 %0, %1, -1" : "=v"(hm) : "v"(8 * csz - 8));
+      const uint32_t offset = offhi + (tr_raw & ~(uint32_t)hm);  // (a copy's)
+      const uint32_t litlen = csz - 1 - tl;
+      const uint32_t olen = mine ? (iscopy ? len : litlen) : 0u;
+      const uint32_t incl = scan_dpp(olen);
+      const uint32_t opt = op + incl - olen;
+      const uint32_t lsrc = tpos + 1 + tl;                       // (a literal's)
+      const uint64_t minem = ntok == 64 ? ~0ull : ((1ull << ntok) - 1);
+      const uint64_t copya = ballot(iscopy) & minem;  // the batch's copies, over all ntok tags
+
+      // The reference's checks (internal.jl:499-518), once per batch where that decides them.  With
+      // X_all the output of all ntok tags and in_end the position after the last of them,
+      //   clean = op + X_all <= size && in_end <= N
+      // settles every length check of the batch, because the checks are monotone in stream order:
+      //  * e_len (:500-505) is avail_out < len: its leniency clause needs avail_out >= 16 >= len,
+      //    so it cannot clear the error when avail_out < len.  For every tag opt + olen = op + incl
+      //    <= op + X_all <= size, so avail_out >= len for a copy and >= litlen for a literal;
+      //  * a batch literal's lsrc + litlen is the next tag's position (its size is 1 + taglen +
+      //    litlen), which is at most in_end <= N: avail_in >= litlen.
+      // What is left per tag is the offset check (:499) as the 32-bit unsigned compare it is (both
+      // sides are zero-extended 32-bit values; offset 0 wraps to 0xffffffff and fails, as there),
+      // and for a fragment e_cross.  The capped batch (nt < ntok) is tested over all ntok tags, as
+      // the full checks are.  A batch that is not clean, or has such a tag, takes the full per-tag
+      // checks below, whose verdict alone decides: the test above only ever skips them.
+      const uint32_t X_all = readlane(incl, ntok - 1);
+      // (uniform 32-bit compares on the scalar unit -- as size - op they fold into a vector
+      // subtract-with-borrow; op <= size holds after any checked batch, and is tested, not assumed:
+      // with it and `narrow` the sum cannot wrap.  ipw is in_end here.)
+      const bool clean = narrow && op <= size && op + X_all <= size && ipw <= N;
+      uint64_t badm = ballot(opt <= offset - 1u);
+      if (!kWhole) badm |= ballot(opt - offset < frag_lo);
+      if (__builtin_expect(!clean || (badm & copya) != 0, 0)) {
+        // the full checks as selects, in the reference's first-failing order; the lowest failing
+        // lane decides the status
+        const int64_t avail_out = (int64_t)size - (int64_t)opt;
+        const int64_t avail_in = (int64_t)N - (int64_t)lsrc;
+        const bool e_off = (int64_t)opt <= (int64_t)(uint32_t)(offset - 1u);                                // :499
+        const bool e_cross = !kWhole && opt - offset < frag_lo;
+        const bool e_len = !((len <= 16) & (offset >= 8) & (avail_out >= 16)) & (avail_out < (int64_t)len);  // :505
+        const bool e_lit = (avail_out < (int64_t)litlen) | (avail_in < (int64_t)litlen);                     // :518
         const int32_t ec = e_off ? kErrCopyOffset : (e_cross ? kErrCross : (e_len ? kErrCopyLength : kOk));
-        d.err = !mine ? kOk : (d.iscopy ? ec : (e_lit ? kErrLiteral : kOk));
-        return d;
-      };
-      const TagDec d = tag_decode(tpos);
-      const uint32_t len = d.len, offset = d.offset, litlen = d.litlen, incl = d.incl, opt = d.opt, lsrc = d.lsrc;
-      const bool iscopy = d.iscopy;
-      const int32_t err = d.err;
-      const uint64_t em = ballot(err != kOk);
-      if (__builtin_expect(em != 0, 0)) return (int32_t)readlane((uint32_t)err, ctz64(em));
+        const int32_t err = !mine ? kOk : (iscopy ? ec : (e_lit ? kErrLiteral : kOk));
+        const uint64_t em = ballot(err != kOk);
+        if (em != 0) return (int32_t)readlane((uint32_t)err, ctz64(em));
+      }
       // cap the batch output at kBatchOut bytes (the window bound; one tag is <= 200 B) and at
       // the output limit (a fragment ends where the next one starts)
       uint32_t nt = ntok;
-      if (__builtin_expect(readlane(incl, ntok - 1) > kBatchOut || readlane(opt, ntok - 1) >= op_lim, 0)) {
-        nt = (uint32_t)__builtin_popcountll(ballot(mine && incl <= kBatchOut && opt < op_lim));
+      if (__builtin_expect(X_all > kBatchOut || (!kWhole && readlane(opt, ntok - 1) >= op_lim), 0)) {
+        nt = (uint32_t)__builtin_popcountll(ballot(mine && incl <= kBatchOut && (kWhole || opt < op_lim)));
         ipw = ip + readlane(tnext, nt - 1);
         big = false;  // the next tag is a batch tag inside the window
       }
@@ -410,7 +444,7 @@ __device__ int32_t decode_stream_batch(const uint8_t* __restrict__ in, uint32_t 
       // (lane sets as SGPR masks: a ballot of a compare is one v_cmp, and inverse_ballot turns a
       // mask back into a lane predicate for free -- a ballot of a combined bool costs two VALU)
       const uint64_t all = nt == 64 ? ~0ull : ((1ull << nt) - 1);
-      const uint64_t copym = ballot(iscopy) & all;
+      const uint64_t copym = copya & all;
       const uint64_t longm = ballot(litlen > 64) & ~copym & all;
       const uint64_t gm = ballot(slo < wbase) & copym;
       const bool gsrc = inverse_ballot(gm);
@@ -479,7 +513,7 @@ __device__ int32_t decode_stream_batch(const uint8_t* __restrict__ in, uint32_t 
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
       }
       op += X;
-      if (__builtin_expect(op > op_lim, 0)) return kErrCross;  // a tag crosses the fragment end
+      if (!kWhole && __builtin_expect(op > op_lim, 0)) return kErrCross;  // a tag crosses the fragment end
       win_flush(out, win, wbase, flushed, op & ~15u, lane);  // whole 16-byte blocks to HBM
       flushed = max(flushed, op & ~15u);
       ip = ipw;
@@ -491,7 +525,7 @@ __device__ int32_t decode_stream_batch(const uint8_t* __restrict__ in, uint32_t 
       issue_pre2 = false;
     }
 
-    if (__builtin_expect(big && op < op_lim, 0)) {  // (at op_lim the literal opens the next fragment)
+    if (__builtin_expect(big && (kWhole || op < op_lim), 0)) {  // (at op_lim the literal opens the next fragment)
       // one literal too long for the batch path (or a wrapped length): straight to HBM
       const uint64_t hv = ring_get8(ring, ip);
       const uint32_t c = uniform((uint32_t)hv & 0xff);
@@ -504,7 +538,7 @@ __device__ int32_t decode_stream_batch(const uint8_t* __restrict__ in, uint32_t 
       const int64_t avail_out = (int64_t)size - (int64_t)op;
       const int64_t avail_in = (int64_t)N - (int64_t)lsrc;
       if (avail_out < (int64_t)litlen || avail_in < (int64_t)litlen) return kErrLiteral;  // :518
-      if ((uint64_t)op + litlen > op_lim) return kErrCross;
+      if (!kWhole && (uint64_t)op + litlen > op_lim) return kErrCross;
       if (litlen <= kMaxBatchLit) {
         // a short literal with 2-4 length bytes (a non-minimal encoding, or a wrapped length): its
         // bytes are in the ring (the tag is in the batch window, ip < wb + 512, so lsrc + litlen <
@@ -617,7 +651,7 @@ __device__ inline int32_t parse_header(const uint8_t* in, uint32_t N, uint32_t l
 }
 
 #ifndef SM_DEC_OCC
-#define SM_DEC_OCC 7  // waves per SIMD: 67 VGPRs, 5.0 KB LDS per wave (8: 64 VGPRs with a spill, 1.444 against 1.357 ms)
+#define SM_DEC_OCC 7  // waves per SIMD: 62 VGPRs, 5.0 KB LDS per wave (8: no spill either, 1.365 against 1.28 ms)
 #endif
 // one stream of the batch (block b) by one wave
 template <uint32_t kLit = 4>
@@ -640,7 +674,7 @@ __device__ inline void decompress_block(const DecompressArgs& a, uint32_t b, uin
   if (st == kOk && size > cap) st = kBufferTooSmall;
   if (st == kOk) {
     uint32_t op_end = 0;
-    st = decode_stream_batch<kLit>(in, N, ip, N, size, dst, 0, 0, sring, sjt, swin, lane, op_end);
+    st = decode_stream_batch<kLit, true>(in, N, ip, N, size, dst, 0, 0, sring, sjt, swin, lane, op_end);
     if (st == kOk && op_end != size) st = kErrInvalid;                                    // Snappy.jl:50
   }
   if (lane == 0) {
