@@ -1,6 +1,7 @@
 // smc_layout.h -- what the three libraries' host sides share about device memory layouts: the
-// scratch carver and the companions' slot pitches.  Plain C++ (the host checkers compile it with
-// the host compiler alone).  Not part of the public ABI.
+// scratch carver and the companions' slot pitches -- and about the stream header: the varint32
+// rule, once, for hosts and kernels alike.  Plain C++ (the host checkers compile it with the host
+// compiler alone).  Not part of the public ABI.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -28,6 +29,45 @@ struct Carve {
 };
 
 SMC_HD constexpr uint64_t max_compressed_length(uint64_t n) { return 32 + n + n / 6; }  // src/Snappy.jl:80-82
+
+// ---- the varint32 stream header (src/varint.jl) ----------------------------------------------
+// bytes encode32! writes for v (varint.jl:46-69)
+SMC_HD inline uint32_t varint_len(uint32_t v) {
+  return v < (1u << 7) ? 1 : v < (1u << 14) ? 2 : v < (1u << 21) ? 3 : v < (1u << 28) ? 4 : 5;
+}
+
+// parse32 (varint.jl:12-37) over a byte accessor: at(i) is byte i of a header of which n bytes
+// exist.  Returns 0 with the value and the header's length hv (1..5), or kErrVarint when the header
+// is truncated, longer than 5 bytes or its 5th byte is 0x10 or more (value is then unspecified,
+// hv 0).  Reads at(i) for i < min(n, 5) only, in order, and stops at the header's last byte.  Where
+// the bytes come from -- a buffer at an offset, the lanes of a wave, a staged chunk head -- is the
+// caller's business.
+constexpr int32_t kErrVarint = 18;  // SM_ERR_VARINT (include/snappy_mi355x.h)
+template <typename At>
+SMC_HD inline int32_t parse_varint32(At at, uint32_t n, uint32_t& value, uint32_t& hv) {
+  int32_t st = kErrVarint;
+  value = 0;
+  hv = 0;
+  for (uint32_t i = 0; i < 5; ++i) {
+    if (i >= n) break;
+    const uint32_t b = at(i);
+    if (i < 4) {
+      value |= (b & 0x7f) << (7 * i);
+      if (b < 0x80) {
+        st = 0;
+        hv = i + 1;
+        break;
+      }
+    } else {
+      value |= (b & 0x7f) << 28;
+      if (b < 0x10) {
+        st = 0;
+        hv = 5;
+      }
+    }
+  }
+  return st;
+}
 
 // A 64 KiB block's output slot.  Two pitches, and they stay two (allocation sizes and the slots'
 // alignment are behaviour): framing rounds the bound up to 16 bytes, multi takes the raw fragment

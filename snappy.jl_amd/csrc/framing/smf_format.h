@@ -101,22 +101,8 @@ SMC_HD inline bool walk_step(Walk& w, const uint8_t* h, uint32_t have, uint64_t 
   if (type == SMF_CHUNK_UNCOMPRESSED) {
     c.ulen = c.pay_len;
   } else {  // the raw stream's varint32 header (the raw decoder's rules: at most 5 bytes, the 5th < 0x10)
-    const uint32_t avail = c.pay_len < 5 ? c.pay_len : 5;
-    uint32_t v = 0;
-    bool ok = false;
-    for (uint32_t i = 0; i < 5; ++i) {
-      if (i >= avail || ok) break;
-      const uint32_t bt = h[8 + i];
-      if (i < 4) {
-        v |= (bt & 0x7f) << (7 * i);
-        ok = bt < 0x80;
-      } else {
-        v |= (bt & 0x7f) << 28;
-        if (bt >= 0x10) break;
-        ok = true;
-      }
-    }
-    if (!ok) {
+    uint32_t v, hv;
+    if (smc::parse_varint32([&](uint32_t i) { return (uint32_t)h[8 + i]; }, c.pay_len, v, hv) != 0) {
       w.status = SM_ERR_VARINT;
       return false;
     }

@@ -27,30 +27,7 @@ constexpr uint32_t kDummy = 64;               // a long stream's slot in the sho
                                               // room an empty input's slot has (sm_max_compressed_length(0) = 32)
 
 SMC_HD inline uint32_t fragment_count(uint64_t len) { return (uint32_t)((len + kBlock - 1) / kBlock); }
-SMC_HD inline uint32_t varint_len(uint32_t v) {
-  return 1u + (v >= 1u << 7) + (v >= 1u << 14) + (v >= 1u << 21) + (v >= 1u << 28);
-}
-
-// varint32 header of p[0..n) (src/varint.jl:12-37): false for a truncated header, more than 5
-// bytes or a 5th byte >= 0x10.  Reads at most min(n, 5) bytes.
-SMC_HD inline bool parse_varint(const uint8_t* p, uint32_t n, uint32_t& value, uint32_t& hv) {
-  value = 0;
-  for (uint32_t i = 0; i < 5 && i < n; ++i) {
-    const uint32_t b = p[i];
-    if (i < 4) {
-      value |= (b & 0x7f) << (7 * i);
-      if (b < 0x80) {
-        hv = i + 1;
-        return true;
-      }
-    } else if (b < 0x10) {
-      value |= b << 28;
-      hv = 5;
-      return true;
-    }
-  }
-  return false;
-}
+using smc::varint_len;
 
 // ---- the index rules (include/snappy_mi355x_multi.h, smm_uncompress_device) ------------------
 // The rule on d_frag_first at element s < nstreams: from 0, non-decreasing, the last <= max_fragments.
@@ -70,7 +47,7 @@ SMC_HD inline bool stream_candidate(const uint8_t* p, uint32_t n, uint32_t cap, 
                                     uint32_t max_fragments, Candidate& c) {
   if (e0 > e1 || e1 > max_fragments) return false;
   if (n >= SM_OUT_LEN_ERROR) return false;  // (an error mark, not a length: the decoder's business)
-  if (!parse_varint(p, n, c.D, c.hv)) return false;
+  if (smc::parse_varint32([&](uint32_t i) { return (uint32_t)p[i]; }, n, c.D, c.hv) != 0) return false;  // (reads at most min(n, 5) bytes)
   if (c.D <= kBlock || c.D > cap) return false;
   c.e0 = e0;
   c.count = e1 - e0;

@@ -276,7 +276,7 @@ PathResult path_first_error(sm_ctx* ctx, uint32_t n, uint32_t size, const std::v
   return {PathResult::kStreamError, 3, sm::kErrInvalid};  // Snappy.jl:50
 }
 
-// One large stream in parallel (sm_decompress.hip, "one large stream"): index pass, true path
+// One large stream in parallel (sm_dec_stream.hip, "one large stream"; the fragment decode: sm_decompress.hip): index pass, true path
 // on the host, one wave per 64 KiB fragment.  The compressed bytes are in ctx->in.  Path 1 (or 2,
 // origin pointers) with the output in ctx->out, path 3 when the stream has an error (its first
 // one in stream order), or a fall back to the in-order decode.  With host_out, a large output
@@ -339,7 +339,7 @@ PathResult parallel_uncompress(sm_ctx* ctx, const uint8_t* comp, uint32_t n, uin
   }
   if (!cross) return {PathResult::kTaken, 1, SM_OK, npiece == 1};
   // Not block-structured (a copy reaches into an earlier block): origin pointers per output
-  // byte, resolved by pointer jumping (sm_decompress.hip, "any large stream").
+  // byte, resolved by pointer jumping (sm_dec_stream.hip, "any large stream").
   if (n >= 0x80000000u || size >= 0x80000000u) return kFallBack;  // 31-bit positions
   const size_t npath = path.size();
   const std::vector<sm::OriginPath> op = sm::origin_path(path, false);
@@ -372,7 +372,7 @@ PathResult parallel_uncompress(sm_ctx* ctx, const uint8_t* comp, uint32_t n, uin
   return {PathResult::kTaken, 2, SM_OK, true};
 }
 
-// A small stream entirely on the device (sm_decompress.hip, "a small stream"): index, chain,
+// A small stream entirely on the device (sm_dec_stream.hip, "a small stream"): index, chain,
 // origin pointers, resolve, gather, then one synchronisation with the output's download.  Path 4
 // with the output in host_out, or a fall back (an error or anything unexpected: the old paths
 // find the reference's first error).  comp: the call's input on the host.  It goes to the device

@@ -23,7 +23,7 @@ enum : int32_t {
   kBufferTooSmall = 2,
   kErrInputTooLarge = 16,
   kErrInvalid = 17,
-  kErrVarint = 18,
+  kErrVarint = smc::kErrVarint,
   kErrCopyOffset = 19,
   kErrCopyLength = 20,
   kErrLiteral = 21,
@@ -65,8 +65,71 @@ SMC_HD inline uint32_t char_entry(uint32_t c) {
 #endif
 }
 
-SMC_HD inline uint32_t varint_len(uint32_t v) {
-  return v < (1u << 7) ? 1 : v < (1u << 14) ? 2 : v < (1u << 21) ? 3 : v < (1u << 28) ? 4 : 5;
+using smc::varint_len;
+
+// ---- one tag (internal.jl:426-462) ---------------------------------------------------------------
+// What every walker -- the kernels' scalar steps, host_walk, literal_only -- reads from a tag byte
+// and the four bytes behind it: the table entry and the trailer, the low taglen bytes of the
+// lookahead.  The leniencies live here and nowhere else: the literal length is len + trailer in
+// UInt32 arithmetic (it wraps), and the lookahead arrives zero-padded past the input's end.
+struct Tag {
+  uint32_t c;        // the tag byte
+  uint32_t entry;    // its table entry (char_entry)
+  uint32_t taglen;   // bytes behind the tag byte that belong to the tag (0..4): entry >> 11
+  uint32_t trailer;  // the low taglen bytes of the lookahead
+  SMC_HD uint32_t len() const { return entry & 0xff; }  // a copy's length, a literal's base length
+  SMC_HD bool is_copy() const { return (c & 3) != 0; }
+  SMC_HD uint32_t offset() const { return (entry & 0x700) + trailer; }  // (a copy's)
+  SMC_HD uint32_t literal_len() const { return len() + trailer; }       // (a literal's; u32 wrap, as the reference)
+  SMC_HD uint32_t out_bytes() const { return is_copy() ? len() : literal_len(); }
+  // bytes in the stream: the tag and, for a literal, its bytes (64-bit: a wrapped length stays exact)
+  SMC_HD uint64_t size() const { return is_copy() ? 1 + taglen : 1ull + taglen + literal_len(); }
+};
+
+// The tag with tag byte c; tr_raw = the four stream bytes after it, little-endian, zero where the
+// input has ended (internal.jl:426-430).  Loading them is the caller's business.  In two steps for
+// a caller that fetches the lookahead after it knows the tag byte (a wave's scalar step reads each
+// through readfirstlane, and the order of those is the order of its instructions).
+SMC_HD inline Tag tag_head(uint32_t c) {
+  const uint32_t entry = char_entry(c);
+  return {c, entry, entry >> 11, 0u};
+}
+SMC_HD inline Tag with_trailer(Tag t, uint32_t tr_raw) {
+  t.trailer = t.taglen >= 4 ? tr_raw : (tr_raw & ((1u << (8 * t.taglen)) - 1u));
+  return t;
+}
+SMC_HD inline Tag decode_tag(uint32_t c, uint32_t tr_raw) { return with_trailer(tag_head(c), tr_raw); }
+// ... from the eight stream bytes at the tag
+SMC_HD inline Tag decode_tag8(uint64_t hv) { return decode_tag((uint32_t)hv & 0xff, (uint32_t)(hv >> 8)); }
+
+// Output bytes of a tag the window walk sized (sm_dec_walk.h walk_window: size csz != 255, so a
+// copy or a literal of at most 200 bytes): a copy's length, and for a literal, whose size is
+// 1 + taglen + length, the rest -- no trailer needed.
+SMC_HD inline uint32_t window_out_bytes(uint32_t c, uint32_t csz) {
+  const uint32_t e = char_entry(c);
+  return (c & 3) ? (e & 0xff) : csz - 1 - (e >> 11);
+}
+
+// The reference's three checks of tag t in their order (incremental_copy! internal.jl:499, :505;
+// copy_literal! :518), in its arithmetic: t writes at output position op of `size` declared
+// bytes, and a literal's bytes start at lsrc of N input bytes.
+// Two shorter forms are equivalent, which is why no caller needs its own:
+//  * :499 `op - 1 <= offset - 1` with unsigned wrap is offset == 0 || offset > op: offset 0 wraps
+//    to 0xffffffff, above any 32-bit op, and otherwise both sides drop the same 1;
+//  * :505's leniency (no length check on the 2 x 8-byte fast path, :500) never clears an error:
+//    it needs avail_out >= 16 >= len, and the error is avail_out < len.  So :505 is
+//    op + len > size.
+SMC_HD inline int32_t check_tag(const Tag& t, uint64_t op, uint32_t size, uint64_t lsrc, uint32_t N) {
+  const int64_t avail_out = (int64_t)size - (int64_t)op;
+  if (t.is_copy()) {
+    const uint32_t offset = t.offset();
+    if ((int64_t)op <= (int64_t)(uint32_t)(offset - 1u)) return kErrCopyOffset;                                  // :499
+    if (!(t.len() <= 16 && offset >= 8 && avail_out >= 16) && avail_out < (int64_t)t.len()) return kErrCopyLength;  // :505
+    return kOk;
+  }
+  const uint32_t litlen = t.literal_len();
+  const int64_t avail_in = (int64_t)N - (int64_t)lsrc;
+  return avail_out < (int64_t)litlen || avail_in < (int64_t)litlen ? kErrLiteral : kOk;                           // :518
 }
 
 // bytes of the literal tag for a run of len (>0) bytes (internal.jl:271-284)

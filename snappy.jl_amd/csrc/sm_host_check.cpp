@@ -1,6 +1,8 @@
 // sm_host_check.cpp -- stand-alone driver of sm_host_rules.h (no device, no HIP): what the main
 // library's host side decides from bytes it does not trust, on heap buffers of exactly the
 // documented sizes, so that AddressSanitizer and UBSan (make host_check) see one byte of over-read.
+// Also the rules the kernels' walkers share with it (sm_format.h decode_tag and check_tag,
+// common/smc_layout.h parse_varint32): swept here as the plain C++ they are.
 // Expected values come from the CPU oracle (oracle/snappy_oracle.c), from a byte-at-a-time tag
 // walker written here, or from the construction of the case -- never from the code under test.
 //   sm_host_check <text file of at least 150000 bytes>   (tests/golden/testdata/alice29.txt)
@@ -411,6 +413,160 @@ void check_varint() {
   EXPECT(sm::parse32(over, 5, 0, nullptr, nullptr) == SM_ERR_VARINT);
 }
 
+// ---- the shared rules: one tag, the reference's checks, the varint (sm_format.h, smc_layout.h) ----
+
+const uint8_t kTrailerBytes[7] = {0x00, 0x01, 0x7f, 0x80, 0xc7, 0xc8, 0xff};
+
+// decode_tag for every tag byte and trailer bytes at the mask's edges in each of the four
+// positions, against the oracle's table and the rule restated: kind, extra bytes, length, offset
+void check_tags() {
+  for (uint32_t c = 0; c < 256; ++c)
+    for (uint32_t k = 0; k < 7 * 7 * 7 * 7; ++k) {
+      const uint8_t b[4] = {kTrailerBytes[k % 7], kTrailerBytes[k / 7 % 7], kTrailerBytes[k / 49 % 7], kTrailerBytes[k / 343]};
+      const uint32_t tr = b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24;
+      const sm::Tag t = sm::decode_tag(c, tr);
+      const uint32_t entry = smo_char_table((uint8_t)c);
+      const uint32_t kind = c & 3, up = c >> 2;
+      const uint32_t extra = kind == 0 ? (up >= 60 ? up - 59 : 0) : kind == 1 ? 1 : kind == 2 ? 2 : 4;
+      uint32_t trailer = 0;
+      for (uint32_t i = 0; i < extra; ++i) trailer |= (uint32_t)b[i] << (8 * i);
+      bool ok = t.c == c && t.entry == entry && t.taglen == extra && t.taglen == entry >> 11 && t.trailer == trailer;
+      if (kind == 0) {
+        const uint32_t lit = (up < 60 ? up + 1 : 1) + trailer;  // (wraps at 32 bits for ff ff ff ff)
+        ok = ok && !t.is_copy() && t.literal_len() == lit && t.out_bytes() == lit && t.size() == 1ull + extra + lit;
+        if (extra == 0 || (extra == 1 && lit <= 200)) ok = ok && sm::window_out_bytes(c, 1 + extra + lit) == lit;
+      } else {
+        const uint32_t len = kind == 1 ? 4 + (up & 7) : up + 1;
+        const uint32_t off = (kind == 1 ? (c >> 5) << 8 : 0) + trailer;
+        ok = ok && t.is_copy() && t.len() == len && t.out_bytes() == len && t.offset() == off && t.size() == 1ull + extra;
+        ok = ok && sm::window_out_bytes(c, 1 + extra) == len;
+      }
+      const sm::Tag t8 = sm::decode_tag8((uint64_t)tr << 8 | c);
+      ok = ok && t8.c == t.c && t8.entry == t.entry && t8.taglen == t.taglen && t8.trailer == t.trailer;
+      if (!ok) {
+        EXPECT(ok);
+        fprintf(stderr, "  tag byte %02x, trailer %08x\n", c, tr);
+        return;
+      }
+    }
+}
+
+// a stream's status by decode_tag and check_tag alone, on the reference's loop (internal.jl:411-466)
+int shared_status(const Bytes& s) {
+  uint32_t size = 0;
+  size_t hdr = 0;
+  if (!header(s, &size, &hdr)) return sm::kErrVarint;
+  const uint32_t n = (uint32_t)s.size();
+  uint64_t op = 0, p = hdr;
+  while (p + 1 < n) {
+    uint32_t tr = 0;
+    for (uint32_t k = 0; k < 4; ++k) tr |= (p + 1 + k < n ? (uint32_t)s[p + 1 + k] : 0u) << (8 * k);
+    const sm::Tag t = sm::decode_tag(s[p], tr);
+    const int32_t st = sm::check_tag(t, op, size, p + 1 + t.taglen, n);
+    if (st != sm::kOk) return st;
+    op += t.out_bytes();
+    p += t.size();
+  }
+  return op == size ? sm::kOk : sm::kErrInvalid;
+}
+
+int checks_run = 0, checks_failing = 0;
+void checks_case(const Bytes& s, uint32_t declared) {
+  const auto c = exact(s);
+  Bytes out((size_t)declared + 64);
+  size_t got = 0;
+  const int want = smo_uncompress(c.get(), s.size(), out.data(), out.size(), &got);
+  const int have = shared_status(s);
+  EXPECT(have == want);
+  ++checks_run;
+  checks_failing += want != SMO_OK;
+}
+
+Bytes raw_copy(uint32_t kind, uint32_t offset, uint32_t len) {
+  if (kind == 1) return {(uint8_t)(1 | (len - 4) << 2 | (offset >> 8) << 5), (uint8_t)offset};
+  Bytes b = {(uint8_t)(kind | (len - 1) << 2)};
+  for (uint32_t k = 0; k < (kind == 2 ? 2u : 4u); ++k) b.push_back((uint8_t)(offset >> (8 * k)));
+  return b;
+}
+
+// one- and two-tag streams around each bound of the three checks: the verdict of check_tag must be
+// the oracle's status
+void check_checks() {
+  for (uint32_t op : {1u, 9u, 20u})  // a literal of op bytes, then a copy
+    for (uint32_t kind : {1u, 2u, 3u})
+      for (uint32_t len : {1u, 4u, 11u, 16u, 17u, 64u}) {
+        if (kind == 1 ? (len < 4 || len > 11) : false) continue;
+        for (uint32_t offset : {0u, 1u, 8u, op, op + 1})
+          for (int d : {-1, 0, 1, 16}) {  // the declared size: one short of the copy's end, exact, beyond (with the leniency's 16)
+            const uint32_t declared = op + len + d;
+            Bytes s;
+            put_varint(s, declared);
+            put_literal(s, op, 0);
+            const Bytes cp = raw_copy(kind, offset, len);
+            s.insert(s.end(), cp.begin(), cp.end());
+            checks_case(s, declared);
+            s.push_back(0x00);  // (and with a byte behind it: the copy is then not the input's last tag)
+            s.push_back(0x55);
+            checks_case(s, declared);
+          }
+      }
+  for (uint32_t nb = 0; nb <= 4; ++nb)  // one literal: to the input's end and the declared size, and one past either
+    for (uint32_t n : {1u, 5u, 60u}) {
+      for (int din : {-1, 0, 1})
+        for (int dout : {-1, 0, 1}) {
+          const uint32_t declared = n + dout;
+          Bytes s;
+          put_varint(s, declared);
+          put_literal(s, n, nb);
+          if (din < 0) s.pop_back();
+          if (din > 0) s.push_back(0x00);
+          checks_case(s, declared);
+        }
+    }
+  // four length bytes at the wrap: 1 + 0xfffffffe = 0xffffffff bytes (past everything), 1 + 0xffffffff = 0 bytes
+  for (uint8_t low : {(uint8_t)0xfe, (uint8_t)0xff})
+    for (uint32_t declared : {0u, 3u})
+      for (uint32_t behind : {0u, 3u}) {
+        Bytes s;
+        put_varint(s, declared);
+        s.insert(s.end(), {(uint8_t)(63 << 2), low, 0xff, 0xff, 0xff});
+        if (behind) put_literal(s, behind, 0);
+        checks_case(s, declared);
+      }
+  EXPECT(checks_run > 600 && checks_failing > 200 && checks_run - checks_failing > 50);
+}
+
+// parse_varint32 against the oracle's parse32: every length from 0 to 6 bytes, every last byte at
+// the rule's edges, on exact buffers
+void check_varint_rule() {
+  const uint8_t last[6] = {0x00, 0x0f, 0x10, 0x7f, 0x80, 0xff}, lead[3] = {0x80, 0xff, 0x01};
+  for (uint32_t len = 0; len <= 6; ++len) {
+    uint32_t leads = 1;
+    for (uint32_t k = 1; k < len; ++k) leads *= 3;
+    for (uint32_t l = 0; l < (len ? 6u : 1u); ++l)
+      for (uint32_t m = 0; m < leads; ++m) {
+        Bytes b;
+        for (uint32_t k = 0, r = m; k + 1 < len; ++k, r /= 3) b.push_back(lead[r % 3]);
+        if (len) b.push_back(last[l]);
+        const auto c = exact(b);
+        const uint8_t* q = c.get();
+        uint32_t got = 0, hv = 0, want = 0;
+        size_t wnext = 0;
+        const int32_t st = smc::parse_varint32([&](uint32_t i) { return (uint32_t)q[i]; }, len, got, hv);
+        EXPECT(st == smo_parse32(q, len, 0, &want, &wnext));
+        EXPECT(st == 0 || st == SM_ERR_VARINT);
+        if (st == 0) EXPECT(got == want && hv == wnext && smc::varint_len(got) <= hv);
+        uint32_t got2 = 0;
+        size_t next2 = 0;
+        EXPECT((int)sm::parse32(q, len, 0, &got2, &next2) == st && (st != 0 || (got2 == got && next2 == hv)));
+      }
+  }
+  for (uint32_t v : {0u, 127u, 128u, 16383u, 16384u, (1u << 21) - 1, 1u << 21, (1u << 28) - 1, 1u << 28, 0xffffffffu}) {
+    uint8_t a[5];
+    EXPECT(smc::varint_len(v) == smo_encode32(a, v));
+  }
+}
+
 // ---- scratch layouts --------------------------------------------------------------------------
 
 struct Array {
@@ -512,6 +668,9 @@ int main(int argc, char** argv) {
   check_shards();
   check_lengths();
   check_varint();
+  check_tags();
+  check_checks();
+  check_varint_rule();
   check_carves();
   if (failures) {
     fprintf(stderr, "sm_host_check: %d failure(s)\n", failures);

@@ -18,7 +18,7 @@ namespace sm {
 
 // ---- types and constants shared with the kernels -------------------------------------------------
 // One large stream decoded in parallel (sm_uncompress): an index pass over 4 KiB chunks of the
-// compressed body, then one wave per 64 KiB output fragment (see sm_decompress.hip).
+// compressed body (sm_dec_stream.hip), then one wave per 64 KiB output fragment (sm_decompress.hip).
 constexpr uint32_t kIdxChunk = 4096;  // compressed bytes per index chunk
 constexpr uint32_t kIdxEntries = 64;  // entry offsets 0..63 covered per chunk
 // path 4 (a small stream on the device): bytes per index chunk -- kSmallChunkFine for bodies of
@@ -41,7 +41,7 @@ struct StreamFrag {
   uint32_t lim;  // output limit (0xffffffff for the last fragment: parse to the end)
 };
 // Any large stream (copies may reach into earlier blocks): origin pointers per output byte,
-// resolved by pointer jumping (sm_decompress.hip).  Path element = the tags starting in [y, ex),
+// resolved by pointer jumping (sm_dec_stream.hip).  Path element = the tags starting in [y, ex),
 // whose out bytes of output start at O.
 struct OriginPath {
   uint32_t y, ex, O, out;
@@ -103,18 +103,13 @@ inline bool literal_only(const uint8_t* c, size_t n, size_t hdr, uint32_t size, 
   sp.n = 0;
   while (p < n) {
     if (sp.n == kLitSpans) return false;
-    const uint32_t t = c[p];
-    if (t & 3) return false;  // a copy
-    uint64_t len = (t >> 2) + 1;
-    size_t q = p + 1;
-    if ((t >> 2) >= 60) {
-      const uint32_t nb = (t >> 2) - 59;
-      if (nb > 3 || q + nb > n) return false;
-      uint32_t v = 0;
-      for (uint32_t k = 0; k < nb; ++k) v |= (uint32_t)c[q + k] << (8 * k);
-      len = (uint64_t)v + 1;
-      q += nb;
-    }
+    uint32_t tr = 0;  // (the length bytes: at most 3 are accepted, and they must lie inside the input)
+    for (uint32_t k = 0; k < 3; ++k) tr |= (p + 1 + k < n ? (uint32_t)c[p + 1 + k] : 0u) << (8 * k);
+    const Tag t = decode_tag(c[p], tr);
+    if (t.is_copy()) return false;
+    const size_t q = p + 1 + t.taglen;
+    if (t.taglen > 3 || q > n) return false;
+    const uint64_t len = t.literal_len();  // (at most 2^24: no wrap with 3 length bytes)
     if (q + len > n || o + len > size) return false;
     sp.src[sp.n] = (uint32_t)q;
     sp.dst[sp.n] = (uint32_t)o;
@@ -132,20 +127,11 @@ inline bool literal_only(const uint8_t* c, size_t n, size_t hdr, uint32_t size, 
 inline void host_walk(const uint8_t* comp, uint32_t n, uint64_t p, uint64_t lim, uint64_t* exit_pos, uint64_t* produced) {
   uint64_t o = 0;
   while (p < lim) {
-    const uint32_t c = comp[p];
-    const uint32_t entry = char_entry(c);
-    const uint32_t taglen = entry >> 11;
     uint32_t tr = 0;
     for (uint32_t k = 0; k < 4; ++k) tr |= (p + 1 + k < n ? (uint32_t)comp[p + 1 + k] : 0u) << (8 * k);
-    const uint32_t trailer = taglen >= 4 ? tr : (tr & ((1u << (8 * taglen)) - 1u));
-    if (c & 3) {
-      p += 1 + taglen;
-      o += entry & 0xff;
-    } else {
-      const uint32_t lit = (entry & 0xff) + trailer;
-      p += 1ull + taglen + lit;
-      o += lit;
-    }
+    const Tag t = decode_tag(comp[p], tr);
+    p += t.size();
+    o += t.out_bytes();
   }
   *exit_pos = p;
   *produced = o;
@@ -299,27 +285,12 @@ inline sm_status check_compressed_lengths(const uint32_t* out_len, const uint32_
 
 // ---- the varint header (src/varint.jl; sm_parse32 and sm_encode32 export these) ------------------
 inline sm_status parse32(const uint8_t* buf, size_t len, size_t off, uint32_t* value, size_t* next) {
-  uint32_t result = 0;
-  for (int i = 0; i < 5; ++i) {
-    if (off + i >= len) return SM_ERR_VARINT;
-    uint32_t b = buf[off + i];
-    if (i < 4) {
-      result |= (b & 0x7f) << (7 * i);
-      if (b < 0x80) {
-        if (value) *value = result;
-        if (next) *next = off + i + 1;
-        return SM_OK;
-      }
-    } else {
-      result |= (b & 0x7f) << 28;
-      if (b < 0x10) {
-        if (value) *value = result;
-        if (next) *next = off + 5;
-        return SM_OK;
-      }
-    }
-  }
-  return SM_ERR_VARINT;
+  uint32_t result, hv;
+  const uint32_t n = (uint32_t)std::min<size_t>(off < len ? len - off : 0, 5);
+  if (smc::parse_varint32([&](uint32_t i) { return (uint32_t)buf[off + i]; }, n, result, hv) != 0) return SM_ERR_VARINT;
+  if (value) *value = result;
+  if (next) *next = off + hv;
+  return SM_OK;
 }
 inline size_t encode32(uint8_t* buf, uint32_t v) {
   size_t i = 0;

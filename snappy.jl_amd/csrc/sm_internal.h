@@ -1,5 +1,6 @@
 // sm_internal.h -- launcher interfaces between the C-ABI layer (sm_api.hip) and the
-// kernels (sm_compress.hip, sm_decompress.hip).  Not part of the public ABI.
+// kernels (sm_compress.hip, sm_compress_fast.hip, sm_compress_sc.hip; sm_decompress.hip,
+// sm_dec_stream.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

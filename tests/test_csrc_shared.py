@@ -66,3 +66,33 @@ def test_host_rules_have_one_definition_without_hip():
         assert found == ["sm_host_rules.h"], (name, found)
     for f in ("sm_host_rules.h", "sm_format.h"):
         assert not re.search(r"#\s*include\s*[<\"]hip/", _sources()[f]), f
+
+
+def test_format_rules_have_one_definition():
+    """The rules every walker applies to untrusted bytes -- one tag, the reference's three checks,
+    the varint header -- are written once: decode_tag and check_tag in sm_format.h, varint_len and
+    parse_varint32 in common/smc_layout.h, and the trailer mask in sm_format.h alone."""
+    for name, where in (("decode_tag", "sm_format.h"), ("check_tag", "sm_format.h"), ("window_out_bytes", "sm_format.h"),
+                        ("varint_len", "common/smc_layout.h"), ("parse_varint32", "common/smc_layout.h")):
+        found = _definitions(r"\b[\w:<>]+[\s\*&]+%s\s*\([^;{}]*\)\s*\{" % name)
+        assert found == [where], (name, found)
+    for name in ("parse_varint", "parse_header32"):  # the companions' former copies
+        assert not _definitions(r"\b[\w:<>]+[\s\*&]+%s\s*\(" % name), name
+    mask = [f for f, text in _sources().items() if re.search(r"1u\s*<<\s*\(\s*8\s*\*\s*\w*\.?taglen\s*\)", text)]
+    assert mask == ["sm_format.h"], mask
+    # a varint parse is a loop over (b & 0x7f) << (7 * i): one file (beside the host checkers, whose
+    # expected values never come from the code under test)
+    loops = [f for f, text in _sources().items()
+             if re.search(r"0x7f\s*\)\s*<<\s*\(\s*7\s*\*", text) and not f.endswith("_check.cpp")]
+    assert loops == ["common/smc_layout.h"], loops
+
+
+def test_decoder_files_are_in_the_version_hash():
+    """sm_dec_walk.h and sm_dec_stream.hip enter the Makefile's HDRS and SRCS, so the version string
+    changes with them and every object is rebuilt when the shared walk changes."""
+    mk = _sources()["Makefile"]
+    hdrs = re.search(r"^HDRS\s*=(.*)$", mk, re.M).group(1).split()
+    srcs = re.search(r"^SRCS\s*=(.*)$", mk, re.M).group(1).split()
+    assert "sm_dec_walk.h" in hdrs and {"sm_decompress.hip", "sm_dec_stream.hip"} <= set(srcs)
+    hips = {f for f in _sources() if f.endswith(".hip") and "/" not in f}
+    assert hips == set(srcs), (hips, srcs)

@@ -546,7 +546,7 @@ def _nonminimal_streams(seed, count):
 
 def test_decompress_nonminimal_literals(sm, oracle, gpu_available):
     """Literal tags with more length bytes than needed (the batch walk leaves every hi >= 61
-    literal to the general path and sizes hi = 60 ones in SWAR: sm_decompress.hip pack_sizes,
+    literal to the general path and sizes hi = 60 ones in SWAR: sm_dec_walk.h pack_sizes,
     tools/check_tag_sizes.c) and wrapped lengths, between copies: outputs equal the LZ77
     meaning and the oracle's, in one batch and through validate."""
     built = _nonminimal_streams(77, 300)
@@ -935,7 +935,7 @@ def test_uncompress_origin_path_cases(sm, oracle, gpu_available):
 
 
 def test_uncompress_small_streams_device_path(sm, oracle, libsnappy, gpu_available):
-    """Path 4 (sm_api.hip small_uncompress; sm_decompress.hip k_stream_chain, k_origin_fill_dev,
+    """Path 4 (sm_api.hip small_uncompress; sm_dec_stream.hip k_stream_chain, k_origin_fill_dev,
     k_origin_resolve_hops): every corpus file in every compress mode and from libsnappy, streams
     at the path's size limits (4 KiB of output, one index chunk, 256 chunks), deep copy chains,
     and mutated streams -- output and status equal the oracle's (test/runtests.jl:8-24 round
@@ -1015,7 +1015,7 @@ def _fine_chunks(sm, s):
 
 def test_small_path_chunk_sizes_and_parallel_runs(sm, oracle, gpu_available):
     """Path 4's two index chunk sizes (sm_api.hip small_chunk) and the chain's parallel runs
-    (sm_decompress.hip k_stream_chain: pointer-jumped chunk links, serial steps between): bodies
+    (sm_dec_stream.hip k_stream_chain: pointer-jumped chunk links, serial steps between): bodies
     of exactly 1, 2 and many 512-byte chunks, both sides of the size rule's bounds, long copy runs
     (runs of >= kMinRun links) broken by long literals (deep entries, then a new run), and
     mutations of such streams.  Output and status equal the oracle's."""

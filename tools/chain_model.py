@@ -1,4 +1,4 @@
-"""CPU model of path 4's device chain (k_stream_chain, sm_decompress.hip) on a stream: how many
+"""CPU model of path 4's device chain (k_stream_chain, sm_dec_stream.hip) on a stream: how many
 path elements the chain takes from the index's entry records, from the deep records, or by its own
 serial walk (dev_walk, the slow case).  Design tool:  python3 tools/chain_model.py STREAM... [--levels K]
 Streams from tools/dump_streams.py (gpurun_out/streams/).  --runs: the round-5 chain's parallel

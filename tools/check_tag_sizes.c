@@ -1,5 +1,5 @@
 // Design check for the decoder's SWAR tag-size computation (pack_sizes in
-// snappy.jl_amd/csrc/sm_decompress.hip): the packed formula must equal the per-byte
+// snappy.jl_amd/csrc/sm_dec_walk.h): the packed formula must equal the per-byte
 // definition (char_entry / spec_size, internal.jl:435-462 semantics) for every input.
 // v_perm_b32 is emulated.  Run by tests/test_host_logic.py.
 #include <stdint.h>

@@ -6,9 +6,11 @@
 Every .hip translation unit of the three libraries (snappy.jl_amd/csrc, csrc/framing, csrc/multi)
 is compiled for the device alone to assembly with its Makefile's flags, in both trees.  Per kernel
 (and per device function that was not inlined) the instruction stream and the .amdhsa_kernel block
-(VGPRs, SGPRs, LDS, scratch, ...) are compared as text; so is everything else in the file (tables,
-the metadata note).  One line per kernel is printed; the exit status is 1 if anything differs.
-CPU only: nothing is launched.
+(VGPRs, SGPRs, LDS, scratch, ...) are compared as text; so is everything else in a file that both
+trees have (tables, the metadata note).  Kernels are matched by name within a library, so one that
+moved to another translation unit is compared with its parent there.  One line per kernel is
+printed, with both sides' register, LDS and scratch figures when it differs; the exit status is 1
+if anything differs.  CPU only: nothing is launched.
 """
 import argparse
 import os
@@ -50,6 +52,10 @@ def split(asm):
     funcs, descs, rest = {}, {}, []
     # (the compilation unit's id hashes the file's path)
     asm = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid", asm)
+    # (local labels carry the function's index in its file: .LBB7_3, .Lfunc_end7, .LJTI7_0)
+    asm = re.sub(r"\.L(JTI|func_begin|func_end)\d+", r".L\1", asm)
+    asm = re.sub(r"BB\d+_(\d+)", r"BB_\1", asm)  # (labels and the loop comments that name them)
+    asm = re.sub(r"[ \t]+;", " ;", asm)            # (a comment's column moves with the label's width)
     lines = [l for l in asm.splitlines() if not re.match(r"\s*\.(file|ident)\b", l)]
     i = 0
     while i < len(lines):
@@ -71,6 +77,35 @@ def split(asm):
     return funcs, descs, "\n".join(rest)
 
 
+FIGURES = (("vgpr", "next_free_vgpr"), ("sgpr", "next_free_sgpr"), ("lds", "group_segment_fixed_size"),
+           ("scratch", "private_segment_fixed_size"))
+
+
+def figures(desc):
+    """The register, LDS and scratch figures of an .amdhsa_kernel block, as one string."""
+    got = dict(re.findall(r"\.amdhsa_(\w+)\s+(\S+)", desc or ""))
+    return " ".join("%s=%s" % (short, got.get(key, "?")) for short, key in FIGURES)
+
+
+def by_name(files):
+    """{function: [(file, instructions, descriptor)]} over a library's translation units."""
+    out = {}
+    for f in sorted(files):
+        funcs, descs, _ = files[f]
+        for fn, body in funcs.items():
+            out.setdefault(fn, []).append((f, body, descs.get(fn)))
+    return out
+
+
+def pairs(a, b):
+    """Pair a function's copies in the two trees: the same file first, then moved ones in order."""
+    fa, fb = {x[0]: x for x in a}, {x[0]: x for x in b}
+    both = sorted(set(fa) & set(fb))
+    la, lb = [fa[f] for f in sorted(set(fa) - set(fb))], [fb[f] for f in sorted(set(fb) - set(fa))]
+    n = max(len(la), len(lb))
+    return [(fa[f], fb[f]) for f in both] + list(zip(la + [None] * (n - len(la)), lb + [None] * (n - len(lb))))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("parent")
@@ -83,24 +118,34 @@ def main():
     print("  " + " ".join(command("<file>.hip", ["[SCHED]"], "<file>.s")))
     old, new = assemble(a.parent, work, "parent"), assemble(a.change, work, "change")
     differ = 0
-    for key in sorted(set(old) | set(new)):
-        name = os.path.join(*key)
-        if key not in old or key not in new:
-            print("%s: only in the %s tree" % (name, "change" if key in new else "parent"))
-            differ += 1
-            continue
-        (f0, d0, r0), (f1, d1, r1) = split(old[key]), split(new[key])
-        for fn in sorted(set(f0) | set(f1)):
-            kind = "kernel" if fn in d0 or fn in d1 else "function"
-            same = f0.get(fn) == f1.get(fn) and d0.get(fn) == d1.get(fn)
-            what = "identical" if same else ("DIFFERENT" if fn in f0 and fn in f1 else "MISSING on one side")
-            if kind == "kernel" and f0.get(fn) == f1.get(fn) and not same:
-                what = "DIFFERENT (resource metadata only)"
-            print("%s: %s %s: %s" % (name, kind, fn, what))
+    for d, _, _ in LIBS:
+        s0 = {f: split(t) for (dd, f), t in old.items() if dd == d}
+        s1 = {f: split(t) for (dd, f), t in new.items() if dd == d}
+        n0, n1 = by_name(s0), by_name(s1)
+        for fn in sorted(set(n0) | set(n1)):
+            for x, y in pairs(n0.get(fn, []), n1.get(fn, [])):
+                where = os.path.join(d, (y or x)[0])
+                if x and y and x[0] != y[0]:
+                    where += " (parent: %s)" % x[0]
+                kind = "kernel" if (x and x[2]) or (y and y[2]) else "function"
+                if not x or not y:
+                    what = "only in the %s tree" % ("change" if y else "parent")
+                elif x[1:] == y[1:]:
+                    what = "identical"
+                else:
+                    what = "DIFFERENT" if x[1] != y[1] else "DIFFERENT (resource metadata only)"
+                    if kind == "kernel":
+                        what += "\n    parent: %s\n    change: %s" % (figures(x[2]), figures(y[2]))
+                print("%s: %s %s: %s" % (where, kind, fn, what))
+                differ += what != "identical"
+        for f in sorted(set(s0) | set(s1)):
+            name = os.path.join(d, f)
+            if f not in s0 or f not in s1:
+                print("%s: only in the %s tree" % (name, "change" if f in s1 else "parent"))
+                continue
+            same = s0[f][2] == s1[f][2]
+            print("%s: everything else (tables, metadata note): %s" % (name, "identical" if same else "DIFFERENT"))
             differ += not same
-        same = r0 == r1
-        print("%s: everything else (tables, metadata note): %s" % (name, "identical" if same else "DIFFERENT"))
-        differ += not same
     print("%d difference(s)" % differ)
     return 1 if differ else 0
 
