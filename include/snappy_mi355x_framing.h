@@ -124,6 +124,30 @@ sm_status smf_range_plan(const smf_chunks* chunks, const uint64_t* chunk_off, ui
  * arrays and 2 * nranges edge slots of 65536 bytes. */
 size_t smf_range_scratch_bytes(uint32_t nranges, uint32_t max_range_chunks);
 
+/* ---- a batch of streams per call (host helpers, no device needed) ------------------- */
+/* The most data chunks an n-byte framed stream can hold: 0 for n < 10, else (n - 10) / 8 -- the
+ * identifier takes 10 bytes and a data chunk 8 at the least (an empty 0x01 chunk).  It bounds
+ * max_chunks for foreign streams of unknown content; a caller who knows a stream's uncompressed
+ * length should use ceil(length / 65536) for this library's streams, which is far smaller. */
+uint64_t smf_max_data_chunks(uint64_t n);
+/* The plan of smf_uncompress_streams_device over HOST arrays, by the rules the device runs: stream s
+ * is in[in_off[s], in_off[s] + in_len[s]) with out_cap[s] bytes of room (out_cap == NULL: no
+ * limit).  It fills what is known before any byte is decoded: status[s] = the walk's structural
+ * error, SM_BUFFER_TOO_SMALL for a well-formed stream longer than out_cap[s], or SM_OK;
+ * out_len[s] = the declared lengths of the data chunks before the error, else of all of them (the
+ * size needed); first[0, nstreams] = the exclusive scan of the slots -- a stream's data chunks when
+ * its status is SM_OK, else 0; *total = their sum.  No byte outside a stream's own range is read.
+ * Returns SM_OK, or SM_BUFFER_TOO_SMALL when *total > max_chunks (every status[s] is then
+ * SM_ERR_ARGUMENT and every out_len[s] 0, as on the device).  first / out_len / status / total may
+ * each be NULL. */
+sm_status smf_streams_plan(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t nstreams,
+                           const uint64_t* out_cap, uint32_t max_chunks, uint32_t* first, uint64_t* out_len,
+                           int32_t* status, uint64_t* total);
+/* Bytes of ctx scratch that a smf_uncompress_streams_device or smf_compress_streams_device call of
+ * nstreams streams and max_slots slots (max_chunks / max_blocks) keeps, the larger of the two: the
+ * per-stream and per-slot arrays and, for compress, the raw compressor's output slots. */
+size_t smf_streams_scratch_bytes(uint32_t nstreams, uint32_t max_slots);
+
 /* ---- context ---------------------------------------------------------------------- */
 /* NULL without a usable device. */
 smf_ctx* smf_ctx_create(int device);
@@ -227,7 +251,74 @@ sm_status smf_uncompress_ranges_device(smf_ctx* ctx, const uint8_t* d_in, uint64
                                        uint8_t* d_out, const uint64_t* d_out_off, uint64_t* d_out_len,
                                        int32_t* d_range_status, void* stream);
 
+/* Decodes a batch of framed streams in one call.  Stream s is d_in[d_in_off[s], d_in_off[s] +
+ * d_in_len[s]) (u64 offsets and lengths, any alignment) and decodes to d_out + d_out_off[s], where
+ * d_out_cap[s] bytes are its own.  The offset, length and capacity arrays are the caller's and are
+ * trusted; the stream bytes are not.  Each stream is walked by a wave of its own, and all data
+ * chunks of all streams go through the raw batched decoder, the copy kernel and the CRC pass once.
+ * For stream s, d_status[s], d_out_len[s] and the bytes are what smf_uncompress_device leaves for
+ * that stream alone with out_capacity = d_out_cap[s]:
+ *   a structural error from the walk: that status; d_out_len[s] = the declared lengths of the data
+ *     chunks before the error; nothing of the stream is decoded and it takes no slots;
+ *   well formed but longer than d_out_cap[s]: SM_BUFFER_TOO_SMALL, d_out_len[s] = the size needed;
+ *     nothing is decoded, no slots;
+ *   else every data chunk takes a slot and decodes to d_out_off[s] + the declared lengths before it
+ *     in its stream; d_status[s] = the first failing chunk's status in stream order (the raw
+ *     decoder's SM_ERR_*, or SMF_ERR_CRC), else SM_OK; d_out_len[s] = the sum of the declared
+ *     lengths; a failing chunk does not stop the other chunks of its stream.
+ * Streams do not affect each other: no byte is read outside a stream's own input range (a stream cut
+ * in the middle of a chunk is SMF_ERR_TRUNCATED whatever lies behind it) and none is written
+ * outside [d_out_off[s], d_out_off[s] + d_out_cap[s]).  Streams whose outputs overlap race.
+ * max_chunks: the caller's bound on the slots summed over all streams (smf_streams_plan's total;
+ * ceil(length / 65536) per stream of this library's encoder; smf_max_data_chunks for any stream);
+ * it sizes the launches and the ctx scratch (smf_streams_scratch_bytes).  If the device plan counts
+ * more, every d_status[s] = SM_ERR_ARGUMENT, every d_out_len[s] = 0 and nothing is written to d_out.
+ * d_chunk_first (nstreams + 1) and d_chunk_status (max_chunks) are optional, both given or both
+ * NULL: d_chunk_first = the exclusive scan of the slots per stream, and
+ * d_chunk_status[d_chunk_first[s] + k] = data chunk k's status of stream s, as
+ * smf_uncompress_chunks_device reports it (slots no chunk took: SM_OK).
+ * nstreams and max_chunks are at most 2^31 - 1; nstreams == 0 launches nothing.  No host
+ * synchronisation, except when the ctx's scratch has to grow. */
+sm_status smf_uncompress_streams_device(smf_ctx* ctx, const uint8_t* d_in, const uint64_t* d_in_off,
+                                        const uint64_t* d_in_len, uint32_t nstreams, uint32_t max_chunks, uint8_t* d_out,
+                                        const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len,
+                                        int32_t* d_status, uint32_t* d_chunk_first, int32_t* d_chunk_status,
+                                        void* stream);
+
+/* Frames a batch of inputs in one call.  Input s is d_in[d_in_off[s], d_in_off[s] + d_in_len[s])
+ * (trusted arrays, any alignment) and becomes one complete framed stream at d_out + d_out_off[s],
+ * where the caller leaves room for smf_max_framed_length(d_in_len[s]) bytes: the bytes
+ * smf_compress_device gives for that input alone in the same mode (the identifier, then one chunk
+ * per 64 KiB block by the encoder rule; the empty input: the identifier alone, 10 bytes).
+ * d_out_len[s] = the stream's length; d_status[s] = SM_OK, or SM_ERR_DEVICE when the raw
+ * compressor left an error mark in one of its blocks (that block is not packed; never expected;
+ * the other streams are unaffected).  All blocks of all inputs go through the raw batched
+ * compressor and the CRC pass once.
+ * max_blocks: the caller's bound on the sum of ceil(d_in_len[s] / 65536); it sizes the launches and
+ * the ctx scratch.  If the device counts more, every d_status[s] = SM_ERR_ARGUMENT, every
+ * d_out_len[s] = 0 and nothing is written to d_out.  nstreams and max_blocks are at most 2^31 - 1.
+ * No seek index is handed out.  No host synchronisation, except when the ctx's scratch has to grow. */
+sm_status smf_compress_streams_device(smf_ctx* ctx, const uint8_t* d_in, const uint64_t* d_in_off,
+                                      const uint64_t* d_in_len, uint32_t nstreams, uint32_t max_blocks, uint8_t* d_out,
+                                      const uint64_t* d_out_off, uint64_t* d_out_len, int32_t* d_status, int mode,
+                                      void* stream);
+
 /* ---- host memory (H2D + the device path + D2H, synchronous) ------------------------- */
+/* smf_compress_streams_device / smf_uncompress_streams_device over the same arrays in HOST memory:
+ * the streams' bytes go up in one copy, the device call runs, and only each stream's own bytes
+ * come back to out + out_off[s] (compress: out_len[s] bytes of the smf_max_framed_length(in_len[s])
+ * the caller leaves; uncompress: the stream's length when it was decoded, within out_cap[s]).  Both
+ * count their bound themselves, the blocks from the lengths and the chunks by smf_streams_plan.
+ * The per-stream results are out_len[s] and status[s]; the return value is SM_OK unless the call
+ * itself failed (SM_ERR_ARGUMENT, SM_ERR_DEVICE, SM_ERR_INPUT_TOO_LARGE for more than 2^31 - 1
+ * blocks or chunks). */
+sm_status smf_compress_streams(smf_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len,
+                               uint32_t nstreams, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
+                               int32_t* status, int mode);
+sm_status smf_uncompress_streams(smf_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len,
+                                 uint32_t nstreams, uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap,
+                                 uint64_t* out_len, int32_t* status);
+
 /* Bytes [lo, lo + len) of the uncompressed content of a framed stream in host memory.  The stream
  * is indexed on the host; only the bytes from the first touched chunk's payload to the last
  * touched chunk's end are uploaded, and smf_uncompress_ranges_device decodes them.

@@ -1,7 +1,7 @@
 // smf_api.hip -- C ABI of the framing format (include/snappy_mi355x_framing.h) over the raw
 // codec's public batched device calls (libsnappy_mi355x.so, linked by name) and the kernels of
-// smf_kernels.hip and smf_range.hip (the seek index and the ranged decode).  The host-only entry
-// points live in smf_host.cpp.
+// smf_kernels.hip, smf_range.hip (the seek index and the ranged decode) and smf_streams.hip (a batch
+// of streams per call).  The host-only entry points live in smf_host.cpp.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -95,6 +95,25 @@ constexpr size_t kIndexEntryBound = 26;
 static_assert(index_bytes(16) / 16 < kIndexEntryBound && 15 * (index_bytes(1) / 16) <= 4096 / kIndexEntryBound,
               "kIndexEntryBound does not cover an index entry of carve_index");
 
+struct StreamCallArrays {  // per stream, what a host-buffer stream call hands the device call (ctx->sarg)
+  uint64_t *in_off, *in_len, *out_off, *out_cap, *out_len;
+  int32_t* status;
+  uintptr_t end;
+};
+constexpr StreamCallArrays carve_stream_call(uintptr_t base, size_t n) {
+  smc::Carve c{base};
+  StreamCallArrays m{};
+  m.in_off = c.take<uint64_t>(n);
+  m.in_len = c.take<uint64_t>(n);
+  m.out_off = c.take<uint64_t>(n);
+  m.out_cap = c.take<uint64_t>(n);
+  m.out_len = c.take<uint64_t>(n);
+  m.status = c.take<int32_t>(n);
+  m.end = c.p;
+  return m;
+}
+constexpr size_t stream_call_bytes(size_t n) { return carve_stream_call(0, n).end; }
+
 // ---- the small device results in ctx->res ---------------------------------------------------------
 struct LenStatus {  // what a *_device call leaves in *d_out_len and *d_status
   uint64_t len;
@@ -125,6 +144,8 @@ struct smf_ctx {
   DevBuf io_in, io_out, res;     // the host-buffer calls' staging; small results
   DevBuf rmeta, redge;           // ranged decode: per-range and per-slot arrays, the edge slots
   DevBuf roff;                   // smf_uncompress_range: the index slice's chunk_off
+  DevBuf smeta;                  // the batched stream calls: per-stream and per-slot arrays
+  DevBuf sarg;                   // smf_compress_streams, smf_uncompress_streams: the calls' own arrays
   std::mutex mu;                 // serialises the host-buffer entry points
 };
 
@@ -202,7 +223,7 @@ void smf_ctx_destroy(smf_ctx* ctx) {
     DeviceGuard g(ctx->device);
     (void)hipDeviceSynchronize();  // (the *_device calls ran on the callers' streams)
     for (DevBuf* b : {&ctx->lut, &ctx->cmeta, &ctx->slots, &ctx->dmeta, &ctx->idx, &ctx->io_in, &ctx->io_out, &ctx->res,
-                      &ctx->rmeta, &ctx->redge, &ctx->roff})
+                      &ctx->rmeta, &ctx->redge, &ctx->roff, &ctx->smeta, &ctx->sarg})
       b->release();
   }
   sm_ctx_destroy(ctx->sm);
@@ -310,6 +331,59 @@ sm_status smf_uncompress_ranges_device(smf_ctx* ctx, const uint8_t* d_in, uint64
     SM_CHECK(smf::launch_range_trim(a, s));
   }
   SM_CHECK(smf::launch_range_verdicts(a, s));
+  return SM_OK;
+}
+
+sm_status smf_uncompress_streams_device(smf_ctx* ctx, const uint8_t* d_in, const uint64_t* d_in_off,
+                                        const uint64_t* d_in_len, uint32_t nstreams, uint32_t max_chunks, uint8_t* d_out,
+                                        const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len,
+                                        int32_t* d_status, uint32_t* d_chunk_first, int32_t* d_chunk_status,
+                                        void* stream) {
+  if (!ctx || nstreams > smf::kMaxStreams || max_chunks > smf::kMaxStreams) return SM_ERR_ARGUMENT;
+  if (!d_chunk_first != !d_chunk_status) return SM_ERR_ARGUMENT;
+  if (nstreams == 0) return SM_OK;
+  if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status)
+    return SM_ERR_ARGUMENT;
+  hipStream_t s = (hipStream_t)stream;
+  DeviceGuard g(ctx->device);
+  const uint32_t m = max_chunks;
+  SM_CHECK(ctx->smeta.ensure(smf::decode_streams_bytes(nstreams, m)));
+  const smf::DecodeStreamsArgs a{d_in,      d_in_off,  d_in_len,   nstreams, m,
+                                 d_out,     d_out_off, d_out_cap,  d_out_len, d_status,
+                                 d_chunk_first, d_chunk_status, smf::carve_decode_streams((uint8_t*)ctx->smeta.p, nstreams, m)};
+  SM_CHECK(smf::launch_streams_plan(a, s));
+  if (m) {
+    SM_PASS(sm_uncompress_batch_device(ctx->sm, d_in, a.s.ch.pay_off, a.s.dec_len, m, d_out, a.s.out_off, a.s.cap,
+                                       a.s.dec_out_len, a.s.dec_status, stream));
+    SM_CHECK(smf::launch_frame_copy(d_in, a.s.ch, m, a.s.out_off, a.s.cap, d_out, s));
+    SM_CHECK(smf::launch_crc32c(d_out, a.s.out_off, a.s.cap, m, a.s.crc_out, 1, (const smf::CrcLut*)ctx->lut.p, s));
+  }
+  SM_CHECK(smf::launch_streams_verdicts(a, s));
+  return SM_OK;
+}
+
+sm_status smf_compress_streams_device(smf_ctx* ctx, const uint8_t* d_in, const uint64_t* d_in_off,
+                                      const uint64_t* d_in_len, uint32_t nstreams, uint32_t max_blocks, uint8_t* d_out,
+                                      const uint64_t* d_out_off, uint64_t* d_out_len, int32_t* d_status, int mode,
+                                      void* stream) {
+  if (!ctx || nstreams > smf::kMaxStreams || max_blocks > smf::kMaxStreams || !valid_mode(mode)) return SM_ERR_ARGUMENT;
+  if (nstreams == 0) return SM_OK;
+  if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_len || !d_status) return SM_ERR_ARGUMENT;
+  hipStream_t s = (hipStream_t)stream;
+  DeviceGuard g(ctx->device);
+  const uint32_t m = max_blocks;
+  SM_CHECK(ctx->smeta.ensure(smf::compress_streams_bytes(nstreams, m)));
+  SM_CHECK(ctx->slots.ensure(smf::compress_streams_slot_bytes(m)));
+  const smf::CompressStreamsArgs a{d_in,  d_in_off,  d_in_len,  nstreams, m, (const uint8_t*)ctx->slots.p,
+                                   d_out, d_out_off, d_out_len, d_status,
+                                   smf::carve_compress_streams((uint8_t*)ctx->smeta.p, nstreams, m)};
+  SM_CHECK(smf::launch_cstreams_plan(a, s));
+  if (m) {
+    SM_PASS(sm_compress_batch_device(ctx->sm, d_in, a.s.in_off, a.s.in_len, m, (uint8_t*)ctx->slots.p, a.s.slot_off,
+                                     a.s.comp_len, mode, stream));
+    SM_CHECK(smf::launch_crc32c(d_in, a.s.in_off, a.s.in_len, m, a.s.crc, 1, (const smf::CrcLut*)ctx->lut.p, s));
+  }
+  SM_CHECK(smf::launch_cstreams_pack(a, s));
   return SM_OK;
 }
 
@@ -501,6 +575,126 @@ sm_status smf_uncompress_range(smf_ctx* ctx, const uint8_t* framed, size_t n, ui
   if (r.len != len) return SM_ERR_DEVICE;
   SM_CHECK(hipMemcpy(output, ctx->io_out.p, (size_t)len, hipMemcpyDeviceToHost));
   *out_len = (size_t)len;
+  return SM_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The host side of a host-buffer stream call: the streams' bytes packed behind one another in one
+// staging block (one upload), and room for every stream's output at a 16-byte boundary of the
+// device buffer (one download; each stream's own bytes then go to the caller's place).
+struct StreamStaging {
+  std::vector<uint8_t> bytes;
+  std::vector<uint64_t> in_off, out_off;
+  uint64_t out_total = 0;
+  StreamStaging(const uint8_t* in, const uint64_t* off, const uint64_t* len, uint32_t n, const std::vector<uint64_t>& room)
+      : in_off(n), out_off(n) {
+    uint64_t total = 0;
+    for (uint32_t r = 0; r < n; ++r) {
+      in_off[r] = total;
+      total += len[r];
+      out_off[r] = out_total;
+      out_total += (room[r] + 15) / 16 * 16;
+    }
+    bytes.resize((size_t)total);
+    for (uint32_t r = 0; r < n; ++r)
+      if (len[r]) memcpy(bytes.data() + in_off[r], in + off[r], (size_t)len[r]);
+  }
+};
+
+// uploads the staging and the arrays; out_cap may be null (compress)
+sm_status upload_stream_call(smf_ctx* ctx, const StreamStaging& h, const uint64_t* in_len, const uint64_t* out_cap,
+                             uint32_t n, StreamCallArrays& d) {
+  hipStream_t s = ctx->stream;
+  // (a byte of each at the least: the device calls want both pointers)
+  SM_CHECK(ctx->io_in.ensure(std::max<size_t>(h.bytes.size(), 1)));
+  SM_CHECK(ctx->io_out.ensure(std::max<size_t>((size_t)h.out_total, 1)));
+  SM_CHECK(ctx->sarg.ensure(stream_call_bytes(n)));
+  d = carve_stream_call((uintptr_t)ctx->sarg.p, n);
+  if (!h.bytes.empty()) SM_CHECK(hipMemcpyAsync(ctx->io_in.p, h.bytes.data(), h.bytes.size(), hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(d.in_off, h.in_off.data(), 8 * (size_t)n, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(d.in_len, in_len, 8 * (size_t)n, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(d.out_off, h.out_off.data(), 8 * (size_t)n, hipMemcpyHostToDevice, s));
+  if (out_cap) SM_CHECK(hipMemcpyAsync(d.out_cap, out_cap, 8 * (size_t)n, hipMemcpyHostToDevice, s));
+  return SM_OK;
+}
+
+// the lengths, the statuses and the device output buffer, back on the host (synchronises)
+sm_status download_stream_call(smf_ctx* ctx, const StreamStaging& h, const StreamCallArrays& d, uint32_t n,
+                               uint64_t* out_len, int32_t* status, std::vector<uint8_t>& out) {
+  hipStream_t s = ctx->stream;
+  out.resize((size_t)h.out_total);
+  SM_CHECK(hipMemcpyAsync(out_len, d.out_len, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(status, d.status, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+  if (!out.empty()) SM_CHECK(hipMemcpyAsync(out.data(), ctx->io_out.p, out.size(), hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipStreamSynchronize(s));
+  return SM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+sm_status smf_compress_streams(smf_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len,
+                               uint32_t nstreams, uint8_t* out, const uint64_t* out_off, uint64_t* out_len,
+                               int32_t* status, int mode) {
+  if (!ctx || nstreams > smf::kMaxStreams || !valid_mode(mode)) return SM_ERR_ARGUMENT;
+  if (nstreams == 0) return SM_OK;
+  if (!in_off || !in_len || !out || !out_off || !out_len || !status) return SM_ERR_ARGUMENT;
+  uint64_t blocks = 0;
+  std::vector<uint64_t> room(nstreams);
+  for (uint32_t r = 0; r < nstreams; ++r) {
+    if (in_len[r] && !in) return SM_ERR_ARGUMENT;
+    blocks += smf::stream_blocks(in_len[r]);
+    if (blocks > smf::kMaxStreams) return SM_ERR_INPUT_TOO_LARGE;
+    room[r] = smf_max_framed_length((size_t)in_len[r]);
+  }
+  const StreamStaging h(in, in_off, in_len, nstreams, room);
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  StreamCallArrays d;
+  SM_PASS(upload_stream_call(ctx, h, in_len, nullptr, nstreams, d));
+  SM_PASS(smf_compress_streams_device(ctx, (const uint8_t*)ctx->io_in.p, d.in_off, d.in_len, nstreams, (uint32_t)blocks,
+                                      (uint8_t*)ctx->io_out.p, d.out_off, d.out_len, d.status, mode, ctx->stream));
+  std::vector<uint8_t> framed;
+  SM_PASS(download_stream_call(ctx, h, d, nstreams, out_len, status, framed));
+  for (uint32_t r = 0; r < nstreams; ++r) {
+    if (out_len[r] > room[r]) return SM_ERR_DEVICE;
+    memcpy(out + out_off[r], framed.data() + h.out_off[r], (size_t)out_len[r]);
+  }
+  return SM_OK;
+}
+
+sm_status smf_uncompress_streams(smf_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len,
+                                 uint32_t nstreams, uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap,
+                                 uint64_t* out_len, int32_t* status) {
+  if (!ctx || nstreams > smf::kMaxStreams) return SM_ERR_ARGUMENT;
+  if (nstreams == 0) return SM_OK;
+  if (!in_off || !in_len || !out_off || !out_cap || !out_len || !status) return SM_ERR_ARGUMENT;
+  // the plan on the host: the slots, and the room each decoded stream needs on the device
+  std::vector<uint64_t> room(nstreams);
+  uint64_t chunks = 0;
+  const sm_status planned = smf_streams_plan(in, in_off, in_len, nstreams, out_cap, smf::kMaxStreams, nullptr, room.data(),
+                                             status, &chunks);
+  if (planned != SM_OK) return planned == SM_BUFFER_TOO_SMALL ? (sm_status)SM_ERR_INPUT_TOO_LARGE : planned;
+  for (uint32_t r = 0; r < nstreams; ++r) {
+    if (status[r] != SM_OK) room[r] = 0;  // (not decoded)
+    if (room[r] && !out) return SM_ERR_ARGUMENT;
+  }
+  const StreamStaging h(in, in_off, in_len, nstreams, room);
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  StreamCallArrays d;
+  SM_PASS(upload_stream_call(ctx, h, in_len, out_cap, nstreams, d));
+  SM_PASS(smf_uncompress_streams_device(ctx, (const uint8_t*)ctx->io_in.p, d.in_off, d.in_len, nstreams, (uint32_t)chunks,
+                                        (uint8_t*)ctx->io_out.p, d.out_off, d.out_cap, d.out_len, d.status, nullptr,
+                                        nullptr, ctx->stream));
+  std::vector<uint8_t> decoded;
+  SM_PASS(download_stream_call(ctx, h, d, nstreams, out_len, status, decoded));
+  for (uint32_t r = 0; r < nstreams; ++r)
+    if (room[r]) memcpy(out + out_off[r], decoded.data() + h.out_off[r], (size_t)room[r]);
   return SM_OK;
 }
 

@@ -122,6 +122,20 @@ SMC_HD inline int32_t walk_status(const Walk& w, bool stored, uint32_t max_chunk
   return stored && w.nchunks > max_chunks ? SM_BUFFER_TOO_SMALL : SM_OK;
 }
 
+// ---- the encoder rule ---------------------------------------------------------------------------
+constexpr uint8_t kTypeNone = 0xff;  // the compressor left an error mark for the block: nothing is packed
+
+// A block of n bytes whose Snappy stream has c bytes (or is an error mark): the chunk's type -- 0x00
+// iff the stream is strictly shorter than the block -- and, returned, the chunk's size in the stream.
+SMC_HD inline uint32_t encoder_chunk(uint32_t c, uint32_t n, uint8_t& type) {
+  if (c >= SM_OUT_LEN_ERROR) {
+    type = kTypeNone;
+    return 0;
+  }
+  type = c < n ? SMF_CHUNK_COMPRESSED : SMF_CHUNK_UNCOMPRESSED;
+  return 8u + (type == SMF_CHUNK_COMPRESSED ? c : n);
+}
+
 // ---- CRC-32C in parallel (k_crc32c, smf_kernels.hip) ------------------------------------------
 // Polynomials over GF(2) mod P in the reflected register's bit order: bit 31 is x^0.  A raw
 // register s (zero init, no final xor) followed by k zero bytes becomes s * x^(8k) mod P.

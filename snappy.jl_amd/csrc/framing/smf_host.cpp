@@ -1,8 +1,10 @@
 // smf_host.cpp -- the host-only part of the framing library (include/snappy_mi355x_framing.h):
-// the chunk walker over a host buffer, the bytewise CRC-32C and the size helpers.  No HIP and no
+// the chunk walker over a host buffer, the bytewise CRC-32C, the size helpers and the host plans of
+// the ranged and the batched decode.  No HIP and no
 // call into the raw codec, so this file also builds alone (the sanitizer driver, smf_host_check.cpp).
 #include "smf_format.h"
 #include "smf_range.h"
+#include "smf_streams.h"
 
 namespace {
 
@@ -162,6 +164,47 @@ sm_status smf_range_plan(const smf_chunks* chunks, const uint64_t* chunk_off, ui
 
 size_t smf_range_scratch_bytes(uint32_t nranges, uint32_t max_range_chunks) {
   return smf::range_meta_bytes(nranges, max_range_chunks) + smf::range_edge_bytes(nranges);
+}
+
+uint64_t smf_max_data_chunks(uint64_t n) { return n < SMF_IDENTIFIER_LENGTH ? 0 : (n - SMF_IDENTIFIER_LENGTH) / 8; }
+
+size_t smf_streams_scratch_bytes(uint32_t nstreams, uint32_t max_slots) {
+  const size_t decode = smf::decode_streams_bytes(nstreams, max_slots);
+  const size_t compress = smf::compress_streams_bytes(nstreams, max_slots) + smf::compress_streams_slot_bytes(max_slots);
+  return decode > compress ? decode : compress;
+}
+
+// the device's decode plan, stream by stream (smf_streams.h)
+sm_status smf_streams_plan(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t nstreams,
+                           const uint64_t* out_cap, uint32_t max_chunks, uint32_t* first, uint64_t* out_len,
+                           int32_t* status, uint64_t* total) {
+  if (nstreams > smf::kMaxStreams || max_chunks > smf::kMaxStreams) return SM_ERR_ARGUMENT;
+  if (nstreams && (!in_off || !in_len)) return SM_ERR_ARGUMENT;
+  for (uint32_t r = 0; r < nstreams; ++r)
+    if (in_len[r] && !in) return SM_ERR_ARGUMENT;
+  uint64_t sum = 0;
+  for (uint32_t r = 0; r < nstreams; ++r) {
+    const uint8_t* const p = in_len[r] ? in + in_off[r] : nullptr;
+    const smf::Walk w = smf::walk_stream(
+        in_len[r],
+        [p](uint64_t pos, uint32_t have, uint8_t* h) {
+          for (uint32_t i = 0; i < have; ++i) h[i] = p[pos + i];
+        },
+        [](uint32_t, uint64_t, const smf::Chunk&) {});
+    const smf::StreamPlan sp = smf::stream_plan(w, out_cap ? out_cap[r] : UINT64_MAX);
+    if (first) first[r] = sum > 0xffffffffull ? 0xffffffffu : (uint32_t)sum;
+    if (out_len) out_len[r] = sp.length;
+    if (status) status[r] = sp.status;
+    sum += sp.slots;
+  }
+  if (first) first[nstreams] = sum > 0xffffffffull ? 0xffffffffu : (uint32_t)sum;
+  if (total) *total = sum;
+  if (sum <= max_chunks) return SM_OK;
+  for (uint32_t r = 0; r < nstreams; ++r) {
+    if (status) status[r] = SM_ERR_ARGUMENT;
+    if (out_len) out_len[r] = 0;
+  }
+  return SM_BUFFER_TOO_SMALL;
 }
 
 }  // extern "C"

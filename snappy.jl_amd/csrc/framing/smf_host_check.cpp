@@ -1,6 +1,7 @@
 // smf_host_check.cpp -- stand-alone driver of the host-only framing code (smf_host.cpp), built with
 // -fsanitize=address,undefined by `make host_check`.  Every buffer is a heap block of exactly the
-// stream's size, so a walker that reads past a cut stream trips the sanitizer.  It also runs the
+// stream's size, so a walker that reads past a cut stream trips the sanitizer; the batched decode's
+// plan (smf_streams_plan) runs over the same cases laid directly behind one another.  It also runs the
 // CRC kernel's arithmetic (k_crc32c: the tables, the per-lane granule steps, the x^(128 t)
 // multipliers) lane by lane on the CPU against the bytewise CRC, and the kernels' shared byte
 // mover (smc::copy_bytes) thread by thread.
@@ -13,6 +14,7 @@
 #include "../common/smc_device.h"
 #include "smf_format.h"
 #include "smf_range.h"
+#include "smf_streams.h"
 
 namespace {
 
@@ -73,7 +75,16 @@ Result walk(const S& stream, uint32_t max_chunks = 16) {
   return r;
 }
 
+struct Case {
+  S stream;
+  int32_t status;
+  uint32_t nchunks;
+  uint64_t total;
+};
+std::vector<Case> cases;  // every status_case, for streams_cases
+
 void status_case(const char* name, const S& stream, int32_t status, uint32_t nchunks = 0, uint64_t total = 0) {
+  cases.push_back(Case{stream, status, nchunks, total});
   const Result r = walk(stream);
   if (r.sum.status != status || r.sum.nchunks != nchunks || r.sum.total_length != total) {
     std::printf("FAIL %s: status %d (want %d), chunks %u (want %u), total %llu (want %llu)\n", name, r.sum.status, status,
@@ -325,6 +336,77 @@ void range_cases() {
           }
 }
 
+// ---- the batched decode's plan (smf_streams.h through smf_streams_plan) --------------------------
+// Every structural case as one batch, the streams directly behind one another in a heap block of
+// exactly their size: a walk that leaves its stream reads its neighbour (a wrong status) or, at the
+// last stream, trips the sanitizer.  Expected values are the single-stream cases' own.
+void streams_cases() {
+  const uint32_t k = (uint32_t)cases.size();
+  std::vector<uint64_t> off(k), len(k), cap(k), out_len(k);
+  std::vector<uint32_t> first(k + 1), want_first(k + 1);
+  std::vector<int32_t> status(k);
+  uint64_t n = 0, slots = 0;
+  for (uint32_t s = 0; s < k; ++s) {
+    off[s] = n;
+    len[s] = cases[s].stream.size();
+    n += len[s];
+    cap[s] = cases[s].total;
+    want_first[s] = (uint32_t)slots;
+    slots += cases[s].status == SM_OK ? cases[s].nchunks : 0;
+  }
+  want_first[k] = (uint32_t)slots;
+  uint8_t* heap = (uint8_t*)std::malloc(n);
+  for (uint32_t s = 0; s < k; ++s) std::memcpy(heap + off[s], cases[s].stream.data(), len[s]);
+  auto run = [&](uint32_t max_chunks, uint64_t& total) {
+    return smf_streams_plan(heap, off.data(), len.data(), k, cap.data(), max_chunks, first.data(), out_len.data(),
+                            status.data(), &total);
+  };
+  uint64_t total = 0;
+  expect(run((uint32_t)slots, total) == SM_OK && total == slots && first == want_first, "streams plan: the scan");
+  for (uint32_t s = 0; s < k; ++s)
+    if (status[s] != cases[s].status || out_len[s] != cases[s].total) {
+      std::printf("FAIL streams plan: stream %u status %d (want %d), length %llu (want %llu)\n", s, status[s],
+                  cases[s].status, (unsigned long long)out_len[s], (unsigned long long)cases[s].total);
+      ++failures;
+    }
+  // a byte short: that stream alone changes, and it gives its slots up
+  for (uint32_t v = 0; v < k; ++v) {
+    if (cases[v].status != SM_OK || cases[v].total == 0) continue;
+    --cap[v];
+    expect(run((uint32_t)slots, total) == SM_OK && total == slots - cases[v].nchunks, "a byte short: the total");
+    for (uint32_t s = 0; s < k; ++s)
+      expect(status[s] == (s == v ? (int32_t)SM_BUFFER_TOO_SMALL : cases[s].status) && out_len[s] == cases[s].total,
+             "a byte short: the statuses");
+    expect(first[v + 1] == first[v], "a byte short: no slots");
+    ++cap[v];
+  }
+  // one slot short: nothing is planned
+  expect(run((uint32_t)slots - 1, total) == SM_BUFFER_TOO_SMALL && total == slots, "one slot short");
+  for (uint32_t s = 0; s < k; ++s) expect(status[s] == SM_ERR_ARGUMENT && out_len[s] == 0, "one slot short: the statuses");
+  // no room limit, no outputs, no streams, bad arguments
+  expect(smf_streams_plan(heap, off.data(), len.data(), k, nullptr, 0x7fffffffu, nullptr, nullptr, nullptr, &total) == SM_OK &&
+             total == slots,
+         "streams plan: null outputs");
+  expect(smf_streams_plan(heap, off.data(), len.data(), k, nullptr, 0x7fffffffu, nullptr, nullptr, nullptr, nullptr) == SM_OK,
+         "streams plan: null total");
+  first[0] = 7;
+  expect(smf_streams_plan(nullptr, nullptr, nullptr, 0, nullptr, 0, first.data(), nullptr, nullptr, &total) == SM_OK &&
+             total == 0 && first[0] == 0,
+         "streams plan: no streams");
+  expect(smf_streams_plan(nullptr, off.data(), len.data(), k, nullptr, 0, nullptr, nullptr, nullptr, nullptr) == SM_ERR_ARGUMENT &&
+             smf_streams_plan(heap, nullptr, len.data(), k, nullptr, 0, nullptr, nullptr, nullptr, nullptr) == SM_ERR_ARGUMENT &&
+             smf_streams_plan(heap, off.data(), len.data(), 0x80000000u, nullptr, 0, nullptr, nullptr, nullptr, nullptr) ==
+                 SM_ERR_ARGUMENT,
+         "streams plan: arguments");
+  std::free(heap);
+  expect(smf_max_data_chunks(0) == 0 && smf_max_data_chunks(9) == 0 && smf_max_data_chunks(10) == 0 &&
+             smf_max_data_chunks(17) == 0 && smf_max_data_chunks(18) == 1 && smf_max_data_chunks(10 + 8 * 1000) == 1000,
+         "max data chunks");
+  expect(smf_streams_scratch_bytes(3, 7) > smf_streams_scratch_bytes(3, 6) &&
+             smf_streams_scratch_bytes(4, 7) >= smf_streams_scratch_bytes(3, 7) && smf_streams_scratch_bytes(0, 0) > 0,
+         "streams scratch bytes");
+}
+
 // ---- the shared byte mover (../common/smc_device.h), every tid one after another ----------------
 // The source is a heap block that ends exactly at src + n, so a read past the end trips the
 // sanitizer; the function's own assert (host build) holds every 16-byte load to an aligned address
@@ -463,6 +545,7 @@ int main() {
   }
   expect(smf::host_message(SMF_ERR_CRC) != nullptr && smf::host_message(SM_OK) == nullptr, "messages");
   range_cases();
+  streams_cases();
   copy_bytes_cases();
 
   if (failures) {

@@ -1,11 +1,14 @@
 // smf_internal.h -- launcher interfaces between the framing C ABI (smf_api.hip) and its kernels
-// (smf_kernels.hip).  Not part of the public ABI.  All pointers are device pointers.
+// (smf_kernels.hip, smf_range.hip, smf_streams.hip).  Not part of the public ABI.  All pointers are
+// device pointers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../common/smc_device.h"
 #include "smf_format.h"
 #include "smf_range.h"
+#include "smf_streams.h"
 
 namespace smf {
 
@@ -30,6 +33,22 @@ struct PackArgs {
   uint8_t* dst;
 };
 hipError_t launch_frame_pack(const PackArgs& a, uint64_t* out_len, int32_t* status, hipStream_t s);
+
+// One chunk at d, by the workgroups (blockIdx.x, *) of k_frame_pack and k_streams_pack: the header
+// and the CRC field, then the payload -- the block's Snappy stream (0x00) or the block (0x01);
+// blockIdx.y strides the payload.  Nothing for a block with an error mark.
+__device__ inline void pack_chunk(uint32_t type, const uint8_t* __restrict__ block, uint32_t n,
+                                  const uint8_t* __restrict__ comp, uint32_t c, uint32_t crc, uint8_t* __restrict__ d) {
+  if (type == kTypeNone) return;
+  const uint32_t t = threadIdx.x;
+  const uint32_t pl = type == SMF_CHUNK_COMPRESSED ? c : n;
+  if (blockIdx.y == 0 && t < 8) {
+    const uint32_t L = pl + 4;
+    d[t] = t == 0 ? (uint8_t)type : (t < 4 ? (uint8_t)(L >> (8 * (t - 1))) : (uint8_t)(crc >> (8 * (t - 4))));
+  }
+  smc::copy_bytes(type == SMF_CHUNK_COMPRESSED ? comp : block, pl, d + 8, blockIdx.y * blockDim.x + t,
+                  gridDim.y * blockDim.x);
+}
 
 // index: ch == null counts only
 hipError_t launch_frame_index(const uint8_t* in, uint64_t n, const smf_chunks* ch, uint32_t max_chunks, smf_summary* sum,
@@ -76,5 +95,40 @@ hipError_t launch_range_copy(const RangeArgs& a, hipStream_t s);
 hipError_t launch_range_trim(const RangeArgs& a, hipStream_t s);
 // per slot and, segmented by range, per range
 hipError_t launch_range_verdicts(const RangeArgs& a, hipStream_t s);
+
+// ---- smf_streams.hip: a batch of framed streams per call -------------------------------------
+struct DecodeStreamsArgs {
+  const uint8_t* in;
+  const uint64_t *in_off, *in_len;
+  uint32_t nstreams, m;  // m = max_chunks: the slots
+  uint8_t* out;
+  const uint64_t *out_off, *out_cap;
+  uint64_t* out_len;
+  int32_t* status;
+  uint32_t* chunk_first;  // optional, with chunk_status
+  int32_t* chunk_status;
+  DecodeStreams s;
+};
+// the counting walk, the scan of the slots against m, the storing walk and the unused slots
+hipError_t launch_streams_plan(const DecodeStreamsArgs& a, hipStream_t s);
+// behind the raw decoder, the copies and the CRC pass: per slot, then segmented by stream
+hipError_t launch_streams_verdicts(const DecodeStreamsArgs& a, hipStream_t s);
+
+struct CompressStreamsArgs {
+  const uint8_t* in;
+  const uint64_t *in_off, *in_len;
+  uint32_t nstreams, m;  // m = max_blocks: the slots
+  const uint8_t* slots;
+  uint8_t* out;
+  const uint64_t* out_off;
+  uint64_t* out_len;
+  int32_t* status;
+  CompressStreams s;
+};
+// the scan of the streams' block counts against m, then per block its stream, input and slot
+hipError_t launch_cstreams_plan(const CompressStreamsArgs& a, hipStream_t s);
+// behind the raw compressor and the CRC pass: types and places, the packed chunks, then per stream
+// the identifier, the length and the status
+hipError_t launch_cstreams_pack(const CompressStreamsArgs& a, hipStream_t s);
 
 }  // namespace smf

@@ -20,9 +20,6 @@ using smc::block_scan;
 using smc::copy_bytes;
 using smc::kWave;
 
-constexpr uint32_t kOutLenError = SM_OUT_LEN_ERROR;
-constexpr uint8_t kTypeNone = 0xff;  // k_frame_scan: the compressor left an error mark, nothing is packed
-
 __device__ inline uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 }  // namespace
@@ -125,12 +122,10 @@ __global__ __launch_bounds__(256) void k_frame_scan(const uint32_t* comp_len, co
     const uint32_t b = base + threadIdx.x;
     uint64_t size = 0;
     if (b < nblk) {
-      const uint32_t c = comp_len[b], n = in_len[b];
-      const bool mark = c >= kOutLenError;
-      const uint8_t ty = mark ? kTypeNone : (c < n ? SMF_CHUNK_COMPRESSED : SMF_CHUNK_UNCOMPRESSED);
+      uint8_t ty;
+      size = encoder_chunk(comp_len[b], in_len[b], ty);
       type[b] = ty;
-      size = mark ? 0u : 8u + (ty == SMF_CHUNK_COMPRESSED ? c : n);
-      if (mark) bad = 1;  // (any writer: the same value)
+      if (ty == kTypeNone) bad = 1;  // (any writer: the same value)
     }
     uint64_t total;
     const uint64_t ex = block_scan(size, sh, total);
@@ -157,16 +152,7 @@ __global__ __launch_bounds__(256) void k_frame_pack(const uint8_t* __restrict__ 
     dst[t] = id[t];
   }
   if (b >= nblk) return;  // (the empty input: the identifier alone)
-  const uint32_t ty = type[b];
-  if (ty == kTypeNone) return;
-  const uint32_t pl = ty == SMF_CHUNK_COMPRESSED ? comp_len[b] : in_len[b];
-  uint8_t* const d = dst + dst_off[b];
-  if (blockIdx.y == 0 && t < 8) {
-    const uint32_t L = pl + 4, c = crc[b];
-    d[t] = t == 0 ? (uint8_t)ty : (t < 4 ? (uint8_t)(L >> (8 * (t - 1))) : (uint8_t)(c >> (8 * (t - 4))));
-  }
-  const uint8_t* const src = ty == SMF_CHUNK_COMPRESSED ? slots + slot_off[b] : in + in_off[b];
-  copy_bytes(src, pl, d + 8, blockIdx.y * blockDim.x + t, gridDim.y * blockDim.x);
+  pack_chunk(type[b], in + in_off[b], in_len[b], slots + slot_off[b], comp_len[b], crc[b], dst + dst_off[b]);
 }
 
 hipError_t launch_frame_compress_plan(uint64_t n, uint32_t nblk, uint64_t pitch, uint64_t* in_off, uint32_t* in_len,

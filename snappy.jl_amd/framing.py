@@ -11,11 +11,14 @@ of libsnappy_mi355x.so.
     compress_framed(x, return_index=True) -> (bytes, FramedIndex)  the encoder's own index
     uncompress_framed_range(x, lo, length)  -> bytes   only the touched chunks are decoded
     uncompress_framed_ranges(x, ranges)     -> (list of bytes, statuses)  one batched call
+    compress_framed_streams(xs)             -> list of bytes   many inputs, one batched call
+    uncompress_framed_streams(xs)           -> list of bytes   many streams, one batched call
+    streams_plan(xs), max_data_chunks(n)    the batched decode's plan and chunk bound (host)
 
 and, on torch tensors resident in HBM: crc32c_batch_device, compress_framed_device,
 index_framed_device, uncompressed_length_framed_device, uncompress_chunks_device,
 uncompress_framed_device, compress_framed_indexed_device, chunk_offsets_device,
-uncompress_ranges_device.
+uncompress_ranges_device, compress_framed_streams_device, uncompress_framed_streams_device.
 
 The package imports without this library; it is loaded on the first call here.  No CPU
 fallback: every codec call needs both HIP libraries and a device.
@@ -49,6 +52,12 @@ FRAMING_ABI_SYMBOLS = (
     "smf_chunk_offsets_device", "smf_compress_indexed_device", "smf_uncompress_ranges_device", "smf_uncompress_range",
 )
 RANGE_ABI_SYMBOLS = FRAMING_ABI_SYMBOLS[-8:]
+# a batch of streams per call (checked by tests/test_framing_streams_host.py)
+STREAMS_ABI_SYMBOLS = (
+    "smf_max_data_chunks", "smf_streams_plan", "smf_streams_scratch_bytes", "smf_uncompress_streams_device",
+    "smf_compress_streams_device", "smf_compress_streams", "smf_uncompress_streams",
+)
+FRAMING_ABI_SYMBOLS += STREAMS_ABI_SYMBOLS
 
 
 class Chunks(ctypes.Structure):
@@ -132,6 +141,20 @@ def lib():
         L.smf_uncompress_ranges_device.argtypes = [vp, vp, u64, pch, vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp]
         L.smf_uncompress_range.restype = i32
         L.smf_uncompress_range.argtypes = [vp, vp, sz, u64, u64, vp, ctypes.POINTER(sz)]
+        L.smf_max_data_chunks.restype = u64
+        L.smf_max_data_chunks.argtypes = [u64]
+        L.smf_streams_plan.restype = i32
+        L.smf_streams_plan.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, vp, ctypes.POINTER(u64)]
+        L.smf_streams_scratch_bytes.restype = sz
+        L.smf_streams_scratch_bytes.argtypes = [u32, u32]
+        L.smf_uncompress_streams_device.restype = i32
+        L.smf_uncompress_streams_device.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.smf_compress_streams_device.restype = i32
+        L.smf_compress_streams_device.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, ctypes.c_int, vp]
+        L.smf_compress_streams.restype = i32
+        L.smf_compress_streams.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, ctypes.c_int]
+        L.smf_uncompress_streams.restype = i32
+        L.smf_uncompress_streams.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -380,6 +403,99 @@ def uncompress_framed_ranges(data, ranges, index=None, device=0):
     return [out[o:o + int(k)].tobytes() for o, k in zip(out_off[:-1].tolist(), lens.tolist())], st
 
 
+def max_data_chunks(n):
+    """smf_max_data_chunks: the most data chunks an n-byte framed stream can hold, (n - 10) // 8.
+    For a stream of this library's encoder ceil(uncompressed length / 65536) is the count."""
+    return lib().smf_max_data_chunks(int(n))
+
+
+def _lay_out(datas):
+    """The buffers `datas` behind one another: (uint8 array, uint64 offsets, uint64 lengths)."""
+    parts = [np.frombuffer(d, np.uint8) if isinstance(d, (bytes, bytearray, memoryview)) else
+             np.ascontiguousarray(d).view(np.uint8).reshape(-1) for d in datas]
+    lens = np.array([p.size for p in parts], dtype=np.uint64)
+    offs = np.zeros(len(parts), np.uint64)
+    if len(parts) > 1:
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    buf = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    return (buf if buf.size else np.zeros(1, np.uint8)), offs, lens
+
+
+def streams_plan(streams, out_cap=None, max_chunks=0x7FFFFFFF):
+    """smf_streams_plan, the device's decode plan on the host, for a list of framed streams:
+    (rc, first, out_len, status, total) -- per stream what is known before any byte is decoded
+    (the walk's error, SM_BUFFER_TOO_SMALL against out_cap[s], or 0), the size needed, and the
+    exclusive scan of the slots (len(streams) + 1 entries)."""
+    buf, offs, lens = _lay_out(streams)
+    k = len(streams)
+    cap = None if out_cap is None else np.ascontiguousarray(out_cap, dtype=np.uint64)
+    first, out_len, status = np.zeros(k + 1, np.uint32), np.zeros(k, np.uint64), np.zeros(k, np.int32)
+    total = ctypes.c_uint64(0)
+    rc = lib().smf_streams_plan(buf.ctypes.data, offs.ctypes.data, lens.ctypes.data, k,
+                                None if cap is None else cap.ctypes.data, int(max_chunks), first.ctypes.data,
+                                out_len.ctypes.data, status.ctypes.data, ctypes.byref(total))
+    return int(rc), first, out_len, status, total.value
+
+
+def compress_framed_streams(datas, mode="fast", device=0):
+    """Frame every buffer of `datas` as a stream of its own in one batched call
+    (smf_compress_streams): a list of bytes, each what compress_framed gives for that input."""
+    datas = list(datas)
+    if not datas:
+        return []
+    buf, offs, lens = _lay_out(datas)
+    room = [10 + 8 * ((int(n) + 65535) // 65536) + int(n) for n in lens]
+    out_off = np.concatenate([[0], np.cumsum(room)]).astype(np.uint64)
+    out = np.empty(int(out_off[-1]), np.uint8)
+    out_len, status = np.zeros(len(datas), np.uint64), np.zeros(len(datas), np.int32)
+    st = lib().smf_compress_streams(context(device), buf.ctypes.data, offs.ctypes.data, lens.ctypes.data, len(datas),
+                                    out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data, status.ctypes.data,
+                                    _mode(mode))
+    if st:
+        raise FramingError(st)
+    for s, code in enumerate(status.tolist()):
+        if code:
+            raise StreamError(code, s)
+    return [out[int(o):int(o) + int(n)].tobytes() for o, n in zip(out_off[:-1], out_len)]
+
+
+class StreamError(FramingError):
+    """A FramingError of one stream of a batch: `stream` is its number in the batch."""
+
+    def __init__(self, code, stream):
+        super().__init__(code)
+        self.stream = stream
+
+
+def uncompress_framed_streams(streams, device=0, return_status=False):
+    """Decode a list of framed streams in one batched call (smf_uncompress_streams), every chunk's
+    CRC-32C checked: a list of bytes.  A failing stream raises StreamError (a FramingError with the
+    first failing stream's status and its number as `.stream`); with return_status=True nothing is
+    raised and the result is (list of bytes, or None for a failing stream; list of statuses)."""
+    streams = list(streams)
+    if not streams:
+        return ([], []) if return_status else []
+    buf, offs, lens = _lay_out(streams)
+    k = len(streams)
+    _, _, need, pre, _ = streams_plan(streams)
+    cap = np.where(pre == 0, need, 0).astype(np.uint64)
+    out_off = np.concatenate([[0], np.cumsum(cap)]).astype(np.uint64)
+    out = np.empty(max(int(out_off[-1]), 1), np.uint8)
+    out_len, status = np.zeros(k, np.uint64), np.zeros(k, np.int32)
+    st = lib().smf_uncompress_streams(context(device), buf.ctypes.data, offs.ctypes.data, lens.ctypes.data, k,
+                                      out.ctypes.data, out_off.ctypes.data, cap.ctypes.data, out_len.ctypes.data,
+                                      status.ctypes.data)
+    if st:
+        raise FramingError(st)
+    codes = status.tolist()
+    if not return_status:
+        for s, code in enumerate(codes):
+            if code:
+                raise StreamError(code, s)
+    res = [None if code else out[int(o):int(o) + int(n)].tobytes() for code, o, n in zip(codes, out_off[:-1], out_len)]
+    return (res, codes) if return_status else res
+
+
 def validate_framed(data, device=0):
     """SM_OK (0) or the status uncompress_framed(data) would raise with."""
     src, n, keep = _in_arg(data)
@@ -532,7 +648,39 @@ def uncompress_ranges_device(d_in, arrays, d_chunk_off, nchunks, d_lo, d_len, ma
         raise FramingError(st)
 
 
-__all__ = ["FRAMING_ABI_SYMBOLS", "MODES", "compress_framed", "uncompress_framed", "length_uncompressed_framed",
+def compress_framed_streams_device(d_in, d_in_off, d_in_len, max_blocks, d_out, d_out_off, d_out_len, d_status,
+                                   mode="fast", stream=None, device=None):
+    """Batched framing (smf_compress_streams_device): input s = d_in[d_in_off[s] : d_in_off[s] +
+    d_in_len[s]] becomes one framed stream at d_out[d_out_off[s]:], where max_framed_length(d_in_len[s])
+    bytes are left for it.  d_in / d_out uint8, d_in_off / d_in_len / d_out_off / d_out_len
+    int64[nstreams], d_status int32[nstreams]; max_blocks bounds the sum of ceil(d_in_len[s] / 65536)."""
+    dev = _dev(d_out, device)
+    st = lib().smf_compress_streams_device(context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), d_in_len.numel(),
+                                           int(max_blocks), _ptr(d_out), _ptr(d_out_off), _ptr(d_out_len),
+                                           _ptr(d_status), _mode(mode), _sp(stream, dev))
+    if st:
+        raise FramingError(st)
+
+
+def uncompress_framed_streams_device(d_in, d_in_off, d_in_len, max_chunks, d_out, d_out_off, d_out_cap, d_out_len,
+                                     d_status, d_chunk_first=None, d_chunk_status=None, stream=None, device=None):
+    """Batched decode (smf_uncompress_streams_device): framed stream s = d_in[d_in_off[s] :
+    d_in_off[s] + d_in_len[s]] decodes into d_out[d_out_off[s] : d_out_off[s] + d_out_cap[s]]; per
+    stream d_out_len (int64) and d_status (int32) as uncompress_framed_device leaves them for that
+    stream alone.  max_chunks bounds the data chunks summed over the streams that are decoded.
+    Optional, both or neither: d_chunk_first int32[nstreams + 1], d_chunk_status int32[max_chunks]."""
+    dev = _dev(d_out, device)
+    st = lib().smf_uncompress_streams_device(
+        context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), d_in_len.numel(), int(max_chunks), _ptr(d_out),
+        _ptr(d_out_off), _ptr(d_out_cap), _ptr(d_out_len), _ptr(d_status),
+        None if d_chunk_first is None else _ptr(d_chunk_first),
+        None if d_chunk_status is None else _ptr(d_chunk_status), _sp(stream, dev))
+    if st:
+        raise FramingError(st)
+
+
+__all__ = ["FRAMING_ABI_SYMBOLS", "MODES", "compress_framed_streams", "uncompress_framed_streams", "streams_plan",
+           "max_data_chunks", "compress_framed_streams_device", "uncompress_framed_streams_device", "StreamError", "compress_framed", "uncompress_framed", "length_uncompressed_framed",
            "validate_framed", "index_framed", "crc32c_batch_device", "compress_framed_device", "index_framed_device",
            "uncompressed_length_framed_device", "uncompress_chunks_device", "uncompress_framed_device", "FramedIndex",
            "seek_index_framed", "chunk_offsets", "range_chunk_count", "range_plan", "uncompress_framed_range",
