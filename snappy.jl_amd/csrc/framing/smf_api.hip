@@ -26,7 +26,7 @@ namespace {
 constexpr uint64_t kSlotPitch = smc::kFramingSlotPitch;
 
 // ---- scratch layouts: each is sized by its own carve from a null base (smc::Carve) ----------------
-struct CompressMeta {  // per block (ctx->cmeta)
+struct CompressMeta {  // per block (ctx->meta)
   uint64_t *in_off, *slot_off, *dst_off;
   uint32_t *in_len, *comp_len, *crc;
   uint8_t* type;
@@ -47,26 +47,13 @@ constexpr CompressMeta carve_compress(uintptr_t base, size_t n) {
 }
 constexpr size_t compress_bytes(size_t n) { return carve_compress(0, n).end; }
 
-struct DecodeMeta {  // per chunk (ctx->dmeta)
-  uint64_t* out_off;
-  uint32_t *cap, *dec_len, *dec_out_len, *crc_out;
-  int32_t *pre, *dec_status;
-  uintptr_t end;
-};
-constexpr DecodeMeta carve_decode(uintptr_t base, size_t n) {
+// smf_uncompress_chunks_device's slots at base (ctx->meta): one group, the caller's index and
+// d_chunk_status serve, so the call owns the plan's arrays and the stage's outputs.  Returns the bytes.
+size_t carve_chunk_slots(uintptr_t base, size_t n, smf::Slots& sl) {
   smc::Carve c{base};
-  DecodeMeta m{};
-  m.out_off = c.take<uint64_t>(n);
-  m.cap = c.take<uint32_t>(n);
-  m.dec_len = c.take<uint32_t>(n);
-  m.pre = c.take<int32_t>(n);
-  m.dec_out_len = c.take<uint32_t>(n);
-  m.dec_status = c.take<int32_t>(n);
-  m.crc_out = c.take<uint32_t>(n);
-  m.end = c.p;
-  return m;
+  sl = smf::carve_slots(c, n, 1, false, true, false);
+  return c.p - base;
 }
-constexpr size_t decode_bytes(size_t n) { return carve_decode(0, n).end; }
 
 struct IndexMeta {  // a stream's index and the per-chunk status behind it (ctx->idx)
   smf_chunks ch;
@@ -129,8 +116,6 @@ static_assert(offsetof(Results, io) == 64 && offsetof(Results, range) == 128 && 
                   sizeof(Results) <= 4096,
               "the layout of ctx->res");
 
-bool valid_chunks(const smf_chunks& ch) { return ch.type && ch.pay_off && ch.pay_len && ch.crc && ch.ulen; }
-
 }  // namespace
 
 struct smf_ctx {
@@ -138,13 +123,12 @@ struct smf_ctx {
   int device = 0;
   hipStream_t stream = nullptr;  // the sm_ctx's: the host-buffer calls run on it
   DevBuf lut;                    // smf::CrcLut
-  DevBuf cmeta, slots;           // compress: per-block arrays, the raw compressor's output slots
-  DevBuf dmeta;                  // decode: per-chunk arrays
+  DevBuf meta;                   // a *_device call's per-slot and per-group arrays
+  DevBuf slots;                  // compress: the raw compressor's output slots
   DevBuf idx;                    // a stream's index (smf_uncompress_device, smf_uncompress)
   DevBuf io_in, io_out, res;     // the host-buffer calls' staging; small results
-  DevBuf rmeta, redge;           // ranged decode: per-range and per-slot arrays, the edge slots
+  DevBuf redge;                  // ranged decode: the edge slots
   DevBuf roff;                   // smf_uncompress_range: the index slice's chunk_off
-  DevBuf smeta;                  // the batched stream calls: per-stream and per-slot arrays
   DevBuf sarg;                   // smf_compress_streams, smf_uncompress_streams: the calls' own arrays
   std::mutex mu;                 // serialises the host-buffer entry points
 };
@@ -170,12 +154,48 @@ sm_status upload_chunks(const smf_chunks& dst, const smf_chunks& src, uint32_t f
   return SM_OK;
 }
 
-// The pair a *_device call on s left at d: read back (synchronises s); a status in it is returned.
-sm_status read_back(const LenStatus* d, LenStatus& r, hipStream_t s) {
+// The slot stage (smf_slots.h) behind a decode plan: the raw decoder over the m slots of `in`, the
+// 0x01 slots' copies, the CRC-32C of every slot's output and the slots' verdicts.  Output offsets
+// are relative to out_base.
+sm_status slot_stage(smf_ctx* ctx, const uint8_t* in, uint8_t* out_base, const smf::Slots& sl, uint32_t m, hipStream_t s) {
+  if (m == 0) return SM_OK;
+  SM_PASS(sm_uncompress_batch_device(ctx->sm, in, sl.in_off, sl.dec_len, m, out_base, sl.out_off, sl.cap, sl.dec_out_len,
+                                     sl.dec_status, s));
+  SM_CHECK(smf::launch_slot_copy(in, out_base, sl, m, s));
+  SM_CHECK(smf::launch_crc32c(out_base, sl.out_off, sl.cap, m, sl.crc_out, 1, (const smf::CrcLut*)ctx->lut.p, s));
+  SM_CHECK(smf::launch_slot_verify(sl, m, s));
+  return SM_OK;
+}
+
+// The end of a single-buffer host call: the pair its *_device call on s left at d, read back
+// (synchronises s; a status in it is returned), the length checked (at most `most`, or exactly it),
+// and, with dst, that many bytes of ctx->io_out to the caller.
+sm_status finish(smf_ctx* ctx, const LenStatus* d, uint64_t most, bool exact, uint8_t* dst, size_t* length, hipStream_t s) {
+  LenStatus r;
   SM_CHECK(hipMemcpyAsync(&r, d, sizeof(r), hipMemcpyDeviceToHost, s));
   SM_CHECK(hipStreamSynchronize(s));
-  return r.st;
+  SM_PASS(r.st);
+  if (r.len > most || (exact && r.len != most)) return SM_ERR_DEVICE;
+  if (dst && r.len) SM_CHECK(hipMemcpy(dst, ctx->io_out.p, (size_t)r.len, hipMemcpyDeviceToHost));
+  if (length) *length = (size_t)r.len;
+  return SM_OK;
 }
+
+// A stream's index on the host, filled by smf_index; sum is its summary.
+struct HostIndex {
+  std::vector<uint8_t> type;
+  std::vector<uint64_t> pay_off;
+  std::vector<uint32_t> pay_len, crc, ulen;
+  smf_summary sum{};
+  smf_chunks view() { return smf_chunks{type.data(), pay_off.data(), pay_len.data(), crc.data(), ulen.data()}; }
+  sm_status fill(const uint8_t* framed, size_t n, uint32_t nchunks) {
+    type.resize(nchunks);
+    pay_off.resize(nchunks);
+    for (auto* v : {&pay_len, &crc, &ulen}) v->resize(nchunks);
+    const smf_chunks h = view();
+    return smf_index(framed, n, &h, nchunks, &sum);
+  }
+};
 
 }  // namespace
 
@@ -222,8 +242,8 @@ void smf_ctx_destroy(smf_ctx* ctx) {
   {
     DeviceGuard g(ctx->device);
     (void)hipDeviceSynchronize();  // (the *_device calls ran on the callers' streams)
-    for (DevBuf* b : {&ctx->lut, &ctx->cmeta, &ctx->slots, &ctx->dmeta, &ctx->idx, &ctx->io_in, &ctx->io_out, &ctx->res,
-                      &ctx->rmeta, &ctx->redge, &ctx->roff, &ctx->smeta, &ctx->sarg})
+    for (DevBuf* b : {&ctx->lut, &ctx->meta, &ctx->slots, &ctx->idx, &ctx->io_in, &ctx->io_out, &ctx->res, &ctx->redge,
+                      &ctx->roff, &ctx->sarg})
       b->release();
   }
   sm_ctx_destroy(ctx->sm);
@@ -254,18 +274,14 @@ static sm_status compress_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, 
   if (d_chunk_off) {
     if (!d_nchunks) return SM_ERR_ARGUMENT;
     if (max_chunks < nblk64) return SM_BUFFER_TOO_SMALL;
-    if (nblk64) {
-      if (!d_chunks) return SM_ERR_ARGUMENT;
-      ich = *d_chunks;
-      if (!valid_chunks(ich)) return SM_ERR_ARGUMENT;
-    }
+    if (!smf::take_chunks(d_chunks, nblk64, ich)) return SM_ERR_ARGUMENT;
   }
   const uint32_t nblk = (uint32_t)nblk64;
   hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(ctx->device);
-  SM_CHECK(ctx->cmeta.ensure(compress_bytes(nblk)));
+  SM_CHECK(ctx->meta.ensure(compress_bytes(nblk)));
   SM_CHECK(ctx->slots.ensure((size_t)nblk * kSlotPitch));
-  const CompressMeta m = carve_compress((uintptr_t)ctx->cmeta.p, nblk);
+  const CompressMeta m = carve_compress((uintptr_t)ctx->meta.p, nblk);
   uint8_t* slots = (uint8_t*)ctx->slots.p;
   SM_CHECK(smf::launch_frame_compress_plan(n, nblk, kSlotPitch, m.in_off, m.in_len, m.slot_off, s));
   SM_PASS(sm_compress_batch_device(ctx->sm, d_in, m.in_off, m.in_len, nblk, slots, m.slot_off, m.comp_len, mode, stream));
@@ -307,30 +323,23 @@ sm_status smf_uncompress_ranges_device(smf_ctx* ctx, const uint8_t* d_in, uint64
   if (!ctx || nchunks > smf::kMaxIndexChunks || nranges > smf::kMaxIndexChunks) return SM_ERR_ARGUMENT;
   if (nranges == 0) return SM_OK;
   if (!d_chunk_off || !d_lo || !d_len || !d_out_off || !d_out_len || !d_range_status) return SM_ERR_ARGUMENT;
-  smf_chunks ch{nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (nchunks) {
-    if (!d_in || !d_out || !d_chunks) return SM_ERR_ARGUMENT;
-    ch = *d_chunks;
-    if (!valid_chunks(ch)) return SM_ERR_ARGUMENT;
-  }
+  smf_chunks ch;
+  if (nchunks && (!d_in || !d_out)) return SM_ERR_ARGUMENT;
+  if (!smf::take_chunks(d_chunks, nchunks, ch)) return SM_ERR_ARGUMENT;
   hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(ctx->device);
   const uint32_t m = max_range_chunks;
-  SM_CHECK(ctx->rmeta.ensure(smf::range_meta_bytes(nranges, m)));
+  SM_CHECK(ctx->meta.ensure(smf::range_meta_bytes(nranges, m)));
   SM_CHECK(ctx->redge.ensure(smf::range_edge_bytes(nranges)));
-  smf::RangeArgs a{d_in,    n,     ch,        d_chunk_off, nchunks,        d_lo,
-                   d_len,   nranges, m,       d_out,       d_out_off,      d_out_len,
-                   d_range_status, (uint8_t*)ctx->redge.p, smf::carve_range((uint8_t*)ctx->rmeta.p, nranges, m)};
+  const smf::RangeArgs a{d_in,  n,       ch, d_chunk_off, nchunks,   d_lo,
+                         d_len, nranges, m,  d_out,       d_out_off, (uint8_t*)ctx->redge.p,
+                         smf::carve_range((uint8_t*)ctx->meta.p, nranges, m)};
   SM_CHECK(smf::launch_range_plan(a, s));
-  if (m) {
-    // every slot's output offset is relative to the edge slots (smf_range.hip, k_range_slots)
-    SM_PASS(sm_uncompress_batch_device(ctx->sm, d_in ? d_in : a.edge, a.s.in_off, a.s.dec_len, m, a.edge, a.s.out_off,
-                                       a.s.cap, a.s.dec_out_len, a.s.dec_status, stream));
-    SM_CHECK(smf::launch_range_copy(a, s));
-    SM_CHECK(smf::launch_crc32c(a.edge, a.s.out_off, a.s.cap, m, a.s.crc_out, 1, (const smf::CrcLut*)ctx->lut.p, s));
-    SM_CHECK(smf::launch_range_trim(a, s));
-  }
-  SM_CHECK(smf::launch_range_verdicts(a, s));
+  // every slot's output offset is relative to the edge slots (smf_range.hip, k_range_slots)
+  SM_PASS(slot_stage(ctx, d_in ? d_in : a.edge, a.edge, a.s.slots, m, s));
+  SM_CHECK(smf::launch_range_trim(a, s));
+  SM_CHECK(smf::launch_group_result(a.s.slots,
+                                    smf::Groups{nranges, a.s.hdr, a.s.rpre, d_len, false, d_out_len, d_range_status}, s));
   return SM_OK;
 }
 
@@ -347,18 +356,15 @@ sm_status smf_uncompress_streams_device(smf_ctx* ctx, const uint8_t* d_in, const
   hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(ctx->device);
   const uint32_t m = max_chunks;
-  SM_CHECK(ctx->smeta.ensure(smf::decode_streams_bytes(nstreams, m)));
-  const smf::DecodeStreamsArgs a{d_in,      d_in_off,  d_in_len,   nstreams, m,
-                                 d_out,     d_out_off, d_out_cap,  d_out_len, d_status,
-                                 d_chunk_first, d_chunk_status, smf::carve_decode_streams((uint8_t*)ctx->smeta.p, nstreams, m)};
+  SM_CHECK(ctx->meta.ensure(smf::decode_streams_bytes(nstreams, m)));
+  smf::DecodeStreamsArgs a{d_in,  d_in_off,  d_in_len,  nstreams,      m,
+                           d_out, d_out_off, d_out_cap, d_chunk_first,
+                           smf::carve_decode_streams((uint8_t*)ctx->meta.p, nstreams, m)};
+  if (d_chunk_status) a.s.slots.slot_status = d_chunk_status;  // (the verdicts, where the caller wants them)
   SM_CHECK(smf::launch_streams_plan(a, s));
-  if (m) {
-    SM_PASS(sm_uncompress_batch_device(ctx->sm, d_in, a.s.ch.pay_off, a.s.dec_len, m, d_out, a.s.out_off, a.s.cap,
-                                       a.s.dec_out_len, a.s.dec_status, stream));
-    SM_CHECK(smf::launch_frame_copy(d_in, a.s.ch, m, a.s.out_off, a.s.cap, d_out, s));
-    SM_CHECK(smf::launch_crc32c(d_out, a.s.out_off, a.s.cap, m, a.s.crc_out, 1, (const smf::CrcLut*)ctx->lut.p, s));
-  }
-  SM_CHECK(smf::launch_streams_verdicts(a, s));
+  SM_PASS(slot_stage(ctx, d_in, d_out, a.s.slots, m, s));
+  SM_CHECK(smf::launch_group_result(a.s.slots, smf::Groups{nstreams, a.s.hdr, a.s.pre, a.s.length, true, d_out_len, d_status},
+                                    s));
   return SM_OK;
 }
 
@@ -372,11 +378,11 @@ sm_status smf_compress_streams_device(smf_ctx* ctx, const uint8_t* d_in, const u
   hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(ctx->device);
   const uint32_t m = max_blocks;
-  SM_CHECK(ctx->smeta.ensure(smf::compress_streams_bytes(nstreams, m)));
+  SM_CHECK(ctx->meta.ensure(smf::compress_streams_bytes(nstreams, m)));
   SM_CHECK(ctx->slots.ensure(smf::compress_streams_slot_bytes(m)));
   const smf::CompressStreamsArgs a{d_in,  d_in_off,  d_in_len,  nstreams, m, (const uint8_t*)ctx->slots.p,
                                    d_out, d_out_off, d_out_len, d_status,
-                                   smf::carve_compress_streams((uint8_t*)ctx->smeta.p, nstreams, m)};
+                                   smf::carve_compress_streams((uint8_t*)ctx->meta.p, nstreams, m)};
   SM_CHECK(smf::launch_cstreams_plan(a, s));
   if (m) {
     SM_PASS(sm_compress_batch_device(ctx->sm, d_in, a.s.in_off, a.s.in_len, m, (uint8_t*)ctx->slots.p, a.s.slot_off,
@@ -392,7 +398,7 @@ sm_status smf_index_device(smf_ctx* ctx, const uint8_t* d_in, uint64_t n, const 
   if (!ctx || !d_summary || (n && !d_in)) return SM_ERR_ARGUMENT;
   smf_chunks none{nullptr, nullptr, nullptr, nullptr, nullptr};
   if (d_chunks && max_chunks == 0) d_chunks = &none;  // (nothing is stored; more than 0 chunks is still too small)
-  if (d_chunks && max_chunks && !valid_chunks(*d_chunks)) return SM_ERR_ARGUMENT;
+  if (d_chunks && max_chunks && !smf::valid_chunks(*d_chunks)) return SM_ERR_ARGUMENT;
   DeviceGuard g(ctx->device);
   SM_CHECK(smf::launch_frame_index(d_in, n, d_chunks, max_chunks, d_summary, (hipStream_t)stream));
   return SM_OK;
@@ -412,22 +418,22 @@ sm_status smf_uncompress_chunks_device(smf_ctx* ctx, const uint8_t* d_in, const 
                                        uint32_t nchunks, uint8_t* d_out, uint64_t out_capacity,
                                        int32_t* d_chunk_status, uint64_t* d_out_len, int32_t* d_status, void* stream) {
   if (!ctx || !d_out_len || !d_status) return SM_ERR_ARGUMENT;
-  smf_chunks ch{nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (nchunks) {
-    if (!d_in || !d_out || !d_chunk_status || !d_chunks) return SM_ERR_ARGUMENT;
-    ch = *d_chunks;
-    if (!valid_chunks(ch)) return SM_ERR_ARGUMENT;
-  }
+  smf_chunks ch;
+  if (nchunks && (!d_in || !d_out || !d_chunk_status)) return SM_ERR_ARGUMENT;
+  if (!smf::take_chunks(d_chunks, nchunks, ch)) return SM_ERR_ARGUMENT;
   hipStream_t s = (hipStream_t)stream;
   DeviceGuard g(ctx->device);
-  SM_CHECK(ctx->dmeta.ensure(decode_bytes(nchunks)));
-  const DecodeMeta m = carve_decode((uintptr_t)ctx->dmeta.p, nchunks);
-  SM_CHECK(smf::launch_frame_plan(ch, nchunks, out_capacity, m.out_off, m.cap, m.dec_len, m.pre, d_out_len, s));
-  SM_PASS(sm_uncompress_batch_device(ctx->sm, d_in, ch.pay_off, m.dec_len, nchunks, d_out, m.out_off, m.cap,
-                                     m.dec_out_len, m.dec_status, stream));
-  SM_CHECK(smf::launch_frame_copy(d_in, ch, nchunks, m.out_off, m.cap, d_out, s));
-  SM_CHECK(smf::launch_crc32c(d_out, m.out_off, m.cap, nchunks, m.crc_out, 1, (const smf::CrcLut*)ctx->lut.p, s));
-  SM_CHECK(smf::launch_frame_verify(ch, nchunks, m.pre, m.dec_status, m.crc_out, d_chunk_status, d_status, s));
+  smf::Slots sl;
+  SM_CHECK(ctx->meta.ensure(carve_chunk_slots(0, nchunks, sl)));
+  carve_chunk_slots((uintptr_t)ctx->meta.p, nchunks, sl);
+  // the caller's index is the slots' (a chunk that is not decoded has no room, so its copy moves nothing)
+  sl.type = ch.type;
+  sl.in_off = ch.pay_off;
+  sl.crc_want = ch.crc;
+  sl.slot_status = d_chunk_status;
+  SM_CHECK(smf::launch_frame_plan(ch, nchunks, out_capacity, sl, d_out_len, s));
+  SM_PASS(slot_stage(ctx, d_in, d_out, sl, nchunks, s));
+  SM_CHECK(smf::launch_group_result(sl, smf::Groups{1, nullptr, nullptr, nullptr, false, nullptr, d_status}, s));
   return SM_OK;
 }
 
@@ -475,12 +481,7 @@ sm_status smf_compress(smf_ctx* ctx, const uint8_t* input, size_t n, uint8_t* fr
   LenStatus* d = &((Results*)ctx->res.p)->io;
   SM_PASS(smf_compress_device(ctx, (const uint8_t*)ctx->io_in.p, n, (uint8_t*)ctx->io_out.p, need, &d->len, &d->st, mode,
                               s));
-  LenStatus r;
-  SM_PASS(read_back(d, r, s));
-  if (r.len > need) return SM_ERR_DEVICE;
-  SM_CHECK(hipMemcpy(framed, ctx->io_out.p, r.len, hipMemcpyDeviceToHost));
-  *framed_length = (size_t)r.len;
-  return SM_OK;
+  return finish(ctx, d, need, false, framed, framed_length, s);
 }
 
 // host index, upload, decode; output == null validates only (the decode goes to scratch)
@@ -492,11 +493,9 @@ static sm_status uncompress_host(smf_ctx* ctx, const uint8_t* framed, size_t n, 
     return SM_BUFFER_TOO_SMALL;
   }
   const uint32_t nc = sum.nchunks;
-  std::vector<uint8_t> type(nc);
-  std::vector<uint64_t> pay_off(nc);
-  std::vector<uint32_t> pay_len(nc), crc(nc), ulen(nc);
-  const smf_chunks h{type.data(), pay_off.data(), pay_len.data(), crc.data(), ulen.data()};
-  SM_PASS(smf_index(framed, n, &h, nc, &sum));
+  HostIndex hx;
+  SM_PASS(hx.fill(framed, n, nc));
+  const smf_chunks h = hx.view();
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
   hipStream_t s = ctx->stream;
@@ -509,11 +508,7 @@ static sm_status uncompress_host(smf_ctx* ctx, const uint8_t* framed, size_t n, 
   LenStatus* d = &((Results*)ctx->res.p)->io;
   SM_PASS(smf_uncompress_chunks_device(ctx, (const uint8_t*)ctx->io_in.p, &ix.ch, nc, (uint8_t*)ctx->io_out.p,
                                        sum.total_length, ix.chunk_status, &d->len, &d->st, s));
-  LenStatus r;
-  SM_PASS(read_back(d, r, s));
-  if (output && r.len) SM_CHECK(hipMemcpy(output, ctx->io_out.p, r.len, hipMemcpyDeviceToHost));
-  if (length) *length = (size_t)r.len;
-  return SM_OK;
+  return finish(ctx, d, sum.total_length, false, output, length, s);
 }
 
 sm_status smf_uncompress(smf_ctx* ctx, const uint8_t* framed, size_t n, uint8_t* output, size_t* length) {
@@ -539,12 +534,13 @@ sm_status smf_uncompress_range(smf_ctx* ctx, const uint8_t* framed, size_t n, ui
   *out_len = 0;
   if (len == 0) return SM_OK;
   const uint32_t nc = sum.nchunks;
-  std::vector<uint8_t> type(nc);
-  std::vector<uint64_t> pay_off(nc), chunk_off((size_t)nc + 1);
-  std::vector<uint32_t> pay_len(nc), crc(nc), ulen(nc);
-  const smf_chunks h{type.data(), pay_off.data(), pay_len.data(), crc.data(), ulen.data()};
-  SM_PASS(smf_index(framed, n, &h, nc, &sum));
-  SM_PASS(smf_chunk_offsets(ulen.data(), nc, chunk_off.data()));
+  HostIndex hx;
+  SM_PASS(hx.fill(framed, n, nc));
+  const smf_chunks h = hx.view();
+  std::vector<uint64_t>& pay_off = hx.pay_off;
+  const std::vector<uint32_t>& pay_len = hx.pay_len;
+  std::vector<uint64_t> chunk_off((size_t)nc + 1);
+  SM_PASS(smf_chunk_offsets(hx.ulen.data(), nc, chunk_off.data()));
   // the touched chunks [f, f + k), their bytes in the stream, and the index slice rebased to them
   const smf::RangeChunks rc = smf::range_chunks(chunk_off.data(), nc, lo, len);
   if (rc.status != SM_OK || rc.count == 0) return SM_ERR_ARGUMENT;
@@ -570,12 +566,8 @@ sm_status smf_uncompress_range(smf_ctx* ctx, const uint8_t* framed, size_t n, ui
   SM_CHECK(hipMemcpyAsync(d_arg, arg, sizeof(arg), hipMemcpyHostToDevice, s));
   SM_PASS(smf_uncompress_ranges_device(ctx, (const uint8_t*)ctx->io_in.p, span, &ix.ch, (const uint64_t*)ctx->roff.p, k,
                                        d_arg, d_arg + 1, 1, k, (uint8_t*)ctx->io_out.p, d_arg + 2, &d->len, &d->st, s));
-  LenStatus r;
-  SM_PASS(read_back(d, r, s));  // (also: the pageable uploads above have left their host buffers)
-  if (r.len != len) return SM_ERR_DEVICE;
-  SM_CHECK(hipMemcpy(output, ctx->io_out.p, (size_t)len, hipMemcpyDeviceToHost));
-  *out_len = (size_t)len;
-  return SM_OK;
+  // (the read-back's synchronisation also lets the pageable uploads above leave their host buffers)
+  return finish(ctx, d, len, true, output, out_len, s);
 }
 
 }  // extern "C"

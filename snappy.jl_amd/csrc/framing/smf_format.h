@@ -1,6 +1,6 @@
-// smf_format.h -- the framing format's rules, shared by the host walker (smf_host.cpp) and the
-// one-wave device walker (smf_kernels.hip): one chunk step, written once, so that both give the
-// same status for the same stream.  Not part of the public ABI.
+// smf_format.h -- the framing format's rules, shared by the host walkers (smf_host.cpp) and the
+// one-wave device walkers (smf_kernels.hip, smf_streams.hip): one chunk step and one loop around
+// it, written once, so that all give the same status for the same stream.  Not part of the public ABI.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -120,6 +120,60 @@ SMC_HD inline bool walk_step(Walk& w, const uint8_t* h, uint32_t have, uint64_t 
 SMC_HD inline int32_t walk_status(const Walk& w, bool stored, uint32_t max_chunks) {
   if (w.status != SM_OK) return w.status;
   return stored && w.nchunks > max_chunks ? SM_BUFFER_TOO_SMALL : SM_OK;
+}
+
+// One stream of n bytes, chunk by chunk: the one loop around walk_step.  fetch(pos, have, h) brings
+// the `have` bytes at pos into h -- the only access to the stream, so no byte at n or behind it is
+// read, whatever lies there; entry(k, at, c) gets data chunk k, which starts at byte `at` of the
+// stream's content.
+template <typename Fetch, typename Entry>
+SMC_HD inline Walk walk_stream(uint64_t n, Fetch fetch, Entry entry) {
+  Walk w;
+  uint64_t pos = 0;
+  for (;;) {
+    const uint32_t have = pos < n ? (uint32_t)(n - pos < kHeadBytes ? n - pos : kHeadBytes) : 0u;
+    uint8_t h[kHeadBytes];
+    fetch(pos, have, h);
+    Chunk c;
+    if (!walk_step(w, h, have, pos, n, c)) break;
+    if (c.data) {
+      entry(w.nchunks, w.total, c);
+      ++w.nchunks;
+      w.total += c.ulen;
+    }
+    pos = c.next;
+  }
+  return w;
+}
+
+// the walk's fetch from a host buffer
+struct ByteFetch {
+  const uint8_t* p;
+  void operator()(uint64_t pos, uint32_t have, uint8_t* h) const {
+    for (uint32_t i = 0; i < have; ++i) h[i] = p[pos + i];
+  }
+};
+
+// entry k of an index
+SMC_HD inline void store_chunk(const smf_chunks& ch, uint32_t k, const Chunk& c) {
+  ch.type[k] = c.type;
+  ch.pay_off[k] = c.pay_off;
+  ch.pay_len[k] = c.pay_len;
+  ch.crc[k] = c.crc;
+  ch.ulen[k] = c.ulen;
+}
+
+// an index the caller handed in: every array is there
+inline bool valid_chunks(const smf_chunks& ch) { return ch.type && ch.pay_off && ch.pay_len && ch.crc && ch.ulen; }
+
+// A call's index of n entries into ch: null arrays for none, else the caller's, which has to be
+// there whole (false: SM_ERR_ARGUMENT).
+inline bool take_chunks(const smf_chunks* given, uint64_t n, smf_chunks& ch) {
+  ch = smf_chunks{nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (n == 0) return true;
+  if (!given || !valid_chunks(*given)) return false;
+  ch = *given;
+  return true;
 }
 
 // ---- the encoder rule ---------------------------------------------------------------------------

@@ -82,30 +82,10 @@ uint32_t smf_crc32c_mask(uint32_t crc) { return smf::mask(crc); }
 sm_status smf_index(const uint8_t* buf, size_t n, const smf_chunks* chunks, uint32_t max_chunks,
                     smf_summary* summary) {
   if (!summary || (!buf && n)) return SM_ERR_ARGUMENT;
-  if (chunks && max_chunks && (!chunks->type || !chunks->pay_off || !chunks->pay_len || !chunks->crc || !chunks->ulen))
-    return SM_ERR_ARGUMENT;
-  smf::Walk w;
-  uint64_t pos = 0;
-  for (;;) {
-    uint8_t head[smf::kHeadBytes];
-    const uint32_t have = (uint32_t)(n - pos < smf::kHeadBytes ? n - pos : smf::kHeadBytes);
-    for (uint32_t i = 0; i < have; ++i) head[i] = buf[pos + i];
-    smf::Chunk c;
-    if (!smf::walk_step(w, head, have, pos, n, c)) break;
-    if (c.data) {
-      if (chunks && w.nchunks < max_chunks) {
-        const uint32_t k = w.nchunks;
-        chunks->type[k] = c.type;
-        chunks->pay_off[k] = c.pay_off;
-        chunks->pay_len[k] = c.pay_len;
-        chunks->crc[k] = c.crc;
-        chunks->ulen[k] = c.ulen;
-      }
-      ++w.nchunks;
-      w.total += c.ulen;
-    }
-    pos = c.next;
-  }
+  if (chunks && max_chunks && !smf::valid_chunks(*chunks)) return SM_ERR_ARGUMENT;
+  const smf::Walk w = smf::walk_stream(n, smf::ByteFetch{buf}, [&](uint32_t k, uint64_t, const smf::Chunk& c) {
+    if (chunks && k < max_chunks) smf::store_chunk(*chunks, k, c);
+  });
   summary->total_length = w.total;
   summary->nchunks = w.nchunks;
   summary->status = smf::walk_status(w, chunks != nullptr, max_chunks);
@@ -141,15 +121,15 @@ sm_status smf_range_plan(const smf_chunks* chunks, const uint64_t* chunk_off, ui
                          uint32_t* first, uint32_t* count, int32_t* status, uint64_t* total) {
   if (!chunk_off || nchunks > smf::kMaxIndexChunks || nranges > smf::kMaxIndexChunks) return SM_ERR_ARGUMENT;
   if (nranges && (!lo || !len)) return SM_ERR_ARGUMENT;
-  if (nchunks && (!chunks || !chunks->type || !chunks->pay_off || !chunks->pay_len || !chunks->crc || !chunks->ulen))
-    return SM_ERR_ARGUMENT;
+  smf_chunks ch;
+  if (!smf::take_chunks(chunks, nchunks, ch)) return SM_ERR_ARGUMENT;
   uint64_t sum = 0;
   for (uint32_t r = 0; r < nranges; ++r) {
     const smf::RangeChunks rc = smf::range_chunks(chunk_off, nchunks, lo[r], len[r]);
     int32_t st = rc.status;
     for (uint32_t k = 0; k < rc.count && st == SM_OK; ++k) {
       bool skip;
-      st = smf::slot_place(*chunks, chunk_off, n, rc.first + k, lo[r], len[r], k == 0, k == rc.count - 1, skip).status;
+      st = smf::slot_place(ch, chunk_off, n, rc.first + k, lo[r], len[r], k == 0, k == rc.count - 1, skip).status;
     }
     if (first) first[r] = rc.first;
     if (count) count[r] = rc.count;
@@ -185,12 +165,7 @@ sm_status smf_streams_plan(const uint8_t* in, const uint64_t* in_off, const uint
   uint64_t sum = 0;
   for (uint32_t r = 0; r < nstreams; ++r) {
     const uint8_t* const p = in_len[r] ? in + in_off[r] : nullptr;
-    const smf::Walk w = smf::walk_stream(
-        in_len[r],
-        [p](uint64_t pos, uint32_t have, uint8_t* h) {
-          for (uint32_t i = 0; i < have; ++i) h[i] = p[pos + i];
-        },
-        [](uint32_t, uint64_t, const smf::Chunk&) {});
+    const smf::Walk w = smf::walk_stream(in_len[r], smf::ByteFetch{p}, [](uint32_t, uint64_t, const smf::Chunk&) {});
     const smf::StreamPlan sp = smf::stream_plan(w, out_cap ? out_cap[r] : UINT64_MAX);
     if (first) first[r] = sum > 0xffffffffull ? 0xffffffffu : (uint32_t)sum;
     if (out_len) out_len[r] = sp.length;

@@ -3,8 +3,8 @@
 // stream's size, so a walker that reads past a cut stream trips the sanitizer; the batched decode's
 // plan (smf_streams_plan) runs over the same cases laid directly behind one another.  It also runs the
 // CRC kernel's arithmetic (k_crc32c: the tables, the per-lane granule steps, the x^(128 t)
-// multipliers) lane by lane on the CPU against the bytewise CRC, and the kernels' shared byte
-// mover (smc::copy_bytes) thread by thread.
+// multipliers) lane by lane on the CPU against the bytewise CRC, the slot stage's two verdict rules
+// (smf_slots.h) against a table, and the kernels' shared byte mover (smc::copy_bytes) thread by thread.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,6 +14,7 @@
 #include "../common/smc_device.h"
 #include "smf_format.h"
 #include "smf_range.h"
+#include "smf_slots.h"
 #include "smf_streams.h"
 
 namespace {
@@ -407,6 +408,61 @@ void streams_cases() {
          "streams scratch bytes");
 }
 
+// ---- the slot stage's verdict rules (smf_slots.h), the functions the kernels run -------------------
+// Every combination against a table written out here, row by row: why the slot was not decoded
+// wins, then the raw decoder's status for a 0x00 chunk, then the CRC; over the bound wins for a
+// group, then its plan's status, then its first failing slot's.
+void verdict_cases() {
+  const int32_t OK = SM_OK, ARG = SM_ERR_ARGUMENT, SMALL = SM_BUFFER_TOO_SMALL, LARGE = SMF_ERR_CHUNK_TOO_LARGE,
+                DEC = SM_ERR_VARINT, CRC = SMF_ERR_CRC;
+  const struct {
+    int32_t pre;
+    uint32_t type;
+    int32_t dec;
+    bool crc_differs;
+    int32_t want;
+  } slot[] = {
+      {OK, 0, OK, false, OK},       {OK, 0, OK, true, CRC},       {OK, 0, DEC, false, DEC},      {OK, 0, DEC, true, DEC},
+      {OK, 1, OK, false, OK},       {OK, 1, OK, true, CRC},       {OK, 1, DEC, false, OK},       {OK, 1, DEC, true, CRC},
+      {ARG, 0, OK, false, ARG},     {ARG, 0, OK, true, ARG},      {ARG, 0, DEC, false, ARG},     {ARG, 0, DEC, true, ARG},
+      {ARG, 1, OK, false, ARG},     {ARG, 1, OK, true, ARG},      {ARG, 1, DEC, false, ARG},     {ARG, 1, DEC, true, ARG},
+      {SMALL, 0, OK, false, SMALL}, {SMALL, 0, OK, true, SMALL},  {SMALL, 0, DEC, false, SMALL}, {SMALL, 0, DEC, true, SMALL},
+      {SMALL, 1, OK, false, SMALL}, {SMALL, 1, OK, true, SMALL},  {SMALL, 1, DEC, false, SMALL}, {SMALL, 1, DEC, true, SMALL},
+      {LARGE, 0, OK, false, LARGE}, {LARGE, 0, OK, true, LARGE},  {LARGE, 0, DEC, false, LARGE}, {LARGE, 0, DEC, true, LARGE},
+      {LARGE, 1, OK, false, LARGE}, {LARGE, 1, OK, true, LARGE},  {LARGE, 1, DEC, false, LARGE}, {LARGE, 1, DEC, true, LARGE},
+  };
+  static_assert(sizeof(slot) / sizeof(slot[0]) == 4 * 2 * 2 * 2, "every combination");
+  for (const auto& r : slot) {
+    const uint32_t want_crc = 0x12345678u;
+    const int32_t got = smf::slot_verdict(r.pre, r.type, r.dec, r.crc_differs ? ~want_crc : want_crc, want_crc);
+    if (got != r.want) {
+      std::printf("FAIL slot_verdict(pre %d, type %u, dec %d, crc %s): %d, want %d\n", r.pre, r.type, r.dec,
+                  r.crc_differs ? "differs" : "equal", got, r.want);
+      ++failures;
+    }
+  }
+  const int32_t TRUNC = SMF_ERR_TRUNCATED;
+  const struct {
+    bool over;
+    int32_t pre;
+    bool failed;  // a slot failed, with SMF_ERR_CRC; else the slot status handed in is never looked at
+    int32_t want;
+  } group[] = {
+      {false, OK, false, OK},     {false, OK, true, CRC},     {false, TRUNC, false, TRUNC}, {false, TRUNC, true, TRUNC},
+      {true, OK, false, ARG},     {true, OK, true, ARG},      {true, TRUNC, false, ARG},    {true, TRUNC, true, ARG},
+  };
+  static_assert(sizeof(group) / sizeof(group[0]) == 2 * 2 * 2, "every combination");
+  for (const auto& r : group) {
+    const int32_t got = smf::group_verdict(r.over, r.pre, r.failed ? 3u : smf::kNoSlot, r.failed ? CRC : DEC);
+    if (got != r.want) {
+      std::printf("FAIL group_verdict(over %d, pre %d, %s): %d, want %d\n", r.over, r.pre, r.failed ? "a failing slot" : "none",
+                  got, r.want);
+      ++failures;
+    }
+  }
+  expect(smf::group_verdict(false, OK, 0u, CRC) == CRC, "group_verdict: slot 0 fails");
+}
+
 // ---- the shared byte mover (../common/smc_device.h), every tid one after another ----------------
 // The source is a heap block that ends exactly at src + n, so a read past the end trips the
 // sanitizer; the function's own assert (host build) holds every 16-byte load to an aligned address
@@ -546,6 +602,7 @@ int main() {
   expect(smf::host_message(SMF_ERR_CRC) != nullptr && smf::host_message(SM_OK) == nullptr, "messages");
   range_cases();
   streams_cases();
+  verdict_cases();
   copy_bytes_cases();
 
   if (failures) {

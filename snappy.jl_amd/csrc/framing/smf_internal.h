@@ -1,6 +1,6 @@
 // smf_internal.h -- launcher interfaces between the framing C ABI (smf_api.hip) and its kernels
-// (smf_kernels.hip, smf_range.hip, smf_streams.hip).  Not part of the public ABI.  All pointers are
-// device pointers.
+// (smf_kernels.hip, smf_range.hip, smf_streams.hip; their shared device helpers: smf_device.h).
+// Not part of the public ABI.  All pointers are device pointers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,6 +8,7 @@
 #include "../common/smc_device.h"
 #include "smf_format.h"
 #include "smf_range.h"
+#include "smf_slots.h"
 #include "smf_streams.h"
 
 namespace smf {
@@ -34,22 +35,6 @@ struct PackArgs {
 };
 hipError_t launch_frame_pack(const PackArgs& a, uint64_t* out_len, int32_t* status, hipStream_t s);
 
-// One chunk at d, by the workgroups (blockIdx.x, *) of k_frame_pack and k_streams_pack: the header
-// and the CRC field, then the payload -- the block's Snappy stream (0x00) or the block (0x01);
-// blockIdx.y strides the payload.  Nothing for a block with an error mark.
-__device__ inline void pack_chunk(uint32_t type, const uint8_t* __restrict__ block, uint32_t n,
-                                  const uint8_t* __restrict__ comp, uint32_t c, uint32_t crc, uint8_t* __restrict__ d) {
-  if (type == kTypeNone) return;
-  const uint32_t t = threadIdx.x;
-  const uint32_t pl = type == SMF_CHUNK_COMPRESSED ? c : n;
-  if (blockIdx.y == 0 && t < 8) {
-    const uint32_t L = pl + 4;
-    d[t] = t == 0 ? (uint8_t)type : (t < 4 ? (uint8_t)(L >> (8 * (t - 1))) : (uint8_t)(crc >> (8 * (t - 4))));
-  }
-  smc::copy_bytes(type == SMF_CHUNK_COMPRESSED ? comp : block, pl, d + 8, blockIdx.y * blockDim.x + t,
-                  gridDim.y * blockDim.x);
-}
-
 // index: ch == null counts only
 hipError_t launch_frame_index(const uint8_t* in, uint64_t n, const smf_chunks* ch, uint32_t max_chunks, smf_summary* sum,
                               hipStream_t s);
@@ -57,13 +42,13 @@ hipError_t launch_frame_index(const uint8_t* in, uint64_t n, const smf_chunks* c
 hipError_t launch_frame_result(uint64_t* d_len, uint64_t len, const smf_summary* sum, int32_t* d_status, int32_t status,
                                hipStream_t s);
 
-// uncompress: places and the raw decoder's arguments; the 0x01 chunks' copies; the verdicts
-hipError_t launch_frame_plan(const smf_chunks& ch, uint32_t nchunks, uint64_t out_capacity, uint64_t* out_off,
-                             uint32_t* cap, uint32_t* dec_len, int32_t* pre, uint64_t* out_len, hipStream_t s);
-hipError_t launch_frame_copy(const uint8_t* in, const smf_chunks& ch, uint32_t nchunks, const uint64_t* out_off,
-                             const uint32_t* cap, uint8_t* out, hipStream_t s);
-hipError_t launch_frame_verify(const smf_chunks& ch, uint32_t nchunks, const int32_t* pre, const int32_t* dec_status,
-                               const uint32_t* crc_out, int32_t* chunk_status, int32_t* status, hipStream_t s);
+// smf_uncompress_chunks_device's plan: places, the raw decoder's arguments and pre; *sl.fail = none
+hipError_t launch_frame_plan(const smf_chunks& ch, uint32_t nchunks, uint64_t out_capacity, const Slots& sl,
+                             uint64_t* out_len, hipStream_t s);
+// the slot stage's own kernels (m > 0): the 0x01 slots' copies, the slots' verdicts; then the groups'
+hipError_t launch_slot_copy(const uint8_t* in, uint8_t* out_base, const Slots& sl, uint32_t m, hipStream_t s);
+hipError_t launch_slot_verify(const Slots& sl, uint32_t m, hipStream_t s);
+hipError_t launch_group_result(const Slots& sl, const Groups& g, hipStream_t s);
 
 // ---- smf_range.hip: the seek index and the ranged decode ------------------------------------
 // chunk_off[0, nchunks] = the exclusive scan of ulen
@@ -83,18 +68,13 @@ struct RangeArgs {
   uint32_t nranges, m;  // m = max_range_chunks: the slots
   uint8_t* out;
   const uint64_t* out_off;
-  uint64_t* out_len;
-  int32_t* range_status;
   uint8_t* edge;  // 2 nranges edge slots of kEdgePitch bytes: the raw decoder's and the CRC pass's base
   RangeScratch s;
 };
 // per range its chunks, the scan of the counts against m, per slot the raw decoder's arguments
 hipError_t launch_range_plan(const RangeArgs& a, hipStream_t s);
-// behind the raw decoder: the 0x01 chunks' copies; behind the CRC pass: the edge slots' covered bytes
-hipError_t launch_range_copy(const RangeArgs& a, hipStream_t s);
+// behind the slot stage: the edge slots' covered bytes
 hipError_t launch_range_trim(const RangeArgs& a, hipStream_t s);
-// per slot and, segmented by range, per range
-hipError_t launch_range_verdicts(const RangeArgs& a, hipStream_t s);
 
 // ---- smf_streams.hip: a batch of framed streams per call -------------------------------------
 struct DecodeStreamsArgs {
@@ -103,16 +83,11 @@ struct DecodeStreamsArgs {
   uint32_t nstreams, m;  // m = max_chunks: the slots
   uint8_t* out;
   const uint64_t *out_off, *out_cap;
-  uint64_t* out_len;
-  int32_t* status;
-  uint32_t* chunk_first;  // optional, with chunk_status
-  int32_t* chunk_status;
+  uint32_t* chunk_first;  // optional
   DecodeStreams s;
 };
 // the counting walk, the scan of the slots against m, the storing walk and the unused slots
 hipError_t launch_streams_plan(const DecodeStreamsArgs& a, hipStream_t s);
-// behind the raw decoder, the copies and the CRC pass: per slot, then segmented by stream
-hipError_t launch_streams_verdicts(const DecodeStreamsArgs& a, hipStream_t s);
 
 struct CompressStreamsArgs {
   const uint8_t* in;

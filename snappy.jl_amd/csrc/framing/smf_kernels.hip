@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../common/smc_device.h"
+#include "smf_device.h"
 #include "smf_format.h"
 #include "smf_internal.h"
 
@@ -172,8 +173,10 @@ hipError_t launch_frame_pack(const PackArgs& a, uint64_t* out_len, int32_t* stat
 
 // ---- index ---------------------------------------------------------------------------------------
 // One wave walks the chunk chain.  A step's bytes (header, CRC, varint: kHeadBytes) come in by one
-// load, a byte a lane, and every lane then takes the same step (walk_step, shared with the host
-// walker), so a chunk costs one dependent load.  stored == 0: count only.
+// load, a byte a lane, and every lane then takes the same step, so a chunk costs one dependent load.
+// The loop and the fetch are walk_stream's and WaveFetch's, written out: through them the compiler
+// turns the varint's branches into selects on the dependent chain, and smf_uncompress_device's walk
+// of 10,000 chunks measured 0.13 ms (1 %) slower than this form.  stored == 0: count only.
 __global__ __launch_bounds__(64) void k_frame_index(const uint8_t* __restrict__ in, uint64_t n, smf_chunks ch, int stored,
                                                     uint32_t max_chunks, smf_summary* sum) {
   const uint32_t lane = lane_id();
@@ -188,14 +191,7 @@ __global__ __launch_bounds__(64) void k_frame_index(const uint8_t* __restrict__ 
     Chunk c;
     if (!walk_step(w, h, have, pos, n, c)) break;
     if (c.data) {
-      if (stored && w.nchunks < max_chunks && lane == 0) {
-        const uint32_t k = w.nchunks;
-        ch.type[k] = c.type;
-        ch.pay_off[k] = c.pay_off;
-        ch.pay_len[k] = c.pay_len;
-        ch.crc[k] = c.crc;
-        ch.ulen[k] = c.ulen;
-      }
+      if (stored && w.nchunks < max_chunks && lane == 0) store_chunk(ch, w.nchunks, c);
       ++w.nchunks;
       w.total += c.ulen;
     }
@@ -237,79 +233,79 @@ hipError_t launch_frame_result(uint64_t* d_len, uint64_t len, const smf_summary*
 // not decoded): the decoder's capacity and the CRC pass's length.  dec_len[c] = the payload's length
 // for a 0x00 chunk to decode, else 0 -- the raw decoder returns at once on an empty stream
 // (its status for that chunk is not looked at).
-__global__ __launch_bounds__(256) void k_frame_plan(smf_chunks ch, uint32_t nchunks, uint64_t out_capacity,
-                                                    uint64_t* out_off, uint32_t* cap, uint32_t* dec_len, int32_t* pre,
+__global__ __launch_bounds__(256) void k_frame_plan(smf_chunks ch, uint32_t nchunks, uint64_t out_capacity, Slots s,
                                                     uint64_t* out_len) {
   __shared__ uint64_t sh[4];
-  uint64_t carry = 0;
-  for (uint32_t base = 0; base < nchunks; base += 256) {
-    const uint32_t c = base + threadIdx.x;
-    const uint32_t u = c < nchunks ? ch.ulen[c] : 0u;
-    uint64_t total;
-    const uint64_t ex = block_scan(u, sh, total);
-    if (c < nchunks) {
-      const uint32_t ty = ch.type[c], pl = ch.pay_len[c];
-      const uint64_t at = carry + ex;
-      int32_t st = SM_OK;
-      if (ty > SMF_CHUNK_UNCOMPRESSED) st = SM_ERR_ARGUMENT;
-      else if (u > kBlock || (ty == SMF_CHUNK_UNCOMPRESSED && pl != u)) st = SMF_ERR_CHUNK_TOO_LARGE;
-      else if (at > out_capacity || out_capacity - at < u) st = SM_BUFFER_TOO_SMALL;
-      out_off[c] = at;
-      pre[c] = st;
-      cap[c] = st == SM_OK ? u : 0u;
-      dec_len[c] = st == SM_OK && ty == SMF_CHUNK_COMPRESSED ? pl : 0u;
-    }
-    carry += total;
+  const uint64_t total = tile_scan(nchunks, sh, [&](uint32_t c) { return ch.ulen[c]; }, [&](uint32_t c, uint64_t ulen, uint64_t o) {
+    const uint32_t ty = ch.type[c], pl = ch.pay_len[c], u = (uint32_t)ulen;
+    int32_t st = SM_OK;
+    if (ty > SMF_CHUNK_UNCOMPRESSED) st = SM_ERR_ARGUMENT;
+    else if (u > kBlock || (ty == SMF_CHUNK_UNCOMPRESSED && pl != u)) st = SMF_ERR_CHUNK_TOO_LARGE;
+    else if (o > out_capacity || out_capacity - o < u) st = SM_BUFFER_TOO_SMALL;
+    s.out_off[c] = o;
+    s.pre[c] = st;
+    s.cap[c] = st == SM_OK ? u : 0u;
+    s.dec_len[c] = st == SM_OK && ty == SMF_CHUNK_COMPRESSED ? pl : 0u;
+  });
+  if (threadIdx.x == 0) {
+    *out_len = total;
+    s.fail[0] = kNoSlot;
   }
-  if (threadIdx.x == 0) *out_len = carry;
 }
 
-// 0x01 chunks: the payload is the output
-__global__ __launch_bounds__(256) void k_frame_copy(const uint8_t* __restrict__ in, smf_chunks ch, const uint64_t* out_off,
-                                                    const uint32_t* cap, uint8_t* __restrict__ out) {
-  const uint32_t c = blockIdx.x;
-  if (ch.type[c] != SMF_CHUNK_UNCOMPRESSED) return;
-  copy_bytes(in + ch.pay_off[c], cap[c], out + out_off[c], blockIdx.y * blockDim.x + threadIdx.x,
+// ---- the slot stage (smf_slots.h) -----------------------------------------------------------------
+// 0x01 slots: the payload is the output.  blockIdx.x = the slot, blockIdx.y strides the payload.
+__global__ __launch_bounds__(256) void k_slot_copy(const uint8_t* __restrict__ in, uint8_t* __restrict__ out_base,
+                                                   Slots s) {
+  const uint32_t j = blockIdx.x;
+  if (s.type[j] != SMF_CHUNK_UNCOMPRESSED) return;
+  copy_bytes(in + s.in_off[j], s.cap[j], at(out_base, s.out_off[j]), blockIdx.y * blockDim.x + threadIdx.x,
              gridDim.y * blockDim.x);
 }
 
-// Per chunk: why it was not decoded, else the raw decoder's status (0x00), else the CRC's verdict.
-// *status = the first failing chunk's, by one workgroup.
-__global__ __launch_bounds__(256) void k_frame_verify(smf_chunks ch, uint32_t nchunks, const int32_t* pre,
-                                                      const int32_t* dec_status, const uint32_t* crc_out,
-                                                      int32_t* chunk_status, int32_t* status) {
-  __shared__ uint32_t first;
-  if (threadIdx.x == 0) first = 0xffffffffu;
-  __syncthreads();
-  uint32_t mine = 0xffffffffu;
-  for (uint32_t c = threadIdx.x; c < nchunks; c += 256) {
-    int32_t st = pre[c];
-    if (st == SM_OK && ch.type[c] == SMF_CHUNK_COMPRESSED) st = dec_status[c];
-    if (st == SM_OK && crc_out[c] != ch.crc[c]) st = SMF_ERR_CRC;
-    chunk_status[c] = st;
-    if (st != SM_OK) mine = min(mine, c);
+// Per slot its verdict (slot_verdict); a failing slot enters its group's minimum.
+__global__ __launch_bounds__(256) void k_slot_verify(Slots s, uint32_t m) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const uint32_t g = s.group ? s.group[j] : 0u;
+  int32_t st = SM_OK;
+  if (g != kNoSlot) {
+    st = slot_verdict(s.pre ? s.pre[j] : (int32_t)SM_OK, s.type[j], s.dec_status[j], s.crc_out[j], s.crc_want[j]);
+    if (st != SM_OK) atomicMin(&s.fail[g], j);
   }
-  if (mine != 0xffffffffu) atomicMin(&first, mine);
-  __syncthreads();
-  if (threadIdx.x == 0) *status = first == 0xffffffffu ? SM_OK : chunk_status[first];
+  s.slot_status[j] = st;
 }
 
-hipError_t launch_frame_plan(const smf_chunks& ch, uint32_t nchunks, uint64_t out_capacity, uint64_t* out_off,
-                             uint32_t* cap, uint32_t* dec_len, int32_t* pre, uint64_t* out_len, hipStream_t s) {
-  hipLaunchKernelGGL(k_frame_plan, dim3(1), dim3(256), 0, s, ch, nchunks, out_capacity, out_off, cap, dec_len, pre, out_len);
+// Per group its status (group_verdict) and the length it reports.
+__global__ __launch_bounds__(256) void k_group_result(Slots s, Groups g) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= g.n) return;
+  const bool over = g.hdr && g.hdr->over;
+  const uint32_t f = s.fail[r];
+  const int32_t st =
+      group_verdict(over, g.pre ? g.pre[r] : (int32_t)SM_OK, f, f != kNoSlot ? s.slot_status[f] : (int32_t)SM_OK);
+  g.status[r] = st;
+  if (g.out_len) g.out_len[r] = over || (st != SM_OK && !g.len_on_error) ? 0 : g.len[r];
+}
+
+hipError_t launch_frame_plan(const smf_chunks& ch, uint32_t nchunks, uint64_t out_capacity, const Slots& sl,
+                             uint64_t* out_len, hipStream_t s) {
+  hipLaunchKernelGGL(k_frame_plan, dim3(1), dim3(256), 0, s, ch, nchunks, out_capacity, sl, out_len);
   return hipGetLastError();
 }
 
-hipError_t launch_frame_copy(const uint8_t* in, const smf_chunks& ch, uint32_t nchunks, const uint64_t* out_off,
-                             const uint32_t* cap, uint8_t* out, hipStream_t s) {
-  if (nchunks == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_frame_copy, dim3(nchunks, 4), dim3(256), 0, s, in, ch, out_off, cap, out);
+hipError_t launch_slot_copy(const uint8_t* in, uint8_t* out_base, const Slots& sl, uint32_t m, hipStream_t s) {
+  hipLaunchKernelGGL(k_slot_copy, dim3(m, 4), dim3(256), 0, s, in, out_base, sl);
   return hipGetLastError();
 }
 
-hipError_t launch_frame_verify(const smf_chunks& ch, uint32_t nchunks, const int32_t* pre, const int32_t* dec_status,
-                               const uint32_t* crc_out, int32_t* chunk_status, int32_t* status, hipStream_t s) {
-  hipLaunchKernelGGL(k_frame_verify, dim3(1), dim3(256), 0, s, ch, nchunks, pre, dec_status, crc_out, chunk_status, status);
+hipError_t launch_slot_verify(const Slots& sl, uint32_t m, hipStream_t s) {
+  hipLaunchKernelGGL(k_slot_verify, dim3((m + 255) / 256), dim3(256), 0, s, sl, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_group_result(const Slots& sl, const Groups& g, hipStream_t s) {
+  hipLaunchKernelGGL(k_group_result, dim3((g.n + 255) / 256), dim3(256), 0, s, sl, g);
   return hipGetLastError();
 }
 

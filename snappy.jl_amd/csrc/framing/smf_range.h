@@ -10,11 +10,11 @@
 #include <stdint.h>
 
 #include "smf_format.h"
+#include "smf_slots.h"
 
 namespace smf {
 
 constexpr uint32_t kMaxIndexChunks = 0x7fffffffu;  // a longer index: SM_ERR_ARGUMENT
-constexpr uint32_t kNoSlot = 0xffffffffu;          // a range without a failing slot
 constexpr uint64_t kEdgePitch = kBlock;            // an edge slot: one whole chunk
 
 // How many of off[0, cnt) are <= v, for a non-decreasing off; any other array gives some value in
@@ -119,48 +119,31 @@ SMC_HD inline Place slot_place(const smf_chunks& ch, const uint64_t* chunk_off, 
 }
 
 // ---- scratch (smc::Carve: a null base measures) ------------------------------------------------
-struct RangeHeader {  // the plan's words for the kernels behind it
-  uint32_t total;     // slots in use
-  uint32_t over;      // the ranges touch more than max_range_chunks chunks: nothing is decoded
-};
-
 struct RangeScratch {
-  // per slot (m = max_range_chunks)
-  uint64_t *in_off, *out_off, *trim_dst;
-  uint32_t *dec_len, *cap, *dec_out_len, *crc_out, *crc_want, *trim_src, *trim_len, *range;
-  int32_t *pre, *dec_status, *slot_status;
-  uint8_t* copy;  // 1: a 0x01 chunk, copied
+  GroupHeader* hdr;
+  // per slot (m = max_range_chunks): the stage's arrays (a slot's group is its range; out_off is
+  // relative to the edge slots), and of an edge slot the bytes that go to the range's output
+  Slots slots;
+  uint64_t* trim_dst;
+  uint32_t *trim_src, *trim_len;
   // per range
-  uint32_t *first, *count, *base, *fail;
+  uint32_t *first, *count, *base;
   int32_t* rpre;
-  RangeHeader* hdr;
   uintptr_t end;
 };
 
 inline RangeScratch carve_range(uint8_t* buf, size_t nranges, size_t m) {
   smc::Carve c{reinterpret_cast<uintptr_t>(buf)};
   RangeScratch s;
-  s.hdr = c.take<RangeHeader>(1);
-  s.in_off = c.take<uint64_t>(m);
-  s.out_off = c.take<uint64_t>(m);
+  s.hdr = c.take<GroupHeader>(1);
+  s.slots = carve_slots(c, m, nranges, true, true, true);
   s.trim_dst = c.take<uint64_t>(m);
-  s.dec_len = c.take<uint32_t>(m);
-  s.cap = c.take<uint32_t>(m);
-  s.dec_out_len = c.take<uint32_t>(m);
-  s.crc_out = c.take<uint32_t>(m);
-  s.crc_want = c.take<uint32_t>(m);
   s.trim_src = c.take<uint32_t>(m);
   s.trim_len = c.take<uint32_t>(m);
-  s.range = c.take<uint32_t>(m);
-  s.pre = c.take<int32_t>(m);
-  s.dec_status = c.take<int32_t>(m);
-  s.slot_status = c.take<int32_t>(m);
   s.first = c.take<uint32_t>(nranges);
   s.count = c.take<uint32_t>(nranges);
   s.base = c.take<uint32_t>(nranges + 1);
-  s.fail = c.take<uint32_t>(nranges);
   s.rpre = c.take<int32_t>(nranges);
-  s.copy = c.take<uint8_t>(m);
   s.end = c.p;
   return s;
 }

@@ -1,12 +1,13 @@
 // smf_range.hip -- the seek index and the ranged decode of the framing library: gfx950 kernels and
 // their launchers (smf_range.h).  Plumbing around the raw codec's batched decoder and k_crc32c, as
 // smf_kernels.hip's decode is; the decisions are the shared rules of smf_range.h, taken per range
-// and per slot on the device, so a call needs no host synchronisation.  block_scan, copy_bytes
-// and sat32 are the shared ones of ../common/smc_device.h.
+// and per slot on the device, so a call needs no host synchronisation.  The slot stage behind
+// the plan is the shared one (smf_slots.h); the scans are smf_device.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../common/smc_device.h"
+#include "smf_device.h"
 #include "smf_format.h"
 #include "smf_internal.h"
 #include "smf_range.h"
@@ -15,12 +16,7 @@ namespace smf {
 
 namespace {
 
-using smc::block_scan;
 using smc::copy_bytes;
-using smc::sat32;
-
-// base + off where off may stand for a place before base (the offsets of k_range_slots)
-__device__ inline uint8_t* at(uint8_t* base, uint64_t off) { return (uint8_t*)((uintptr_t)base + off); }
 
 }  // namespace
 
@@ -29,16 +25,9 @@ __device__ inline uint8_t* at(uint8_t* base, uint64_t off) { return (uint8_t*)((
 __global__ __launch_bounds__(256) void k_chunk_offsets(const uint32_t* __restrict__ ulen, uint32_t nchunks,
                                                        uint64_t* __restrict__ chunk_off) {
   __shared__ uint64_t sh[4];
-  uint64_t carry = 0;
-  for (uint32_t base = 0; base < nchunks; base += 256) {  // (uniform: every thread takes every tile)
-    const uint32_t c = base + threadIdx.x;
-    const uint32_t u = c < nchunks ? ulen[c] : 0u;
-    uint64_t total;
-    const uint64_t ex = block_scan(u, sh, total);
-    if (c < nchunks) chunk_off[c] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) chunk_off[nchunks] = carry;
+  const uint64_t total = tile_scan(nchunks, sh, [&](uint32_t c) { return ulen[c]; },
+                                   [&](uint32_t c, uint64_t, uint64_t o) { chunk_off[c] = o; });
+  if (threadIdx.x == 0) chunk_off[nchunks] = total;
 }
 
 hipError_t launch_chunk_offsets(const uint32_t* ulen, uint32_t nchunks, uint64_t* chunk_off, hipStream_t s) {
@@ -82,28 +71,13 @@ __global__ __launch_bounds__(256) void k_range_find(RangeArgs a) {
   a.s.first[r] = rc.first;
   a.s.count[r] = rc.count;
   a.s.rpre[r] = rc.status;
-  a.s.fail[r] = kNoSlot;
+  a.s.slots.fail[r] = kNoSlot;
 }
 
-// base = the exclusive scan of the counts over the ranges, and the compare with max_range_chunks,
-// by one workgroup.  Over the bound the bases are not used (they saturate).
-__global__ __launch_bounds__(256) void k_range_scan(RangeArgs a) {
+// base = the exclusive scan of the counts over the ranges, and the compare with max_range_chunks
+__global__ __launch_bounds__(256) void k_range_counts(RangeArgs a) {
   __shared__ uint64_t sh[4];
-  uint64_t carry = 0;
-  for (uint32_t b0 = 0; b0 < a.nranges; b0 += 256) {
-    const uint32_t r = b0 + threadIdx.x;
-    const uint32_t cnt = r < a.nranges ? a.s.count[r] : 0u;
-    uint64_t total;
-    const uint64_t ex = block_scan(cnt, sh, total);
-    if (r < a.nranges) a.s.base[r] = sat32(carry + ex);
-    carry += total;
-  }
-  if (threadIdx.x == 0) {
-    const bool over = carry > a.m;
-    a.s.base[a.nranges] = sat32(carry);
-    a.s.hdr->over = over ? 1u : 0u;
-    a.s.hdr->total = over ? 0u : (uint32_t)carry;
-  }
+  scan_counts(a.nranges, a.m, [&](uint32_t r) { return a.s.count[r]; }, a.s.base, nullptr, a.s.hdr, sh);
 }
 
 // Slot j: its range (a search in the scanned counts), its chunk, the entry checks, and what the raw
@@ -117,7 +91,7 @@ __global__ __launch_bounds__(256) void k_range_slots(RangeArgs a) {
   uint64_t in_off = 0, out_off = 0, trim_dst = 0;
   uint32_t dec_len = 0, cap = 0, trim_src = 0, trim_len = 0, range = kNoSlot, want = 0;
   int32_t pre = SM_OK;
-  uint8_t copy = 0;
+  uint8_t type = SMF_CHUNK_COMPRESSED;
   if (j < a.s.hdr->total) {
     const uint32_t r = upper_bound(a.s.base, a.nranges + 1, j) - 1;  // base[r] <= j < base[r + 1]
     const uint32_t k = r < a.nranges ? j - a.s.base[r] : kNoSlot, cnt = r < a.nranges ? a.s.count[r] : 0u;
@@ -129,15 +103,14 @@ __global__ __launch_bounds__(256) void k_range_slots(RangeArgs a) {
         range = r;
         pre = p.status;
         if (pre == SM_OK) {
-          const uint8_t ty = a.ch.type[c];
+          type = a.ch.type[c];
           const uint8_t* const target = p.edge ? a.edge + (2 * (uint64_t)r + (p.edge - 1)) * kEdgePitch
                                                : a.out + a.out_off[r] + p.dst;
           out_off = (uint64_t)(uintptr_t)target - (uint64_t)(uintptr_t)a.edge;
           in_off = a.ch.pay_off[c];
           cap = a.ch.ulen[c];
           want = a.ch.crc[c];
-          if (ty == SMF_CHUNK_COMPRESSED) dec_len = a.ch.pay_len[c];
-          else copy = 1;
+          if (type == SMF_CHUNK_COMPRESSED) dec_len = a.ch.pay_len[c];
           if (p.edge) {
             trim_src = p.src;
             trim_len = p.n;
@@ -147,41 +120,27 @@ __global__ __launch_bounds__(256) void k_range_slots(RangeArgs a) {
       }
     }
   }
-  a.s.in_off[j] = in_off;
-  a.s.out_off[j] = out_off;
+  a.s.slots.in_off[j] = in_off;
+  a.s.slots.out_off[j] = out_off;
   a.s.trim_dst[j] = trim_dst;
-  a.s.dec_len[j] = dec_len;
-  a.s.cap[j] = cap;
+  a.s.slots.dec_len[j] = dec_len;
+  a.s.slots.cap[j] = cap;
   a.s.trim_src[j] = trim_src;
   a.s.trim_len[j] = trim_len;
-  a.s.range[j] = range;
-  a.s.crc_want[j] = want;
-  a.s.pre[j] = pre;
-  a.s.copy[j] = copy;
+  a.s.slots.group[j] = range;
+  a.s.slots.crc_want[j] = want;
+  a.s.slots.pre[j] = pre;
+  a.s.slots.type[j] = type;
 }
 
 hipError_t launch_range_plan(const RangeArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_range_find, dim3((a.nranges + 255) / 256), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_range_scan, dim3(1), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_range_counts, dim3(1), dim3(256), 0, s, a);
   if (a.m) hipLaunchKernelGGL(k_range_slots, dim3((a.m + 255) / 256), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
 // ---- behind the raw decoder ----------------------------------------------------------------------
-// 0x01 chunks: the payload is the output, at the direct place or in the edge slot
-__global__ __launch_bounds__(256) void k_range_copy(RangeArgs a) {
-  const uint32_t j = blockIdx.x;
-  if (!a.s.copy[j]) return;
-  copy_bytes(a.in + a.s.in_off[j], a.s.cap[j], at(a.edge, a.s.out_off[j]), blockIdx.y * blockDim.x + threadIdx.x,
-             gridDim.y * blockDim.x);
-}
-
-hipError_t launch_range_copy(const RangeArgs& a, hipStream_t s) {
-  if (a.m == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_range_copy, dim3(a.m, 4), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
 // An edge slot's covered bytes to the range's output.  The plan's numbers keep the reads inside
 // the slot (trim_src + trim_len <= the chunk's length <= the slot) and the writes inside the range
 // (trim_dst - out_off[r] + trim_len <= len), whatever the chunk decoded to.
@@ -189,47 +148,13 @@ __global__ __launch_bounds__(256) void k_range_trim(RangeArgs a) {
   const uint32_t j = blockIdx.x;
   const uint32_t n = a.s.trim_len[j];
   if (n == 0) return;
-  copy_bytes(at(a.edge, a.s.out_off[j] + a.s.trim_src[j]), n, a.out + a.s.trim_dst[j],
+  copy_bytes(at(a.edge, a.s.slots.out_off[j] + a.s.trim_src[j]), n, a.out + a.s.trim_dst[j],
              blockIdx.y * blockDim.x + threadIdx.x, gridDim.y * blockDim.x);
 }
 
 hipError_t launch_range_trim(const RangeArgs& a, hipStream_t s) {
   if (a.m == 0) return hipSuccess;
   hipLaunchKernelGGL(k_range_trim, dim3(a.m, 4), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
-// Per slot: why it was not decoded, else the raw decoder's status (0x00), else the CRC's verdict;
-// a failing slot enters its range's minimum.  Then per range: the first failing slot's status.
-__global__ __launch_bounds__(256) void k_range_verify(RangeArgs a) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= a.m) return;
-  const uint32_t r = a.s.range[j];
-  int32_t st = SM_OK;
-  if (r != kNoSlot) {
-    st = a.s.pre[j];
-    if (st == SM_OK && !a.s.copy[j]) st = a.s.dec_status[j];
-    if (st == SM_OK && a.s.crc_out[j] != a.s.crc_want[j]) st = SMF_ERR_CRC;
-    if (st != SM_OK) atomicMin(&a.s.fail[r], j - a.s.base[r]);
-  }
-  a.s.slot_status[j] = st;
-}
-
-__global__ __launch_bounds__(256) void k_range_result(RangeArgs a) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= a.nranges) return;
-  int32_t st = a.s.hdr->over ? (int32_t)SM_ERR_ARGUMENT : a.s.rpre[r];
-  if (st == SM_OK) {
-    const uint32_t f = a.s.fail[r];
-    if (f != kNoSlot) st = a.s.slot_status[a.s.base[r] + f];
-  }
-  a.range_status[r] = st;
-  a.out_len[r] = st == SM_OK ? a.len[r] : 0;
-}
-
-hipError_t launch_range_verdicts(const RangeArgs& a, hipStream_t s) {
-  if (a.m) hipLaunchKernelGGL(k_range_verify, dim3((a.m + 255) / 256), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_range_result, dim3((a.nranges + 255) / 256), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -2,12 +2,13 @@
 // smf_compress_streams_device): gfx950 kernels and their launchers (smf_internal.h).  Plumbing
 // around the raw codec's batched calls and k_crc32c, which run once over all chunks of all streams;
 // the decisions are the shared rules of smf_streams.h and smf_format.h, taken per stream and per
-// slot on the device, so a call needs no host synchronisation.  block_scan, copy_bytes and sat32
-// are the shared ones of ../common/smc_device.h.
+// slot on the device, so a call needs no host synchronisation.  The decode's slot stage
+// behind the plan is the shared one (smf_slots.h); the walk's fetch and the scans are smf_device.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../common/smc_device.h"
+#include "smf_device.h"
 #include "smf_format.h"
 #include "smf_internal.h"
 #include "smf_streams.h"
@@ -17,48 +18,8 @@ namespace smf {
 namespace {
 
 using smc::block_scan;
-using smc::kWave;
-using smc::sat32;
 
 constexpr uint32_t kWalkWaves = 4;  // streams a workgroup of the walkers takes: one per wave
-
-// The walker's fetch, by one wave: a step's bytes come in by one load, a byte a lane, and every
-// lane then takes the same step (as k_frame_index does).
-struct WaveFetch {
-  const uint8_t* in;
-  uint32_t lane;
-  __device__ void operator()(uint64_t pos, uint32_t have, uint8_t* h) const {
-    const uint32_t mine = lane < have ? in[pos + lane] : 0u;
-#pragma unroll
-    for (uint32_t i = 0; i < kHeadBytes; ++i) h[i] = (uint8_t)__shfl((int)mine, (int)i, kWave);
-  }
-};
-
-// the exclusive scan of cnt(r) over the streams against the bound m, by one workgroup: first[0,
-// nstreams] and the header.  Over the bound the scan is not used (it saturates).
-template <typename Count>
-__device__ inline void scan_counts(uint32_t nstreams, uint32_t m, Count cnt, uint32_t* first, uint32_t* first_out,
-                                   StreamsHeader* hdr, uint64_t* sh) {
-  uint64_t carry = 0;
-  for (uint32_t b0 = 0; b0 < nstreams; b0 += 256) {  // (uniform: every thread takes every tile)
-    const uint32_t r = b0 + threadIdx.x;
-    const uint64_t c = r < nstreams ? cnt(r) : 0u;
-    uint64_t total;
-    const uint64_t ex = block_scan(c, sh, total);
-    if (r < nstreams) {
-      first[r] = sat32(carry + ex);
-      if (first_out) first_out[r] = sat32(carry + ex);
-    }
-    carry += total;
-  }
-  if (threadIdx.x == 0) {
-    const bool over = carry > m;
-    first[nstreams] = sat32(carry);
-    if (first_out) first_out[nstreams] = sat32(carry);
-    hdr->over = over ? 1u : 0u;
-    hdr->total = over ? 0u : (uint32_t)carry;
-  }
-}
 
 }  // namespace
 
@@ -75,7 +36,7 @@ __global__ __launch_bounds__(256) void k_streams_count(DecodeStreamsArgs a) {
     a.s.count[r] = p.slots;
     a.s.pre[r] = p.status;
     a.s.length[r] = p.length;
-    a.s.fail[r] = kNoSlot;
+    a.s.slots.fail[r] = kNoSlot;
   }
 }
 
@@ -102,15 +63,13 @@ __global__ __launch_bounds__(256) void k_streams_fill(DecodeStreamsArgs a) {
   walk_stream(a.in_len[r], fetch, [&](uint32_t k, uint64_t at, const Chunk& c) {
     if (lane != 0 || k >= cnt) return;
     const uint32_t j = base + k;
-    a.s.ch.type[j] = c.type;
-    a.s.ch.pay_off[j] = in_off + c.pay_off;
-    a.s.ch.pay_len[j] = c.pay_len;
-    a.s.ch.crc[j] = c.crc;
-    a.s.ch.ulen[j] = c.ulen;
-    a.s.out_off[j] = out_off + at;
-    a.s.cap[j] = c.ulen;
-    a.s.dec_len[j] = c.type == SMF_CHUNK_COMPRESSED ? c.pay_len : 0u;
-    a.s.stream[j] = r;
+    a.s.slots.type[j] = c.type;
+    a.s.slots.in_off[j] = in_off + c.pay_off;
+    a.s.slots.crc_want[j] = c.crc;
+    a.s.slots.out_off[j] = out_off + at;
+    a.s.slots.cap[j] = c.ulen;
+    a.s.slots.dec_len[j] = c.type == SMF_CHUNK_COMPRESSED ? c.pay_len : 0u;
+    a.s.slots.group[j] = r;
   });
 }
 
@@ -119,15 +78,13 @@ __global__ __launch_bounds__(256) void k_streams_fill(DecodeStreamsArgs a) {
 __global__ __launch_bounds__(256) void k_streams_unused(DecodeStreamsArgs a) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= a.m || j < a.s.hdr->total) return;
-  a.s.ch.type[j] = SMF_CHUNK_COMPRESSED;
-  a.s.ch.pay_off[j] = 0;
-  a.s.ch.pay_len[j] = 0;
-  a.s.ch.crc[j] = 0;
-  a.s.ch.ulen[j] = 0;
-  a.s.out_off[j] = 0;
-  a.s.cap[j] = 0;
-  a.s.dec_len[j] = 0;
-  a.s.stream[j] = kNoSlot;
+  a.s.slots.type[j] = SMF_CHUNK_COMPRESSED;
+  a.s.slots.in_off[j] = 0;
+  a.s.slots.crc_want[j] = 0;
+  a.s.slots.out_off[j] = 0;
+  a.s.slots.cap[j] = 0;
+  a.s.slots.dec_len[j] = 0;
+  a.s.slots.group[j] = kNoSlot;
 }
 
 hipError_t launch_streams_plan(const DecodeStreamsArgs& a, hipStream_t s) {
@@ -138,43 +95,6 @@ hipError_t launch_streams_plan(const DecodeStreamsArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_streams_fill, dim3(walkers), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_streams_unused, dim3((a.m + 255) / 256), dim3(256), 0, s, a);
   }
-  return hipGetLastError();
-}
-
-// ---- decode: the verdicts ------------------------------------------------------------------------
-// Per slot, by the rule of k_frame_verify: the raw decoder's status (0x00), else the CRC's verdict; a
-// failing slot enters its stream's minimum.  Then per stream: the plan's status, else the first
-// failing slot's; over the bound SM_ERR_ARGUMENT and no length.
-__global__ __launch_bounds__(256) void k_streams_verify(DecodeStreamsArgs a) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= a.m) return;
-  const uint32_t r = a.s.stream[j];
-  int32_t st = SM_OK;
-  if (r != kNoSlot) {
-    if (a.s.ch.type[j] == SMF_CHUNK_COMPRESSED) st = a.s.dec_status[j];
-    if (st == SM_OK && a.s.crc_out[j] != a.s.ch.crc[j]) st = SMF_ERR_CRC;
-    if (st != SM_OK) atomicMin(&a.s.fail[r], j - a.s.first[r]);
-  }
-  a.s.slot_status[j] = st;
-  if (a.chunk_status) a.chunk_status[j] = st;
-}
-
-__global__ __launch_bounds__(256) void k_streams_result(DecodeStreamsArgs a) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= a.nstreams) return;
-  const bool over = a.s.hdr->over != 0;
-  int32_t st = over ? (int32_t)SM_ERR_ARGUMENT : a.s.pre[r];
-  if (st == SM_OK) {
-    const uint32_t f = a.s.fail[r];
-    if (f != kNoSlot) st = a.s.slot_status[a.s.first[r] + f];
-  }
-  a.status[r] = st;
-  a.out_len[r] = over ? 0 : a.s.length[r];
-}
-
-hipError_t launch_streams_verdicts(const DecodeStreamsArgs& a, hipStream_t s) {
-  if (a.m) hipLaunchKernelGGL(k_streams_verify, dim3((a.m + 255) / 256), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_streams_result, dim3((a.nstreams + 255) / 256), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

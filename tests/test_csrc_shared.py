@@ -96,3 +96,38 @@ def test_decoder_files_are_in_the_version_hash():
     assert "sm_dec_walk.h" in hdrs and {"sm_decompress.hip", "sm_dec_stream.hip"} <= set(srcs)
     hips = {f for f in _sources() if f.endswith(".hip") and "/" not in f}
     assert hips == set(srcs), (hips, srcs)
+
+
+def test_framing_rules_have_one_definition():
+    """The framing library's decode entry points share one slot stage: the two verdict rules, the
+    scan of the groups' slot counts, the chunk walk, the index check and the one-wave fetch are
+    written once under csrc/framing/, and the copies they replaced are gone."""
+    framing = {f: text for f, text in _sources().items() if f.startswith("framing/")}
+    for name, where in (("slot_verdict", "framing/smf_slots.h"), ("group_verdict", "framing/smf_slots.h"),
+                        ("scan_counts", "framing/smf_device.h"), ("walk_stream", "framing/smf_format.h"),
+                        ("valid_chunks", "framing/smf_format.h")):
+        found = sorted(f for f, text in framing.items()
+                       for _ in re.finditer(r"\b[\w:<>]+[\s\*&]+%s\s*\([^;{}]*\)\s*\{" % name, text))
+        assert found == [where], (name, found)
+    fetch = sorted(f for f, text in framing.items() for _ in re.finditer(r"\bstruct\s+WaveFetch\b\s*\{", text))
+    assert fetch == ["framing/smf_device.h"], fetch
+    for f in ("framing/smf_slots.h", "framing/smf_format.h"):  # the sanitizer driver compiles them for the host
+        assert not re.search(r"#\s*include\s*[<\"]hip/", framing[f]), f
+    # walk_step is called by walk_stream, the one loop around it -- and by k_frame_index, which keeps
+    # that loop and the fetch written out because the shared form measured slower there (DESIGN.md 8.4)
+    calls = sorted(f for f, text in framing.items() if not f.endswith("_check.cpp")
+                   for _ in re.finditer(r"(?<![\w:])(?:smf::)?walk_step\s*\((?!Walk&)", text))
+    assert calls == ["framing/smf_format.h", "framing/smf_kernels.hip"], calls
+    shuffles = sorted(f for f, text in framing.items() for _ in re.finditer(r"__shfl\s*\(", text))
+    assert shuffles == ["framing/smf_device.h", "framing/smf_kernels.hip"], shuffles
+    for name in ("RangeHeader", "StreamsHeader", "DecodeMeta", "k_range_scan", "k_range_verify", "k_streams_verify",
+                 "k_frame_verify", "k_range_copy", "k_frame_copy", "k_range_result", "k_streams_result"):
+        found = [f for f, text in framing.items() if re.search(r"\b%s\b" % name, text)]
+        assert not found, (name, found)
+
+
+def test_framing_headers_are_in_the_version_hash():
+    mk = _sources()["framing/Makefile"]
+    hdrs = re.search(r"^HDRS\s*=(.*)$", mk, re.M).group(1).split()
+    here = {f.split("/", 1)[1] for f in _sources() if f.startswith("framing/") and f.endswith(".h")}
+    assert here and here <= set(hdrs), (here, hdrs)
