@@ -36,6 +36,12 @@ SMC_HD inline uint32_t varint_len(uint32_t v) {
   return v < (1u << 7) ? 1 : v < (1u << 14) ? 2 : v < (1u << 21) ? 3 : v < (1u << 28) ? 4 : 5;
 }
 
+// byte i (< nb) of the nb = varint_len(v) bytes encode32! writes for v: every emitter's one header
+// rule, whichever thread or lane writes the byte (the caller has nb: it sized the header by it)
+SMC_HD inline uint8_t varint_byte(uint32_t v, uint32_t i, uint32_t nb) {
+  return (uint8_t)(((v >> (7 * i)) & 0x7f) | (i + 1 < nb ? 0x80 : 0));
+}
+
 // parse32 (varint.jl:12-37) over a byte accessor: at(i) is byte i of a header of which n bytes
 // exist.  Returns 0 with the value and the header's length hv (1..5), or kErrVarint when the header
 // is truncated, longer than 5 bytes or its 5th byte is 0x10 or more (value is then unspecified,

@@ -152,7 +152,7 @@ __global__ __launch_bounds__(kThreads) void k_pack(CompressPlan p) {
   if (blockIdx.y == 0) {
     if (t == 0 && p.frag_pos) p.frag_pos[p.s.ifirst[s] + (j - j0)] = bad ? 0u : (uint32_t)(hv + rel);
     if (j == j0) {
-      if (t < hv && !bad) dst[t] = (uint8_t)(((len >> (7 * t)) & 0x7f) | (t + 1 < hv ? 0x80 : 0));
+      if (t < hv && !bad) dst[t] = smc::varint_byte(len, t, hv);
       if (t == 0) {
         p.out_len[s] = bad ? 0u : (uint32_t)total;
         p.status[s] = bad ? SM_ERR_DEVICE : SM_OK;

@@ -10,8 +10,6 @@
 
 namespace sm {
 
-constexpr uint32_t kScreenTodo = 0xfffffffeu;  // out_len mark of k_literal_screen: the parse compresses this block
-
 // ---- incompressible screen ---------------------------------------------------------------
 // Before the parse, one light workgroup per block looks for repeated content anywhere in the block
 // through content-defined anchors: the positions whose 4-byte word hashes into the top 1/64 of the
@@ -152,8 +150,7 @@ __global__ __launch_bounds__(kScrThreads) void k_literal_screen(CompressArgs a) 
   // [16p, 16p + 16)) makes the aligned output unit that starts m bytes into it, m = -(ad + h) mod
   // 16, from its bytes and the next piece's (lane + 1; a wave's last lane reloads it).  The partial
   // units at either end are written byte by byte.
-  const uint32_t hv0 = a.header ? varint_len(n) : 0u;
-  const uint32_t h = hv0 + literal_tag_bytes(n);
+  const uint32_t h = block_literal_bytes(n, a.header != 0) - n;  // the varint and the tag
   const uint32_t ad = (uint32_t)((uintptr_t)dst & 15);
   const uint32_t m = (16u - ((ad + h) & 15u)) & 15u;
   uint4* d16 = reinterpret_cast<uint4*>(dst - ad);
@@ -190,28 +187,24 @@ __global__ __launch_bounds__(kScrThreads) void k_literal_screen(CompressArgs a) 
   const uint32_t nh = headEnd, nt = h + n - tailBeg;
   for (uint32_t j = tid; j < nh + nt; j += kScrThreads) {
     const uint32_t jj = j < nh ? j : tailBeg + (j - nh);
-    uint8_t c;
-    if (jj < hv0) {
-      c = (uint8_t)(((n >> (7 * jj)) & 0x7f) | (jj + 1 < hv0 ? 0x80 : 0));
-    } else if (jj < h) {  // emit_literal! tag: 60..63 << 2 then len-1 little-endian
-      const uint32_t tb = h - hv0, k = jj - hv0;
-      c = tb == 1 ? (uint8_t)((n - 1) << 2) : (k == 0 ? (uint8_t)((58 + tb) << 2) : (uint8_t)((n - 1) >> (8 * (k - 1))));
-    } else {
-      c = src[jj - h];
-    }
-    dst[jj] = c;
+    dst[jj] = jj < h ? block_literal_head_byte(n, a.header != 0, jj) : src[jj - h];
   }
   if (tid == 0) a.out_len[b] = h + n;
 }
 
 
+// the screen over every block of a (a.screened set: the parse reads its verdicts)
+static hipError_t launch_screen(CompressArgs& a, hipStream_t s) {
+  a.screened = 1;
+  hipLaunchKernelGGL(k_literal_screen, dim3(a.nblk), dim3(kScrThreads), 0, s, a);
+  return hipGetLastError();
+}
+
 // modes 1 (SM_MODE_FAST) and 2 (SM_MODE_FAST_DENSE): the screen first, then the super-chunk parse
 // (k_compress_sc) of the blocks it marked kScreenTodo.
 hipError_t launch_compress_fast(const CompressArgs& a0, int mode, hipStream_t s) {
   CompressArgs a = a0;
-  a.screened = 1;
-  hipLaunchKernelGGL(k_literal_screen, dim3(a.nblk), dim3(kScrThreads), 0, s, a);
-  const hipError_t e = hipGetLastError();
+  const hipError_t e = launch_screen(a, s);
   if (e != hipSuccess) return e;
   return launch_compress_sc(a, mode, s);
 }
@@ -226,9 +219,7 @@ hipError_t launch_compress_batch_parts(const CompressArgs& a0, int mode, const B
       (uint64_t)bp.rem * bp.parts > compress_grid() || !scratch)
     return hipErrorInvalidValue;
   CompressArgs a = a0;
-  a.screened = 1;
-  hipLaunchKernelGGL(k_literal_screen, dim3(a.nblk), dim3(kScrThreads), 0, s, a);
-  hipError_t e = hipGetLastError();
+  hipError_t e = launch_screen(a, s);
   if (e != hipSuccess) return e;
   const uint32_t whole = a.nblk - bp.rem;
   a.nblk = whole;
@@ -252,9 +243,7 @@ hipError_t launch_compress_batch_parts(const CompressArgs& a0, int mode, const B
 hipError_t launch_compress_span(const CompressArgs& a0, int mode, const ScSpan& sp, hipStream_t s) {
   if (mode != 1 && mode != 2) return hipErrorInvalidValue;
   CompressArgs a = a0;
-  a.screened = 1;
-  hipLaunchKernelGGL(k_literal_screen, dim3(a.nblk), dim3(kScrThreads), 0, s, a);
-  const hipError_t e = hipGetLastError();
+  const hipError_t e = launch_screen(a, s);
   if (e != hipSuccess) return e;
   return launch_compress_sc_span(a, mode, sp, s);
 }

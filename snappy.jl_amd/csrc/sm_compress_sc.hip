@@ -43,8 +43,6 @@
 
 namespace sm {
 
-constexpr uint32_t kScreenTodoSc = 0xfffffffeu;  // k_literal_screen's "parse this block" mark
-
 constexpr uint32_t kScS = 1024;           // super-chunk bytes
 constexpr uint32_t kScC = kScS / 64;      // positions per lane (16)
 constexpr uint32_t kScG = kScS / 64;      // 64-position groups per super-chunk (16)
@@ -217,7 +215,7 @@ __device__ inline void sc_lds_orn(uint32_t a, uint4 v, uint32_t nb) {
 }
 
 // ors the (up to 3) bytes of cv into the zeroed LDS byte array at byte address a
-__device__ inline void sc_lds_or3(uint32_t a, uint32_t cv, uint32_t cs = 3) {
+__device__ inline void sc_lds_or3(uint32_t a, uint32_t cv) {
   const uint32_t wa = (a - 1u) & ~3u, t = 0u - a;  // (as sc_lds_or)
   const uint32_t lo = __builtin_amdgcn_alignbyte(cv, 0u, t), hi = __builtin_amdgcn_alignbyte(0u, cv, t);
   asm volatile("ds_or_b32 %0, %1\nds_or_b32 %0, %2 offset:4" : : "v"(wa), "v"(lo), "v"(hi) : "memory");
@@ -231,11 +229,11 @@ __device__ inline uint4 sc_prepend(uint4 v, uint32_t tag, uint32_t t) {
                     __builtin_amdgcn_alignbyte(v.z, v.y, s), __builtin_amdgcn_alignbyte(v.w, v.z, s));
 }
 
-// emit_literal! tag (internal.jl:271-284) for a run of len >= 1 bytes, and its size
-__device__ inline uint32_t sc_lit_tag(uint32_t len, uint32_t& sz) {
-  const uint32_t l1 = len - 1;
-  sz = len <= 60 ? 1u : (len <= 256 ? 2u : 3u);
-  return sz == 1 ? (l1 << 2) : (sz == 2 ? (60u << 2) | (l1 << 8) : (61u << 2) | (l1 << 8));
+// literal_tag (standard rule) for a run inside one super-chunk: 1 <= len <= kScS, which the
+// compiler is told, so the tag is three bytes at most and the longer forms fold away
+__device__ inline TagBytes sc_run_tag(uint32_t len) {
+  __builtin_assume(len >= 1 && len <= kScS);
+  return literal_tag(len, kLiteralStd);
 }
 
 // the bucket of a word: the reference's multiply (internal.jl:94), its top kScTabBits bits, as one
@@ -256,16 +254,6 @@ __device__ inline uint32_t sc_select(uint64_t m, uint32_t a, uint32_t b) {
 // c ? a : b on values (a conditional on lvalues can become a select of their addresses)
 __device__ inline uint32_t sc_sel(uint32_t c, uint32_t a, uint32_t b) { return c ? a : b; }
 
-// one emit_copy_upto_64! piece (internal.jl:289-304), L in 4..64: copy-1 or copy-2, and its size
-__device__ inline uint32_t sc_copy_piece(uint32_t off, uint32_t L, uint32_t& sz) {
-  const bool c1 = L < 12 && off < 2048;
-  sz = c1 ? 2u : 3u;
-  // (both encodings, then a select: the compiler otherwise branches on c1)
-  const uint32_t e1 = (1u + ((L - 4) << 2) + ((off >> 3) & 0xe0u)) | ((off & 0xffu) << 8);
-  const uint32_t e2 = (2u + ((L - 1) << 2)) | (off << 8);
-  return sc_sel(c1, e1, e2);
-}
-
 __device__ inline uint32_t sc_extend(const uint8_t* blk, uint32_t q, uint32_t off, uint32_t L, uint32_t cap) {
   for (;;) {
     const uint4 x = sc_ld128(blk, q + L), y = sc_ld128(blk, q + L - off);
@@ -274,16 +262,6 @@ __device__ inline uint32_t sc_extend(const uint8_t* blk, uint32_t q, uint32_t of
     L = min(L + fb, cap);
     if (fb < 16 || L >= cap) return L;
   }
-}
-
-// copy_tag_bytes (emit_copy!, internal.jl:306-329) for 4 <= L <= 255 in closed form.  emit_copy!
-// cuts 64-byte pieces while L >= 68, a 60-byte piece if more than 64 remain, then the last piece R:
-// (L - 1) >> 6 three-byte pieces before the last, and R < 12 exactly when ((L - 1) & 63) < 11
-// (R = m + 4 for m = ((L - 1) & 63) + 1 < 4, else m) -- checked for every L and both offset
-// classes against the loop (tests/test_host_logic.py); no multiply (3 n as n + 2 n)
-__device__ inline uint32_t sc_copy_bytes(uint32_t off, uint32_t L) {
-  const uint32_t t = L - 1, n = t >> 6;
-  return n + 2 * n + (((t & 63) < 11 && off < 2048) ? 2u : 3u);
 }
 
 // lowest set bit of x, ~0 for 0 (v_ffbl_b32)
@@ -346,7 +324,7 @@ __device__ __attribute__((always_inline)) inline uint32_t sc_next_block(const Co
                                                                    uint32_t lane) {
   for (uint32_t b0 = from; b0 < a.nblk; b0 += 64 * g) {
     const uint32_t bb = b0 + lane * g;
-    const bool todo = bb < a.nblk && (!a.screened || a.out_len[bb] == kScreenTodoSc);
+    const bool todo = bb < a.nblk && (!a.screened || a.out_len[bb] == kScreenTodo);
     const uint64_t m = ballot(todo);
     if (m) return b0 + ctz64(m) * g;
   }
@@ -695,7 +673,7 @@ __device__ __attribute__((always_inline)) inline void sc_superchunk(ScLds& S, co
         lead = sc_sel(has, run, 0u);
       else
         body += sc_sel(has && run, run + 1, 0u);  // an internal run (< 16 bytes: a one-byte tag)
-      body += sc_sel(has, sc_copy_bytes(tv & 0xffffu, L), 0u);
+      body += sc_sel(has, copy_tag_bytes(tv & 0xffffu, L), 0u);
       p = sc_sel(has, q + L, p);
     }
     trail = (live && p < ce) ? ce - p : 0u;
@@ -711,8 +689,7 @@ __device__ __attribute__((always_inline)) inline void sc_superchunk(ScLds& S, co
   const uint32_t Cf = __shfl(Cs, fn, 64);
   const bool starts = trail > 0 && !mid;
   const uint32_t merged = starts ? trail + Cf - Cs : 0u;  // the run this lane's last run starts
-  uint32_t mts;
-  (void)sc_lit_tag(merged ? merged : 1u, mts);
+  const uint32_t mts = sc_run_tag(merged ? merged : 1u).size;
   uint32_t size;
   if (tk.n == 0)
     size = lead == 0 ? 0u : (cont ? lead : mts + trail);
@@ -747,32 +724,27 @@ __device__ __attribute__((always_inline)) inline void sc_superchunk(ScLds& S, co
           // run continues the previous lane's, which ends on that very byte) it is or-ed again
           // onto itself one byte early -- no prepend shifts
           uint4 v = sc_ld128(S.blk - 4, p + 3);  // bytes from position p - 1
-          v.x = ts ? ((v.x & ~0xffu) | ((run - 1) << 2)) : v.x;
+          v.x = ts ? ((v.x & ~0xffu) | literal_tag1(run)) : v.x;
           // (lanes without a run write nothing: a shared dummy address serialises the atomics)
           if (run) sc_lds_orn(stga + at + ts - 1u, sc_trim1(v, run + 1), run + 1);
         }
         at += len;
+        // emit_copy! (internal.jl:306-329): the pieces of copy_piece_len.  Most tokens are one piece,
+        // and that case stays in front of the loop: the loop alone, which covers it, is 0.7% slower
+        // on the bench text
         if (L <= 64) {
-          uint32_t cs;
-          const uint32_t cv = sc_copy_piece(off, L, cs);
-          sc_lds_or3(stga + at, cv, cs);
-          at += cs;
-        } else {  // emit_copy! (internal.jl:306-329): 64-byte pieces while >= 68, a 60 if > 64, the rest
+          const TagBytes c = copy_piece(off, L);
+          sc_lds_or3(stga + at, (uint32_t)c.bytes);
+          at += c.size;
+        } else {
           uint32_t R = L;
-          while (R >= 68) {
-            sc_lds_or3(stga + at, (2u + (63u << 2)) | (off << 8));
-            at += 3;
-            R -= 64;
-          }
-          if (R > 64) {
-            sc_lds_or3(stga + at, (2u + (59u << 2)) | (off << 8));
-            at += 3;
-            R -= 60;
-          }
-          uint32_t cs;
-          const uint32_t cv = sc_copy_piece(off, R, cs);
-          sc_lds_or3(stga + at, cv, cs);
-          at += cs;
+          do {
+            const uint32_t l = copy_piece_len(R);
+            const TagBytes c = copy_piece(off, l);
+            sc_lds_or3(stga + at, (uint32_t)c.bytes);
+            at += c.size;
+            R -= l;
+          } while (R);
         }
         p = q + L;
       }
@@ -780,7 +752,11 @@ __device__ __attribute__((always_inline)) inline void sc_superchunk(ScLds& S, co
     if (live && p < ce) {  // the lane's last run: it starts the merged run, unless it only continues one
       const uint32_t run = ce - p;
       uint32_t tag = 0, ts = 0;
-      if (!(tk.n == 0 && cont)) tag = sc_lit_tag(merged, ts);
+      if (!(tk.n == 0 && cont)) {
+        const TagBytes lt = sc_run_tag(merged);
+        tag = (uint32_t)lt.bytes;
+        ts = lt.size;
+      }
       sc_lds_orn(stga + at, sc_trim(sc_prepend(sc_ld128(S.blk, p), tag, ts), min(ts + run, 16u)), min(ts + run, 16u));
       if (ts + run > 16) sc_lds_or(stga + at + 16, sc_trim(sc_ld128(S.blk, p + 16 - ts), ts + run - 16));
     }
@@ -834,10 +810,10 @@ __device__ __attribute__((always_inline)) inline void sc_writer(ScLds& S, uint32
     __hip_atomic_store(&S.rsize[slot], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     __hip_atomic_store(&S.rseq[slot], k + kScRing, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
-  const uint32_t h = hv + (n ? literal_tag_bytes(n) : 0u);
-  if (whole && !err && n && o > h + n) {  // one literal: the tag after the varint, the block from LDS
+  const uint32_t len = block_literal_bytes(n, false);  // (behind the hv header bytes, which are written)
+  if (whole && !err && n && o > hv + len) {  // one literal: the tag after the varint, the block from LDS
     uint8_t* const g = dst + hv;
-    const uint32_t tb = h - hv, len = tb + n;  // literal stream bytes j: the tag (j < tb), then blk[j - tb]
+    const uint32_t tb = len - n;  // literal stream bytes j: the tag (j < tb), then blk[j - tb]
     const uint32_t ad = (uint32_t)((uintptr_t)g & 15);
     uint4* const g16 = reinterpret_cast<uint4*>(g - ad);
     const uint32_t u1 = (len + ad) >> 4;              // units [ua, u1) are whole and past the tag
@@ -847,18 +823,49 @@ __device__ __attribute__((always_inline)) inline void sc_writer(ScLds& S, uint32
     const uint32_t te = ua < u1 ? 16 * u1 - ad : len;
     for (uint32_t j = lane; j < he + (len - te); j += 64) {
       const uint32_t jj = j < he ? j : te + (j - he);
-      uint8_t c;
-      if (jj < tb) {
-        c = tb == 1 ? (uint8_t)((n - 1) << 2) : (jj == 0 ? (uint8_t)((58 + tb) << 2) : (uint8_t)((n - 1) >> (8 * (jj - 1))));
-      } else {
-        c = S.blk[jj - tb];
-      }
-      g[jj] = c;
+      g[jj] = jj < tb ? block_literal_head_byte(n, false, jj) : S.blk[jj - tb];
     }
-    o = h + n;
+    o = hv + len;
   }
   err |= uniform(__hip_atomic_load(&S.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-  if (lane == 0) *len_out = err ? 0xfff00000u | err : o;  // (an error mark: > any block's length)
+  if (lane == 0) *len_out = err ? kOutLenError | err : o;  // (an error mark: > any block's length)
+}
+
+// A block into the LDS for its parse: the n bytes at src to S.blk (unless they are `there`
+// already), zeros behind them, the table cleared, and the first hv bytes of varint(n) at dst
+// (the whole workgroup; a barrier must follow)
+__device__ __attribute__((always_inline)) inline void sc_stage_block(ScLds& S, const uint8_t* src, uint32_t n, bool there,
+                                                                    uint8_t* dst, uint32_t hv) {
+  const uint32_t tid = threadIdx.x;
+  if (there) {  // (the caller's prefetch put them there)
+  } else if (((uintptr_t)src & 15) == 0) {
+    const uint4* s16 = reinterpret_cast<const uint4*>(src);
+    uint4* d16 = reinterpret_cast<uint4*>(S.blk);
+    const uint32_t n16 = n >> 4;
+    for (uint32_t k = tid; k < n16; k += kScThreads) d16[k] = s16[k];
+    for (uint32_t k = (n & ~15u) + tid; k < n; k += kScThreads) S.blk[k] = src[k];
+  } else {
+    for (uint32_t k = tid; k < n; k += kScThreads) S.blk[k] = src[k];
+  }
+  if (tid < 64) S.blk[n + tid] = 0;  // bytes past the block read as zeros (never part of a match)
+  uint4* t16 = reinterpret_cast<uint4*>(S.T);
+  for (uint32_t k = tid; k < 4 * kScTabWords / 16; k += kScThreads) t16[k] = make_uint4(0, 0, 0, 0);
+  if (tid < hv) dst[tid] = varint_byte(n, tid, hv);
+}
+
+// The hand-off words for a parse that starts at super-chunk k0 (wave 0; before the same barrier)
+__device__ __attribute__((always_inline)) inline void sc_reset_handoff(ScLds& S, uint32_t k0) {
+  const uint32_t lane = threadIdx.x & 63;
+  if (uniform(threadIdx.x >> 6) != 0) return;
+  if (lane < kScRing) {
+    S.rsize[lane] = 0;
+    S.rseq[lane] = k0 + ((lane - k0) & (kScRing - 1));
+  }
+  if (lane == 0) {
+    S.ins = k0;
+    S.next = 64 * k0;
+    S.err = 0;
+  }
 }
 
 // ---- one block in parts, for latency (sm_compress of small inputs) ------------------------
@@ -885,46 +892,21 @@ __device__ __attribute__((always_inline)) inline void sc_span_item(ScLds& S, con
   uint32_t* const plen = sp.part_len + item;
   const uint32_t n = a.in_len[b];
   if (n > kBlockSize) {  // not a block: an error mark in part 0 (the gather refuses it)
-    if (tid == 0) *plen = j == 0 ? 0xffffffffu : 0u;
+    if (tid == 0) *plen = j == 0 ? kNotABlock : 0u;
     return;
   }
   const uint32_t nsc = (n + kScS - 1) / kScS;
   const uint32_t k0 = j * sp.span, k1 = min(k0 + sp.span, nsc);
-  const bool todo = !a.screened || a.out_len[b] == kScreenTodoSc;
+  const bool todo = !a.screened || a.out_len[b] == kScreenTodo;
   if (!todo || k0 >= k1) {  // a screened literal (part 0 is its output) or a part past the block
     if (tid == 0) *plen = (!todo && j == 0) ? (sp.blk_pitch ? kPartScreened : a.out_len[b]) : 0u;
     return;
   }
   const uint8_t* const src = a.in + a.in_off[b];
   uint8_t* const dst = a.out + (sp.blk_pitch ? b * sp.blk_pitch : a.out_off[b]) + (uint64_t)j * sp.pitch;
-  // ---- stage the block, clear the table (as k_compress_sc) ----
-  if (((uintptr_t)src & 15) == 0) {
-    const uint4* s16 = reinterpret_cast<const uint4*>(src);
-    uint4* d16 = reinterpret_cast<uint4*>(S.blk);
-    const uint32_t n16 = n >> 4;
-    for (uint32_t k = tid; k < n16; k += kScThreads) d16[k] = s16[k];
-    for (uint32_t k = (n & ~15u) + tid; k < n; k += kScThreads) S.blk[k] = src[k];
-  } else {
-    for (uint32_t k = tid; k < n; k += kScThreads) S.blk[k] = src[k];
-  }
-  if (tid < 64) S.blk[n + tid] = 0;
-  {
-    uint4* t16 = reinterpret_cast<uint4*>(S.T);
-    for (uint32_t k = tid; k < 4 * kScTabWords / 16; k += kScThreads) t16[k] = make_uint4(0, 0, 0, 0);
-  }
   const uint32_t hv = (a.header && j == 0) ? varint_len(n) : 0u;
-  if (tid < hv) dst[tid] = (uint8_t)(((n >> (7 * tid)) & 0x7f) | (tid + 1 < hv ? 0x80 : 0));
-  if (wave == 0) {  // the hand-off words, starting at super-chunk k0
-    if (lane < kScRing) {
-      S.rsize[lane] = 0;
-      S.rseq[lane] = k0 + ((lane - k0) & (kScRing - 1));
-    }
-    if (lane == 0) {
-      S.ins = k0;
-      S.next = 64 * k0;
-      S.err = 0;
-    }
-  }
+  sc_stage_block(S, src, n, false, dst, hv);
+  sc_reset_handoff(S, k0);
   __syncthreads();
   // ---- the table as the in-order insert of positions [0, kScS k0) leaves it (section B's values:
   // positions, group parity = slot; positions without 4 bytes before the block end never enter;
@@ -1021,45 +1003,21 @@ __global__ __launch_bounds__(kScThreads) void k_compress_sc(CompressArgs a, uint
   while (b < a.nblk) {
     uint8_t* const dst = a.out + a.out_off[b];
     if (n > kBlockSize) {  // (uniform) not a block: error mark, next
-      if (tid == 0) a.out_len[b] = 0xffffffffu;
+      if (tid == 0) a.out_len[b] = kNotABlock;
       b = sc_next_block(a, b + g, g, lane);
       SC_FETCH(b)
       continue;
     }
-    // ---- stage the block, clear the table ----
-    if (inpf) {
+    if (inpf) {  // the prefetched block from the registers
       uint4* d16 = reinterpret_cast<uint4*>(S.blk);
       d16[tid] = pf0;
       d16[tid + kScThreads] = pf1;
       d16[tid + 2 * kScThreads] = pf2;
       d16[tid + 3 * kScThreads] = pf3;
-    } else if (((uintptr_t)src & 15) == 0) {
-      const uint4* s16 = reinterpret_cast<const uint4*>(src);
-      uint4* d16 = reinterpret_cast<uint4*>(S.blk);
-      const uint32_t n16 = n >> 4;
-      for (uint32_t k = tid; k < n16; k += kScThreads) d16[k] = s16[k];
-      for (uint32_t k = (n & ~15u) + tid; k < n; k += kScThreads) S.blk[k] = src[k];
-    } else {
-      for (uint32_t k = tid; k < n; k += kScThreads) S.blk[k] = src[k];
-    }
-    if (tid < 64) S.blk[n + tid] = 0;  // bytes past the block read as zeros (never part of a match)
-    {
-      uint4* t16 = reinterpret_cast<uint4*>(S.T);
-      for (uint32_t k = tid; k < 4 * kScTabWords / 16; k += kScThreads) t16[k] = make_uint4(0, 0, 0, 0);
     }
     const uint32_t hv = a.header ? varint_len(n) : 0u;
-    if (tid < hv) dst[tid] = (uint8_t)(((n >> (7 * tid)) & 0x7f) | (tid + 1 < hv ? 0x80 : 0));
-    if (wave == 0) {  // the hand-off words (the previous block's users are past the barrier)
-      if (lane < kScRing) {
-        S.rsize[lane] = 0;
-        S.rseq[lane] = lane;
-      }
-      if (lane == 0) {
-        S.ins = 0;
-        S.next = 0;
-        S.err = 0;
-      }
-    }
+    sc_stage_block(S, src, n, inpf, dst, hv);
+    sc_reset_handoff(S, 0);  // (the previous block's users are past the barrier)
     // the block after this one (its stride scan now, its bytes when this wave runs out of work)
     const uint32_t bn = sc_next_block(a, b + g, g, lane);
     __syncthreads();
@@ -1099,21 +1057,6 @@ hipError_t launch_compress_sc_span(const CompressArgs& a, int mode, const ScSpan
   return hipGetLastError();
 }
 
-
-// the current device's CU count (cached per device)
-uint32_t compress_grid() {
-  static uint32_t ncu_cache[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  uint32_t ncu = __atomic_load_n(&ncu_cache[dev], __ATOMIC_RELAXED);
-  if (!ncu) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    ncu = (uint32_t)v;
-    __atomic_store_n(&ncu_cache[dev], ncu, __ATOMIC_RELAXED);
-  }
-  return ncu;
-}
 
 // mode 1 (SM_MODE_FAST): the more recent 4-byte match per position; mode 2 (SM_MODE_FAST_DENSE): the
 // longer of the two candidates over 16 bytes (smaller output, about 15% slower).  The blocks of a

@@ -65,6 +65,7 @@ SMC_HD inline uint32_t char_entry(uint32_t c) {
 #endif
 }
 
+using smc::varint_byte;
 using smc::varint_len;
 
 // ---- one tag (internal.jl:426-462) ---------------------------------------------------------------
@@ -132,19 +133,102 @@ SMC_HD inline int32_t check_tag(const Tag& t, uint64_t op, uint32_t size, uint64
   return avail_out < (int64_t)litlen || avail_in < (int64_t)litlen ? kErrLiteral : kOk;                           // :518
 }
 
-// bytes of the literal tag for a run of len (>0) bytes (internal.jl:271-284)
-SMC_HD inline uint32_t literal_tag_bytes(uint32_t len) {
-  uint32_t n = len - 1;
-  return n < 60 ? 1 : n < 256 ? 2 : n < 65536 ? 3 : n < (1u << 24) ? 4 : 5;
+// ---- the emit rules: what a compressor writes for one token ---------------------------------------
+// A tag's bytes packed little-endian (byte j of the stream is bytes >> 8 j) and how many they are.
+struct TagBytes {
+  uint64_t bytes;
+  uint32_t size;
+  SMC_HD uint8_t byte(uint32_t j) const { return (uint8_t)(bytes >> (8 * j)); }
+};
+
+// Which runs get the one-byte literal tag.  The format allows it up to 60 bytes, and the fast
+// modes, the literal fallbacks and the screen use all of it (kLiteralStd).  The reference does so
+// only below 60 (quirk Q3, internal.jl:271: a 60-byte run gets a two-byte tag), and reference mode
+// reproduces that byte for byte (kLiteralQ3).  The two differ at len = 60 and nowhere else.
+enum LiteralRule : uint32_t { kLiteralStd = 0, kLiteralQ3 = 1 };
+
+// emit_literal!'s tag (internal.jl:271-284) for a run of len (> 0) bytes: len - 1 in the tag byte,
+// or 60..63 there and len - 1 in the 1..4 bytes behind it.  literal_tag1 is the one-byte form alone,
+// for a caller that knows its run is shorter than 60 bytes (both rules agree there): the fast
+// parse's runs between two copies of one lane, where the general form's selects cost 1.4% of the
+// kernel.
+SMC_HD inline uint32_t literal_tag1(uint32_t len) { return (len - 1) << 2; }
+SMC_HD inline TagBytes literal_tag(uint32_t len, LiteralRule rule) {
+  const uint32_t n = len - 1;
+  const uint32_t count = n < 60u - rule ? 0 : n < 256 ? 1 : n < 65536 ? 2 : n < (1u << 24) ? 3 : 4;
+  return {count ? ((59 + count) << 2) | ((uint64_t)n << 8) : literal_tag1(len), 1 + count};
+}
+// ... and its size under the standard rule
+SMC_HD inline uint32_t literal_tag_bytes(uint32_t len) { return literal_tag(len, kLiteralStd).size; }
+
+// One emit_copy_upto_64! piece (internal.jl:289-304), len in 4..64: the two-byte form (length and
+// offset bits 8..10 in the tag byte) for short near copies, else the three-byte form.  Both
+// encodings, then a select: no branch on the device.
+SMC_HD inline TagBytes copy_piece(uint32_t offset, uint32_t len) {
+  const bool c1 = len < 12 && offset < 2048;
+  const uint32_t e1 = (1u + ((len - 4) << 2) + ((offset >> 3) & 0xe0u)) | ((offset & 0xffu) << 8);
+  const uint32_t e2 = (2u + ((len - 1) << 2)) | (offset << 8);
+  return {c1 ? e1 : e2, c1 ? 2u : 3u};
 }
 
-// bytes emit_copy! (internal.jl:306-329) produces for (offset, len)
+// emit_copy!'s split (internal.jl:306-329): the next piece of a copy with `remaining` (>= 4) bytes
+// to go -- 64 while 68 or more remain, 60 when more than 64 do (so the last piece is at least 4)
+SMC_HD inline uint32_t copy_piece_len(uint32_t remaining) {
+  return remaining >= 68 ? 64u : remaining > 64 ? 60u : remaining;
+}
+
+// Bytes emit_copy! produces for (offset, len), any len >= 4, in closed form: the pieces before the
+// last are (len - 1) >> 6 three-byte ones, and the last piece R is shorter than 12 exactly when
+// ((len - 1) & 63) < 11 (R = m + 4 for m = ((len - 1) & 63) + 1 < 4, else m).  The host checker
+// steps copy_piece_len over every len up to 65536 against it.  No multiply (3 n as n + 2 n).
 SMC_HD inline uint32_t copy_tag_bytes(uint32_t offset, uint32_t len) {
-  if (len < 12) return (offset < 2048) ? 2 : 3;
-  uint32_t b = 0;
-  while (len >= 68) { b += 3; len -= 64; }
-  if (len > 64) { b += 3; len -= 60; }
-  return b + ((len < 12 && offset < 2048) ? 2 : 3);
+  const uint32_t t = len - 1, n = t >> 6;
+  return n + 2 * n + (((t & 63) < 11 && offset < 2048) ? 2u : 3u);
+}
+
+// A block of n bytes written as ONE literal, the fallback of every parse that came out larger
+// (and the screen's output): varint(n) when the block carries its header, the standard literal
+// tag, the bytes.  An empty block is its header alone.  The size, and byte j of the varint and tag.
+SMC_HD inline uint32_t block_literal_bytes(uint32_t n, bool header) {
+  return (header ? varint_len(n) : 0u) + (n ? literal_tag_bytes(n) + n : 0u);
+}
+SMC_HD inline uint8_t block_literal_head_byte(uint32_t n, bool header, uint32_t j) {
+  const uint32_t hv = header ? varint_len(n) : 0u;
+  return j < hv ? varint_byte(n, j, hv) : literal_tag(n, kLiteralStd).byte(j - hv);
+}
+
+// ---- the parts of one block (k_compress_sc_span's outputs) joined into the block's stream --------
+// part_len[i]: part i's length, or a compressor's error mark.  A mark, or a part longer than its
+// pitch (it would have run into the next part's slot: never expected), refuses the block: mark is
+// the parts' marks or-ed, kOutLenError | 8 for an over-long part.  Part 0 may instead hold a
+// screened block's literal with its header (part0_literal: up to 5 bytes over the bare literal).
+// Otherwise bytes is the block's length in the stream and before the bytes ahead of part j: the
+// parts behind one another, or -- when they sum to more than the block as one literal, or the
+// block is empty -- that literal (block_literal_bytes; before = 0, only j = 0 writes it).
+struct PartsVerdict {
+  uint32_t mark;    // != 0: the block's error mark, nothing is written
+  uint32_t bytes;
+  uint32_t before;
+  bool literal;
+};
+SMC_HD inline PartsVerdict parts_verdict(const uint32_t* part_len, uint32_t parts, uint32_t j, uint32_t pitch,
+                                         uint32_t n, bool header, bool part0_literal) {
+  const uint32_t lit = block_literal_bytes(n, header);
+  uint32_t sum = 0, before = 0, mark = 0;
+  for (uint32_t i = 0; i < parts; ++i) {
+    const uint32_t L = part_len[i];
+    const uint32_t bound = (i == 0 && part0_literal && lit + 5u > pitch) ? lit + 5u : pitch;
+    if (L >= kOutLenError)
+      mark |= L;
+    else if (L > bound)
+      mark |= kOutLenError | 8u;
+    else {
+      sum += L;
+      before += i < j ? L : 0u;
+    }
+  }
+  const bool literal = n == 0 || sum > lit;
+  return {mark, literal ? lit : sum, literal ? 0u : before, literal};
 }
 
 }  // namespace sm

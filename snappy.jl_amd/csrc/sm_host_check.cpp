@@ -567,6 +567,159 @@ void check_varint_rule() {
   }
 }
 
+// ---- the emit rules (sm_format.h, smc_layout.h) --------------------------------------------------
+// Expected values: the oracle's encoder and decoder, decode_tag's round trip (itself swept against
+// the oracle's table above), and the reference's loops and tables written out here.
+
+Bytes tag_bytes(const sm::TagBytes& t) {
+  Bytes b;
+  for (uint32_t j = 0; j < t.size; ++j) b.push_back(t.byte(j));
+  return b;
+}
+sm::Tag decode_bytes(const Bytes& b) {
+  uint32_t tr = 0;
+  for (uint32_t k = 0; k < 4; ++k) tr |= (1 + k < b.size() ? (uint32_t)b[1 + k] : 0u) << (8 * k);
+  return sm::decode_tag(b[0], tr);
+}
+
+// varint(len), the rule's literal tag, len filler bytes
+Bytes literal_stream(uint32_t len, sm::LiteralRule rule, const Bytes& body) {
+  Bytes s;
+  put_varint(s, len);
+  const Bytes t = tag_bytes(sm::literal_tag(len, rule));
+  s.insert(s.end(), t.begin(), t.end());
+  s.insert(s.end(), body.begin(), body.end());
+  return s;
+}
+
+// emit_copy!'s loop (internal.jl:306-329), written out: the pieces' lengths
+std::vector<uint32_t> copy_pieces(uint32_t len) {
+  std::vector<uint32_t> p;
+  while (len >= 68) { p.push_back(64); len -= 64; }
+  if (len > 64) { p.push_back(60); len -= 60; }
+  p.push_back(len);
+  return p;
+}
+
+void check_emit_rules() {
+  // varint_byte: every length class, both ends of each
+  for (uint32_t v : {0u, 127u, 128u, 16383u, 16384u, (1u << 21) - 1, 1u << 21, (1u << 28) - 1, 1u << 28, 0xffffffffu}) {
+    uint8_t a[5];
+    const size_t na = smo_encode32(a, v);
+    for (size_t i = 0; i < na; ++i) EXPECT(smc::varint_byte(v, (uint32_t)i, (uint32_t)na) == a[i]);
+  }
+  // literal_tag, standard rule
+  for (uint32_t len : {1u, 59u, 60u, 61u, 255u, 256u, 257u, 65535u, 65536u, 65537u, 1u << 24, (1u << 24) + 1, 0xffffffffu}) {
+    const sm::TagBytes t = sm::literal_tag(len, sm::kLiteralStd);
+    const uint32_t want = len <= 60 ? 1 : len <= 256 ? 2 : len <= 65536 ? 3 : len <= (1u << 24) ? 4 : 5;
+    const sm::Tag d = decode_bytes(tag_bytes(t));
+    EXPECT(t.size == want && sm::literal_tag_bytes(len) == want && t.size <= 5 && (t.size == 5 || t.bytes >> (8 * t.size) == 0));
+    EXPECT(!d.is_copy() && d.literal_len() == len && 1 + d.taglen == t.size);
+    if (len <= 65536) {
+      Bytes body(len), out(len + 1);
+      for (uint32_t k = 0; k < len; ++k) body[k] = filler(k);
+      const Bytes s = literal_stream(len, sm::kLiteralStd, body);
+      size_t got = 0;
+      EXPECT(smo_uncompress(s.data(), s.size(), out.data(), out.size(), &got) == SMO_OK && got == len &&
+             memcmp(out.data(), body.data(), len) == 0);
+      EXPECT(sm::block_literal_bytes(len, true) == s.size() && sm::block_literal_bytes(len, false) == s.size() - smc::varint_len(len));
+      for (uint32_t j = 0; j + len < s.size(); ++j) {
+        EXPECT(sm::block_literal_head_byte(len, true, j) == s[j]);
+        if (j >= smc::varint_len(len)) EXPECT(sm::block_literal_head_byte(len, false, j - smc::varint_len(len)) == s[j]);
+      }
+    }
+  }
+  EXPECT(sm::block_literal_bytes(0, true) == 1 && sm::block_literal_bytes(0, false) == 0 && sm::block_literal_head_byte(0, true, 0) == 0);
+  // ... and the reference's rule (Q3): another tag at 60 and nowhere else; the streams are the oracle's
+  for (uint32_t len = 1; len <= 70000; ++len) {
+    const sm::TagBytes a = sm::literal_tag(len, sm::kLiteralStd), q = sm::literal_tag(len, sm::kLiteralQ3);
+    EXPECT((a.size == q.size && a.bytes == q.bytes) == (len != 60));
+    if (len < 60) EXPECT(q.size == 1 && q.bytes == sm::literal_tag1(len) && sm::literal_tag1(len) == ((len - 1) << 2));
+  }
+  {
+    const sm::TagBytes q = sm::literal_tag(60, sm::kLiteralQ3);
+    EXPECT(q.size == 2 && q.bytes == (0xf0u | 59u << 8) && decode_bytes(tag_bytes(q)).literal_len() == 60);
+    Bytes in(60);
+    for (uint32_t k = 0; k < 60; ++k) in[k] = (uint8_t)(k * 37 + 11);  // 60 distinct bytes: no match
+    for (int compat = 0; compat < 2; ++compat) {
+      Bytes out(smo_max_compressed_length(in.size()));
+      size_t n = out.size();
+      EXPECT(smo_compress(in.data(), in.size(), out.data(), &n, compat) == SMO_OK);
+      out.resize(n);
+      EXPECT(out == literal_stream(60, compat ? sm::kLiteralStd : sm::kLiteralQ3, in));
+    }
+  }
+  // copy_piece: every length of a piece against both offset classes' edges
+  for (uint32_t len = 4; len <= 64; ++len)
+    for (uint32_t off : {1u, 7u, 2047u, 2048u, 65535u}) {
+      const sm::TagBytes c = sm::copy_piece(off, len);
+      const sm::Tag d = decode_bytes(tag_bytes(c));
+      EXPECT(c.size == ((len < 12 && off < 2048) ? 2u : 3u) && c.bytes >> (8 * c.size) == 0);
+      EXPECT(d.is_copy() && d.offset() == off && d.len() == len && 1 + d.taglen == c.size);
+    }
+  // copy_piece_len stepped, and copy_tag_bytes' closed form, against the loop above
+  for (uint32_t len = 4; len <= 65536; ++len) {
+    const std::vector<uint32_t> want = copy_pieces(len);
+    std::vector<uint32_t> got;
+    for (uint32_t r = len; r;) {
+      got.push_back(sm::copy_piece_len(r));
+      r -= got.back();
+    }
+    const uint32_t last = want.back(), before = 3 * ((uint32_t)want.size() - 1);
+    const bool ok = got == want && sm::copy_tag_bytes(1, len) == before + (last < 12 ? 2 : 3) &&
+                    sm::copy_tag_bytes(2047, len) == before + (last < 12 ? 2 : 3) && sm::copy_tag_bytes(2048, len) == before + 3 &&
+                    sm::copy_tag_bytes(65535, len) == before + 3;
+    if (!ok) {
+      EXPECT(ok);
+      fprintf(stderr, "  copy length %u\n", len);
+      break;
+    }
+  }
+  // parts_verdict: a block of 1000 bytes (its literal: 3 + 1000, with header 2 more) in 4 parts of pitch 400
+  struct Case {
+    std::vector<uint32_t> len;
+    uint32_t n;
+    bool header, part0;
+    uint32_t mark, bytes;
+    bool literal;
+    std::vector<uint32_t> before;
+  };
+  const uint32_t E = sm::kOutLenError;
+  const Case cases[] = {
+      {{100, 200, 300, 50}, 1000, false, false, 0, 650, false, {0, 100, 300, 600}},     // all parts fine
+      {{400, 400, 203, 0}, 1000, false, false, 0, 1003, false, {0, 400, 800, 1003}},    // the literal's size: the parts
+      {{400, 400, 204, 0}, 1000, false, false, 0, 1003, true, {0, 0, 0, 0}},            // one over: the literal
+      {{400, 400, 205, 0}, 1000, true, false, 0, 1005, false, {0, 400, 800, 1005}},     // ... with the header
+      {{400, 400, 206, 0}, 1000, true, false, 0, 1005, true, {0, 0, 0, 0}},
+      {{100, E | 4, 300, 50}, 1000, false, false, E | 4, 0, false, {}},                 // a part's own mark
+      {{100, E | 4, 401, E | 2}, 1000, false, false, E | 4 | 8 | 2, 0, false, {}},      // ... or-ed with the others
+      {{0xffffffffu, 0, 0, 0}, 1000, false, true, 0xffffffffu, 0, false, {}},           // not a block
+      {{400, 401, 0, 0}, 1000, false, false, E | 8, 0, false, {}},                      // a part over its pitch
+      {{401, 0, 0, 0}, 1000, false, false, E | 8, 0, false, {}},
+      {{1008, 0, 0, 0}, 1000, false, false, E | 8, 0, false, {}},                       // no allowance unless asked for
+      {{1003, 0, 0, 0}, 1000, false, true, 0, 1003, false, {0, 1003, 1003, 1003}},      // a screened part 0
+      {{1008, 0, 0, 0}, 1000, false, true, 0, 1003, true, {0, 0, 0, 0}},                // ... at lit + 5
+      {{1009, 0, 0, 0}, 1000, false, true, E | 8, 0, false, {}},                        // ... and one over
+      {{300, 0, 0, 0}, 100, false, true, 0, 102, true, {0, 0, 0, 0}},                   // (lit + 5 below the pitch: the pitch)
+      {{401, 0, 0, 0}, 100, false, true, E | 8, 0, false, {}},
+      {{0, 0, 0, 0}, 0, true, false, 0, 1, true, {0, 0, 0, 0}},                         // an empty block: its header
+      {{0, 0, 0, 0}, 0, false, false, 0, 0, true, {0, 0, 0, 0}},                        // ... or nothing
+  };
+  for (const Case& c : cases) {
+    const auto pl = exact(c.len);
+    for (uint32_t j = 0; j < 4; ++j) {
+      const sm::PartsVerdict v = sm::parts_verdict(pl.get(), 4, j, 400, c.n, c.header, c.part0);
+      bool ok = v.mark == c.mark;
+      if (!c.mark) ok = ok && v.bytes == c.bytes && v.literal == c.literal && v.before == c.before[j];
+      if (!ok) {
+        EXPECT(ok);
+        fprintf(stderr, "  parts case %zu, part %u: mark %x bytes %u before %u literal %d\n", (size_t)(&c - cases), j, v.mark,
+                v.bytes, v.before, (int)v.literal);
+      }
+    }
+  }
+}
+
 // ---- scratch layouts --------------------------------------------------------------------------
 
 struct Array {
@@ -671,6 +824,7 @@ int main(int argc, char** argv) {
   check_tags();
   check_checks();
   check_varint_rule();
+  check_emit_rules();
   check_carves();
   if (failures) {
     fprintf(stderr, "sm_host_check: %d failure(s)\n", failures);

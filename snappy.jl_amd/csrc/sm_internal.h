@@ -1,6 +1,6 @@
 // sm_internal.h -- launcher interfaces between the C-ABI layer (sm_api.hip) and the
-// kernels (sm_compress.hip, sm_compress_fast.hip, sm_compress_sc.hip; sm_decompress.hip,
-// sm_dec_stream.hip).  Not part of the public ABI.
+// kernels (sm_compress.hip, sm_compress_fast.hip, sm_compress_sc.hip, sm_gather.hip;
+// sm_decompress.hip, sm_dec_stream.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -48,6 +48,12 @@ struct DecompressArgs {
   uint32_t one_n = 0;
   uint32_t one_cap = 0;
 };
+
+// out_len marks.  kNotABlock: a block longer than 64 KiB was refused (an error mark: it is above
+// kOutLenError).  kScreenTodo: k_literal_screen's verdict "the parse compresses this block", read by
+// the parse kernels of the same call and overwritten by them.
+constexpr uint32_t kNotABlock = 0xffffffffu;
+constexpr uint32_t kScreenTodo = 0xfffffffeu;
 
 // mode 0 = reference (byte-identical to Snappy.jl), 1 = fast (wave-parallel parse), 2 = fast, denser
 hipError_t launch_compress(const CompressArgs& a, int mode, hipStream_t s);
@@ -134,7 +140,7 @@ hipError_t launch_parts_gather(const uint8_t* src, const uint64_t* out_off, cons
 // persistent whole-block kernel runs ceil(nblk / grid) rounds of blocks, the last of them on
 // nblk % grid workgroups only.  When that remainder is at most half the grid, its blocks are parsed
 // in `parts` parts each on workgroups of their own (span items of the same launch) and joined into the
-// caller's slots (k_gather_parts, the batch overload): the same bytes and lengths.
+// caller's slots (k_gather_parts_batch): the same bytes and lengths.
 constexpr uint32_t kBlockScs = 64;       // 1 KiB super-chunks of a 64 KiB block
 constexpr uint32_t kPartMinScs = 4;      // a part is at least this many super-chunks
 struct BatchParts {
@@ -152,7 +158,21 @@ inline BatchParts batch_parts_rule(uint32_t nblk, uint32_t grid) {
 // aligned), then their lengths
 inline size_t batch_parts_len_offset(uint32_t grid) { return (size_t)(grid / 2) * kBlockScs * kSpanSlot; }
 inline size_t batch_parts_scratch(uint32_t grid) { return batch_parts_len_offset(grid) + 4 * (size_t)grid; }
-uint32_t compress_grid();  // the whole-block kernel's workgroup count for large batches: the device's CUs
+// the current device's CU count (cached per device): the whole-block kernels' workgroup count for
+// large batches, and reference mode's bound for one staged block per CU
+inline uint32_t compress_grid() {
+  static uint32_t ncu_cache[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  uint32_t ncu = __atomic_load_n(&ncu_cache[dev], __ATOMIC_RELAXED);
+  if (!ncu) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+    ncu = (uint32_t)v;
+    __atomic_store_n(&ncu_cache[dev], ncu, __ATOMIC_RELAXED);
+  }
+  return ncu;
+}
 // launch_compress for modes 1 and 2 with the last bp.rem blocks in parts (bp from batch_parts_rule
 // with compress_grid(); bp.rem != 0); scratch: batch_parts_scratch(compress_grid()) bytes, in use
 // until the launches have run

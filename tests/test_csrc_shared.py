@@ -131,3 +131,65 @@ def test_framing_headers_are_in_the_version_hash():
     hdrs = re.search(r"^HDRS\s*=(.*)$", mk, re.M).group(1).split()
     here = {f.split("/", 1)[1] for f in _sources() if f.startswith("framing/") and f.endswith(".h")}
     assert here and here <= set(hdrs), (here, hdrs)
+
+
+def test_emit_rules_have_one_definition():
+    """What a compressor writes for one token is written once, beside its decode twin: the varint
+    byte in common/smc_layout.h; the literal tag (with the reference's Q3 rule as a named choice),
+    the copy piece, emit_copy!'s split, the closed form of its size, a block as one literal and the
+    verdict over a block's parts in sm_format.h.  The kernels call them; none restates one."""
+    src = _sources()
+    for name, where in (("varint_byte", "common/smc_layout.h"), ("literal_tag", "sm_format.h"),
+                        ("literal_tag1", "sm_format.h"), ("literal_tag_bytes", "sm_format.h"), ("copy_piece", "sm_format.h"),
+                        ("copy_piece_len", "sm_format.h"), ("copy_tag_bytes", "sm_format.h"),
+                        ("block_literal_bytes", "sm_format.h"), ("block_literal_head_byte", "sm_format.h"),
+                        ("parts_verdict", "sm_format.h")):
+        found = _definitions(r"\b[\w:<>]+[\s\*&]+%s\s*\([^;{}]*\)\s*\{" % name)
+        assert found == [where], (name, found)
+    assert not re.search(r"#\s*include\s*[<\"]hip/", src["sm_format.h"])
+    product = {f: text for f, text in src.items() if not f.endswith("_check.cpp")}
+    forms = {
+        "varint byte": r"&\s*0x7f\s*\)\s*\|\s*\([^;]*\?\s*0x80",
+        "literal tag": r"\(\s*5[89]\s*\+\s*\w+\s*\)\s*<<\s*2|\b6[0-3]u?\s*<<\s*2",
+        "copy-1 tag": r"&\s*0xe0",
+    }
+    where = {"varint byte": "common/smc_layout.h", "literal tag": "sm_format.h", "copy-1 tag": "sm_format.h"}
+    for what, pattern in forms.items():
+        found = sorted(f for f, text in product.items() if re.search(pattern, text))
+        assert found == [where[what]], (what, found)
+    # the one-byte literal tag's threshold is the named rule, not a `< 60` against a `<= 60` elsewhere
+    assert re.search(r"enum\s+LiteralRule\b[^;]*kLiteralStd[^;]*kLiteralQ3", src["sm_format.h"])
+    q3 = sorted(f for f, text in product.items() if "kLiteralQ3" in text)
+    assert q3 == ["sm_compress.hip", "sm_format.h"], q3
+    # the one-byte form alone (literal_tag1) is called where a run is known to be short: the fast parse's
+    # runs inside one lane's 16 positions -- and by literal_tag itself
+    short = sorted((f, len(re.findall(r"\bliteral_tag1\s*\(", text))) for f, text in product.items() if "literal_tag1" in text)
+    assert short == [("sm_compress_sc.hip", 1), ("sm_format.h", 2)], short
+    for f, text in product.items():  # no call passes the rule as a bare literal
+        assert not re.search(r"\bliteral_tag\s*\([^()]*,\s*(?:0|1|true|false)\s*\)", text), f
+    for name in ("cu_count", "kScreenTodoSc", "sc_lit_tag", "sc_copy_piece", "sc_copy_bytes", "put_copy_upto_64"):
+        found = [f for f, text in src.items() if re.search(r"\b%s\b" % name, text)]
+        assert not found, (name, found)
+    for name, where_ in (("compress_grid", "sm_internal.h"), ("launch_screen", "sm_compress_fast.hip"),
+                         ("sc_stage_block", "sm_compress_sc.hip"), ("sc_reset_handoff", "sm_compress_sc.hip")):
+        found = _definitions(r"\b[\w:<>]+[\s\*&]+%s\s*\([^;{}]*\)\s*\{" % name)
+        assert found == [where_], (name, found)
+    sc = src["sm_compress_sc.hip"]
+    assert len(re.findall(r"\bsc_stage_block\s*\(", sc)) == 3 and len(re.findall(r"\bsc_reset_handoff\s*\(", sc)) == 3
+    assert len(re.findall(r"\blaunch_screen\s*\(", src["sm_compress_fast.hip"])) == 4  # the definition, three launchers
+    for name in ("kScreenTodo", "kNotABlock"):
+        found = _definitions(r"\bconstexpr\s+uint32_t\s+%s\s*=" % name)
+        assert found == ["sm_internal.h"], (name, found)
+    marks = sorted(f for f, text in product.items() if re.search(r"0xfff00000u|0xfffffffeu", text, re.I))
+    assert marks == ["sm_format.h", "sm_internal.h"], marks
+    # the batch parts gather decides by the one verdict.  The single-stream one keeps the rule in its
+    # parallel form (a thread per part, a butterfly sum): on the single-buffer call's latency path the
+    # rule as a loop per thread measured 2.5 to 3 us slower (DESIGN.md section 3.7).  Exactly that one
+    # restatement remains: the part-0 allowance and the butterfly occur once outside sm_format.h.
+    assert len(re.findall(r"\bparts_verdict\s*\(", src["sm_gather.hip"])) == 1
+    allowance = sorted((f, len(re.findall(r"\blit\s*\+\s*5u", text))) for f, text in product.items() if re.search(r"\blit\s*\+\s*5u", text))
+    assert allowance == [("sm_format.h", 2), ("sm_gather.hip", 1)], allowance
+    assert len(re.findall(r"__shfl_xor", src["sm_gather.hip"])) == 1
+    for name in ("block_literal_bytes", "put_literal_head"):  # ... and its literal comes from the shared rules
+        assert len(re.findall(r"\b%s\s*\(" % name, src["sm_gather.hip"])) >= 2, name
+    assert re.search(r"\bk_gather_parts\s*\(", src["sm_gather.hip"]) and re.search(r"\bk_gather_parts_batch\s*\(", src["sm_gather.hip"])

@@ -72,7 +72,7 @@ def test_bench_visible_gpus_from_sysfs(monkeypatch):
 
 
 def test_copy_tag_bytes_closed_form():
-    """k_compress_sc's sc_copy_bytes: emit_copy!'s tag bytes (src/internal.jl:306-329) in closed
+    """copy_tag_bytes (sm_format.h; sm_host_check sweeps the compiled rule): emit_copy!'s tag bytes (src/internal.jl:306-329) in closed
     form, 3 ((L - 1) >> 6) + (2 if ((L - 1) & 63) < 11 and offset < 2048 else 3), against the
     reference's piece loop for every copy length the kernel emits (4..255) and both offset classes."""
     def loop(off, L):

@@ -17,7 +17,7 @@ BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 # every kernel the product launches (sm_api.hip launch_* paths), by unmangled base name
 PRODUCT_KERNELS = {
     "k_compress_exact", "k_literal_screen", "k_compress_sc", "k_compress_sc_span",
-    "k_gather", "k_gather16", "k_gather_parts", "k_frag_plan", "k_place",
+    "k_gather", "k_gather16", "k_gather_parts", "k_gather_parts_batch", "k_frag_plan", "k_place",
     "k_decompress", "k_decompress_one", "k_decompress_frags", "k_validate", "k_uncompressed_length",
     "k_stream_index", "k_stream_chain", "k_origin_fill", "k_origin_fill_dev", "k_origin_resolve",
     "k_origin_gather", "k_small_resolve", "k_to_host", "k_path_check", "k_literal_spans",
