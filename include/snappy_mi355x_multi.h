@@ -16,8 +16,8 @@
  * Threading: an smm_ctx owns an sm_ctx and scratch, and one caller at a time may use it: the
  * *_device calls keep their per-call arrays in the ctx's scratch, so two of them on one ctx must
  * be on one stream (or ordered by the caller), and a call that grows the scratch waits for the
- * device first (hipFree), as smf_compress_device does.  smm_compress / smm_uncompress lock the ctx.
- * Neither *_device call synchronises otherwise: every decision is taken on the device.
+ * device first (hipFree), as smf_compress_device does.  smm_compress / smm_uncompress / smm_index lock
+ * the ctx.  No *_device call synchronises otherwise: every decision is taken on the device.
  */
 #ifndef SNAPPY_MI355X_MULTI_H_
 #define SNAPPY_MI355X_MULTI_H_
@@ -55,8 +55,14 @@ sm_status smm_index_check(const uint8_t* in, const uint64_t* in_off, const uint3
                           uint32_t max_fragments, const uint32_t* out_cap, const uint32_t* frag_first,
                           const uint32_t* frag_pos, uint8_t* indexed);
 
+/* The index rule of smm_index_device (below) on the CPU, over host arrays: the same results, no
+ * device and no ctx.  frag_pos has max_fragments entries. */
+sm_status smm_index_host(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t nstreams,
+                         uint32_t max_fragments, const uint32_t* out_cap, uint32_t* frag_first, uint32_t* frag_pos,
+                         uint8_t* built, int32_t* status);
+
 /* ---- device memory, asynchronous on `stream` (a hipStream_t; NULL = the default stream) ----
- * Compress.  Stream s: input d_in[d_in_off[s] .. +d_in_len[s]) at any alignment -> one complete raw
+ * Compress. Stream s: input d_in[d_in_off[s] .. +d_in_len[s]) at any alignment -> one complete raw
  * Snappy stream at d_out + d_out_off[s], which must have room for
  * sm_max_compressed_length(d_in_len[s]) bytes: varint(len), then the fragments of
  * src/Snappy.jl:29-33 with no gaps -- what sm_compress gives for that input in the same mode, and
@@ -108,6 +114,34 @@ sm_status smm_uncompress_device(smm_ctx* ctx, const uint8_t* d_in, const uint64_
                                 const uint32_t* d_out_cap, uint32_t* d_out_len, int32_t* d_status,
                                 const uint32_t* d_frag_first, const uint32_t* d_frag_pos, void* stream);
 
+/* Index.  Builds, for raw streams that arrive without one (a CPU compressor wrote them, or the
+ * index was not kept), the index smm_uncompress_device accepts: no host synchronisation, no output
+ * bytes.  Every block compressor emits 64 KiB blocks independently (src/Snappy.jl:29-33), so a tag
+ * starts at every output multiple of 65536, and finding those tags is a walk over tag sizes.
+ * Stream s, bytes p[0 .. n) with n = d_in_len[s] and cap = d_out_cap[s] (d_out_cap NULL: no cap):
+ *   count(s)     = smm_fragment_count(D) when n is no error mark (n < SM_OUT_LEN_ERROR), the varint
+ *                  header parses to D with hv bytes, and D <= cap; else 0;
+ *   d_frag_first (nstreams + 1)  the exclusive scan of count, as smm_compress_device writes it;
+ *   D <= 65536:  the stream's entry (if any) is hv; d_built[s] = 0 (never decoded by fragments);
+ *   D > 65536:   tags are sized from x = hv with output o = 0 and f = 0, bytes at or past n reading
+ *                as zero, positions and outputs in 64 bits, no offset or length checked.  Before
+ *                each tag: x >= n fails; o == 65536 f records d_frag_pos[d_frag_first[s] + f] = x
+ *                and steps f, and f == count ends the walk with d_built[s] = 1; o > 65536 f fails
+ *                (a tag crosses the multiple: no block compressor wrote the stream).  A failed
+ *                stream has d_built[s] = 0 and all its entries 0, as a failed stream has from
+ *                smm_compress_device: smm_uncompress_device then decodes it in stream order.
+ * When the counts sum to more than max_fragments: every d_status[s] = SM_ERR_ARGUMENT, every
+ * d_built[s] = 0, d_frag_first is all zeros (a usable empty index) and d_frag_pos is untouched.
+ * Otherwise every d_status[s] = SM_OK.  Entries of d_frag_pos at or past d_frag_first[nstreams] are
+ * never written.  The result says nothing about validity: it stays an untrusted hint, and the
+ * fragment decode and its fallback decide as before.  A stream is one serial walk by one wave, so a
+ * batch of many streams is what this call is for.
+ * Returns SM_ERR_ARGUMENT for a NULL ctx or array (d_out_cap may be NULL; d_frag_pos may be with
+ * max_fragments 0); SM_ERR_DEVICE when a launch or the scratch allocation failed. */
+sm_status smm_index_device(smm_ctx* ctx, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                           uint32_t nstreams, uint32_t max_fragments, const uint32_t* d_out_cap, uint32_t* d_frag_first,
+                           uint32_t* d_frag_pos, uint8_t* d_built, int32_t* d_status, void* stream);
+
 /* diagnostic: the number of streams the ctx's last smm_uncompress_device (or smm_uncompress)
  * decoded by fragments; waits for the device.  -1 for a NULL ctx or before the first call. */
 int smm_ctx_last_indexed(smm_ctx* ctx);
@@ -124,6 +158,11 @@ sm_status smm_compress(smm_ctx* ctx, const uint8_t* in, const uint64_t* in_off, 
 sm_status smm_uncompress(smm_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
                          uint32_t nstreams, uint8_t* out, const uint64_t* out_off, const uint32_t* out_cap,
                          uint32_t* out_len, int32_t* status, const uint32_t* frag_first, const uint32_t* frag_pos);
+/* smm_index_device over host arrays; frag_pos has max_fragments entries, of which the first
+ * frag_first[nstreams] are written. */
+sm_status smm_index(smm_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t nstreams,
+                    uint32_t max_fragments, const uint32_t* out_cap, uint32_t* frag_first, uint32_t* frag_pos,
+                    uint8_t* built, int32_t* status);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 // smm_api.hip -- C ABI of the multi-stream library (include/snappy_mi355x_multi.h) over the raw
 // codec's public batched device calls (libsnappy_mi355x.so, linked by name) and the kernels of
-// smm_kernels.hip.  The host-only entry points live in smm_host.cpp.
+// smm_kernels.hip and smm_index.hip.  The host-only entry points live in smm_host.cpp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -149,6 +149,25 @@ sm_status smm_uncompress_device(smm_ctx* ctx, const uint8_t* d_in, const uint64_
   return SM_OK;
 }
 
+// Launch sequence: the counts' scan (with the short streams' entries), the walk of the long streams.
+sm_status smm_index_device(smm_ctx* ctx, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                           uint32_t nstreams, uint32_t max_fragments, const uint32_t* d_out_cap, uint32_t* d_frag_first,
+                           uint32_t* d_frag_pos, uint8_t* d_built, int32_t* d_status, void* stream) {
+  if (!ctx || !d_frag_first) return SM_ERR_ARGUMENT;
+  hipStream_t s = (hipStream_t)stream;
+  DeviceGuard g(ctx->device);
+  if (nstreams == 0) {
+    SM_CHECK(hipMemsetAsync(d_frag_first, 0, 4, s));
+    return SM_OK;
+  }
+  if (!d_in || !d_in_off || !d_in_len || !d_built || !d_status || (!d_frag_pos && max_fragments)) return SM_ERR_ARGUMENT;
+  SM_CHECK(ctx->meta.ensure(smm::index_scratch_bytes(nstreams)));
+  smm::IndexPlan p{d_in,         d_in_off,   d_in_len, nstreams, max_fragments, d_out_cap,
+                   d_frag_first, d_frag_pos, d_built,  d_status, smm::carve_index((uint8_t*)ctx->meta.p, nstreams)};
+  SM_CHECK(smm::launch_index(p, s));
+  return SM_OK;
+}
+
 // ---- host buffers ------------------------------------------------------------------------------
 
 namespace {  // (its functions are static: inside extern "C" the unnamed namespace alone still exports them)
@@ -158,6 +177,7 @@ struct HostArrays {
   uint64_t *in_off, *out_off;
   uint32_t *in_len, *cap, *out_len, *first, *pos;
   int32_t* status;
+  uint8_t* built;  // (smm_index)
   uintptr_t end;
 };
 static HostArrays carve_host(uintptr_t base, size_t n, size_t entries) {
@@ -171,6 +191,7 @@ static HostArrays carve_host(uintptr_t base, size_t n, size_t entries) {
   a.status = c.take<int32_t>(n);
   a.first = c.take<uint32_t>(n + 1);
   a.pos = c.take<uint32_t>(entries);
+  a.built = c.take<uint8_t>(n);
   a.end = c.p;
   return a;
 }
@@ -283,6 +304,44 @@ sm_status smm_uncompress(smm_ctx* ctx, const uint8_t* in, const uint64_t* in_off
   for (size_t i = 0; i < n; ++i)
     if (status[i] != SM_OK) out_len[i] = 0;
   return copy_out(ctx, out, out_off, out_len, status, n, in_len, out_cap, s);
+}
+
+sm_status smm_index(smm_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t nstreams,
+                    uint32_t max_fragments, const uint32_t* out_cap, uint32_t* frag_first, uint32_t* frag_pos,
+                    uint8_t* built, int32_t* status) {
+  if (!ctx || !frag_first) return SM_ERR_ARGUMENT;
+  if (nstreams == 0) {
+    frag_first[0] = 0;
+    return SM_OK;
+  }
+  if (!in || !in_off || !in_len || !built || !status || (!frag_pos && max_fragments)) return SM_ERR_ARGUMENT;
+  const size_t n = nstreams, m = max_fragments;
+  size_t in_total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (in_len[i] >= SM_OUT_LEN_ERROR) continue;  // (an error mark: no entries, unread)
+    const size_t ie = in_off[i] + in_len[i];
+    if (ie > in_total) in_total = ie;
+  }
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  SM_CHECK(ctx->io_meta.ensure(carve_host(0, n, m).end));
+  const HostArrays a = carve_host((uintptr_t)ctx->io_meta.p, n, m);
+  SM_CHECK(ctx->io_in.ensure(in_total + 16));
+  if (in_total) SM_CHECK(hipMemcpyAsync(ctx->io_in.p, in, in_total, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(a.in_off, in_off, 8 * n, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(a.in_len, in_len, 4 * n, hipMemcpyHostToDevice, s));
+  if (out_cap) SM_CHECK(hipMemcpyAsync(a.cap, out_cap, 4 * n, hipMemcpyHostToDevice, s));
+  SM_PASS(smm_index_device(ctx, (const uint8_t*)ctx->io_in.p, a.in_off, a.in_len, nstreams, max_fragments,
+                           out_cap ? a.cap : nullptr, a.first, a.pos, a.built, a.status, s));
+  SM_CHECK(hipMemcpyAsync(frag_first, a.first, 4 * (n + 1), hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(built, a.built, n, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(status, a.status, 4 * n, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipStreamSynchronize(s));
+  const size_t entries = frag_first[n];  // (at most max_fragments: the device's own scan)
+  if (entries > m) return SM_ERR_DEVICE;
+  if (entries) SM_CHECK(hipMemcpy(frag_pos, a.pos, 4 * entries, hipMemcpyDeviceToHost));
+  return SM_OK;
 }
 
 }  // extern "C"

@@ -36,4 +36,35 @@ sm_status smm_index_check(const uint8_t* in, const uint64_t* in_off, const uint3
   return SM_OK;
 }
 
+// smm_index_device in stream order: k_index_count's counts and scan, then the walk of every stream
+// that declares more than 64 KiB as the scalar loop (smm_plan.h index_walk)
+sm_status smm_index_host(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t nstreams,
+                         uint32_t max_fragments, const uint32_t* out_cap, uint32_t* frag_first, uint32_t* frag_pos,
+                         uint8_t* built, int32_t* status) {
+  if (!frag_first) return SM_ERR_ARGUMENT;
+  frag_first[0] = 0;
+  if (nstreams == 0) return SM_OK;
+  if (!in || !in_off || !in_len || !built || !status || (!frag_pos && max_fragments)) return SM_ERR_ARGUMENT;
+  uint64_t total = 0;
+  for (uint32_t s = 0; s < nstreams; ++s)
+    total += smm::index_count(in + in_off[s], in_len[s], out_cap ? out_cap[s] : 0xffffffffu).count;
+  const bool stop = total > max_fragments;
+  uint32_t e = 0;
+  for (uint32_t s = 0; s < nstreams; ++s) {
+    status[s] = stop ? SM_ERR_ARGUMENT : SM_OK;
+    built[s] = 0;
+    frag_first[s] = e;
+    if (stop) continue;
+    const uint8_t* p = in + in_off[s];
+    const smm::IndexCount c = smm::index_count(p, in_len[s], out_cap ? out_cap[s] : 0xffffffffu);
+    if (c.D > smm::kBlock)
+      built[s] = smm::index_walk(p, in_len[s], c.hv, c.count, frag_pos + e);
+    else if (c.count)
+      frag_pos[e] = c.hv;
+    e += c.count;
+  }
+  frag_first[nstreams] = e;
+  return SM_OK;
+}
+
 }  // extern "C"

@@ -1,7 +1,9 @@
 // smm_host_check.cpp -- stand-alone driver of smm_host.cpp (no device, no HIP): the index rules of
 // smm_uncompress_device over every structural case, on heap buffers of exactly the documented sizes,
 // so that AddressSanitizer and UBSan (make host_check) see any read past an array that an index
-// value could cause.  The rules are the device plan's own code (smm_plan.h).
+// value could cause.  The rules are the device plan's own code (smm_plan.h).  Then smm_index_host,
+// the rule that builds an index, over streams built from tag bytes on heap buffers of exactly the
+// streams' size: a walk that read past a stream's end, or wrote past its entries, stops here.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -87,6 +89,162 @@ std::vector<uint8_t> run(const std::vector<Stream>& streams, uint32_t max_fragme
 
 typedef std::vector<uint32_t> U;
 typedef std::vector<uint8_t> B;
+
+// ---- smm_index_host: streams built from tag bytes, the expected entries worked out by hand --------
+void put_lit(B& s, uint32_t n) {  // a literal of n filler bytes: the tag, 0..3 length bytes, the bytes
+  const uint32_t m = n - 1;
+  if (m < 60) {
+    s.push_back((uint8_t)(m << 2));
+  } else {
+    const uint32_t k = m < 256 ? 1 : m < 65536 ? 2 : 3;
+    s.push_back((uint8_t)((59 + k) << 2));
+    for (uint32_t i = 0; i < k; ++i) s.push_back((uint8_t)(m >> (8 * i)));
+  }
+  s.insert(s.end(), n, (uint8_t)'a');
+}
+void put_copy(B& s, uint32_t offset, uint32_t len) {  // the three-byte copy
+  s.push_back((uint8_t)(2 | ((len - 1) << 2)));
+  s.push_back((uint8_t)offset);
+  s.push_back((uint8_t)(offset >> 8));
+}
+B stream_of(uint32_t declared, const U& lits) {
+  B s = varint(declared);
+  for (uint32_t n : lits) put_lit(s, n);
+  return s;
+}
+
+struct IndexResult {
+  sm_status st;
+  U first, pos;  // pos: max_fragments entries and `guard` more behind them
+  B built;
+  std::vector<int32_t> status;
+};
+constexpr uint32_t kGuard = 0xdeadbeefu;
+
+// One call over heap buffers of exactly the streams' size.  len_as: a length to pass instead of the
+// first stream's own (an error mark); caps empty: no cap array.
+IndexResult index_run(const std::vector<B>& streams, const U& caps, uint32_t max_fragments, uint32_t guard = 2,
+                      uint32_t len_as = 0) {
+  B in;
+  std::vector<uint64_t> off;
+  U len;
+  for (const B& s : streams) {
+    off.push_back(in.size());
+    len.push_back((uint32_t)s.size());
+    in.insert(in.end(), s.begin(), s.end());
+  }
+  if (len_as) len[0] = len_as;
+  const uint32_t n = (uint32_t)streams.size();
+  if (in.empty()) in.push_back(0);
+  auto d_in = exact(in);
+  auto d_off = exact(off);
+  auto d_len = exact(len);
+  auto d_cap = exact(caps);
+  IndexResult r;
+  auto first = exact(U(n + 1, kGuard));
+  auto pos = exact(U(max_fragments + guard, kGuard));
+  auto built = exact(B(n ? n : 1, 7));
+  auto status = exact(std::vector<int32_t>(n ? n : 1, -1));
+  r.st = smm_index_host(d_in.get(), d_off.get(), d_len.get(), n, max_fragments, caps.empty() ? nullptr : d_cap.get(),
+                        first.get(), pos.get(), built.get(), status.get());
+  r.first.assign(first.get(), first.get() + n + 1);
+  r.pos.assign(pos.get(), pos.get() + max_fragments + guard);
+  r.built.assign(built.get(), built.get() + n);
+  r.status.assign(status.get(), status.get() + n);
+  return r;
+}
+
+void index_cases() {
+  const uint32_t G = kGuard, K = 65536;
+  const std::vector<int32_t> ok1 = {SM_OK};
+  // one stream per call: {entries..., guards}
+  auto one = [&](const B& s, uint32_t m, const U& want_pos, uint8_t want_built, uint32_t cap = 0xffffffffu) {
+    const IndexResult r = index_run({s}, cap == 0xffffffffu ? U{} : U{cap}, m);
+    U want = want_pos;
+    const uint32_t cnt = (uint32_t)want_pos.size();
+    want.resize(m + 2, G);
+    EXPECT(r.st == SM_OK && r.status == ok1);
+    EXPECT(r.first == (U{0, cnt}));
+    EXPECT(r.pos == want);
+    EXPECT(r.built == B{want_built});
+  };
+  EXPECT(varint(K + 1).size() == 3);
+  // a 65,536-byte literal (tag, two length bytes) ends exactly on the multiple; D = 65,537
+  one(stream_of(K + 1, {K, 1}), 2, {3, 3 + 3 + K}, 1);
+  one(stream_of(K + 1, {K, 1}), 5, {3, 3 + 3 + K}, 1);  // (a looser bound: the rest is untouched)
+  // ... in short tags: 1,092 literals of 60 bytes, one of 16, then the last byte
+  {
+    U lits(1092, 60);
+    lits.push_back(16);
+    lits.push_back(1);
+    one(stream_of(K + 1, lits), 2, {3, 3 + 1092 * 61 + 17}, 1);
+    lits[1092] = 17;  // the short literal straddles the multiple
+    lits.push_back(3);
+    one(stream_of(K + 5, lits), 2, {0, 0}, 0);
+  }
+  {  // copies up to the multiple (offset 1, length 64), one byte longer: crosses
+    B s = varint(K + 5);
+    put_lit(s, 64);
+    for (uint32_t i = 0; i < 1022; ++i) put_copy(s, 1, 64);
+    B t = s;
+    put_copy(s, 1, 64);
+    put_lit(s, 5);
+    one(s, 2, {3, 3 + 66 + 3 * 1023}, 1);
+    put_copy(t, 1, 60);
+    put_copy(t, 1, 4);
+    put_lit(t, 5);
+    one(t, 2, {3, 3 + 66 + 3 * 1024}, 1);
+    t = varint(K + 5);
+    put_lit(t, 64);
+    for (uint32_t i = 0; i < 1022; ++i) put_copy(t, 1, 64);
+    put_copy(t, 1, 63);
+    put_copy(t, 1, 4);
+    put_lit(t, 2);
+    one(t, 2, {0, 0}, 0);
+  }
+  one(stream_of(70010, {70000, 10}), 2, {0, 0}, 0);               // a 70,000-byte literal crosses
+  one(stream_of(2 * K + 5, {K, K, 5}), 3, {3, 3 + 3 + K, 3 + 2 * (3 + K)}, 1);  // lands exactly, then more
+  one(stream_of(140010, {140000, 10}), 3, {0, 0, 0}, 0);          // a literal crosses two multiples
+  {
+    B s = stream_of(2 * K + 5, {K, K, 5});
+    s.resize(3 + 3 + K + 100);  // cut before the last multiple
+    one(s, 3, {0, 0, 0}, 0);
+    s = stream_of(K + 1, {K});  // the multiple is reached exactly at x == n
+    one(s, 2, {0, 0}, 0);
+    s.push_back(0);             // one stray byte there: a tag starts on it
+    one(s, 2, {3, 3 + 3 + K}, 1);
+    s = varint(K + 1);          // nothing behind the header
+    one(s, 2, {0, 0}, 0);
+  }
+  one(stream_of(K + 1, {K, 1}), 2, {}, 0, K);          // D > cap: no entries
+  one(stream_of(K + 1, {K, 1}), 2, {3, 3 + 3 + K}, 1, K + 1);
+  one(B{0x85, 0x80}, 2, {}, 0);                         // a varint that does not end
+  one(B{0xff, 0xff, 0xff, 0xff, 0x10, 0, 0}, 2, {}, 0);
+  one(B{}, 2, {}, 0);                                   // n = 0
+  one(stream_of(0, {}), 2, {}, 0);                      // D = 0
+  one(stream_of(1, {1}), 2, {1}, 0);                    // D = 1: the entry is hv, not built
+  one(stream_of(K, {K}), 2, {3}, 0);                    // D = 65,536
+  {  // n an error mark: nothing is read
+    const IndexResult r = index_run({B{0x85, 0x80, 0x0c}}, {}, 2, 2, 0xfff00000u);
+    EXPECT(r.st == SM_OK && r.first == (U{0, 0}) && r.built == B{0} && r.pos == (U{G, G, G, G}) && r.status == ok1);
+  }
+  {  // a batch: the scan, a failed stream's zeros between its neighbours, the guards behind
+    const std::vector<B> v = {stream_of(1, {1}), stream_of(K + 1, {K, 1}), B{}, stream_of(70010, {70000, 10}),
+                              stream_of(2 * K + 5, {K, K, 5})};
+    IndexResult r = index_run(v, {}, 8, 3);
+    EXPECT(r.st == SM_OK && r.first == (U{0, 1, 3, 3, 5, 8}) && r.built == (B{0, 1, 0, 0, 1}));
+    EXPECT(r.pos == (U{1, 3, 3 + 3 + K, 0, 0, 3, 3 + 3 + K, 3 + 2 * (3 + K), G, G, G}));
+    EXPECT(r.status == std::vector<int32_t>(5, SM_OK));
+    r = index_run(v, {}, 7, 3);  // one entry too many
+    EXPECT(r.st == SM_OK && r.first == U(6, 0) && r.built == B(5, 0) && r.pos == U(10, G));
+    EXPECT(r.status == std::vector<int32_t>(5, SM_ERR_ARGUMENT));
+  }
+  {
+    uint32_t first = 9;
+    EXPECT(smm_index_host(nullptr, nullptr, nullptr, 0, 0, nullptr, &first, nullptr, nullptr, nullptr) == SM_OK && first == 0);
+    EXPECT(smm_index_host(nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr) == SM_ERR_ARGUMENT);
+  }
+}
 
 }  // namespace
 
@@ -189,6 +347,7 @@ int main() {
     EXPECT(smm_index_check(d_in.get(), &off, &len, 1, 3, &cap, f, p, &idx) == SM_OK && idx == 0);
     EXPECT(smm_index_check(d_in.get(), &off, &len, 1, 3, &cap, f, nullptr, &idx) == SM_ERR_ARGUMENT);
   }
+  index_cases();
   if (failures) {
     fprintf(stderr, "smm_host_check: %d failure(s)\n", failures);
     return 1;

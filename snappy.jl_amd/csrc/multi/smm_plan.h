@@ -1,8 +1,11 @@
 // smm_plan.h -- what the device plans of the multi-stream library (smm_kernels.hip) and its host
 // side (smm_host.cpp, smm_api.hip) share: the fragment arithmetic, the index rules of
-// smm_uncompress_device, the scratch layout, and the launchers' interfaces.  The rules are plain
-// functions over pointers, compiled for the host and the device alike, so the host checker
-// (smm_index_check, run under sanitizers by smm_host_check.cpp) tests the code the kernels run.
+// smm_uncompress_device, the rule that builds an index (smm_index_device), the scratch layout, and
+// the launchers' interfaces.  The rules are plain functions over pointers, compiled for the host and
+// the device alike, so the host checker (smm_index_check, run under sanitizers by
+// smm_host_check.cpp) tests the code the kernels run.  The index walk has two forms, the scalar
+// loop here (smm_index_host) and one wave's window walk (smm_index.hip): both size a tag by
+// sm_format.h's decode_tag rule, and the tests hold them against each other.
 // Not part of the public ABI.
 #pragma once
 #include <stddef.h>
@@ -10,6 +13,7 @@
 
 #include "../../../include/snappy_mi355x_multi.h"
 #include "../common/smc_layout.h"
+#include "../sm_format.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -25,6 +29,9 @@ constexpr uint32_t kNoStream = 0xffffffffu;   // a fragment slot no stream owns
 constexpr uint64_t kSlotPitch = smc::kMultiSlotPitch;  // a fragment's slot
 constexpr uint32_t kDummy = 64;               // a long stream's slot in the short-stream call: "00", with the
                                               // room an empty input's slot has (sm_max_compressed_length(0) = 32)
+
+constexpr uint32_t kIndexStage = 4096;        // bytes of a stream the index walk stages into LDS per piece
+                                              // (smm_index.hip; a prefetched second piece lies beside it)
 
 SMC_HD inline uint32_t fragment_count(uint64_t len) { return (uint32_t)((len + kBlock - 1) / kBlock); }
 using smc::varint_len;
@@ -68,6 +75,44 @@ SMC_HD inline bool fragment_range(const uint32_t* pos, uint32_t f, uint32_t coun
 // what fragment f of `count` must decode to
 SMC_HD inline uint32_t fragment_length(uint32_t D, uint32_t f, uint32_t count) {
   return f + 1 < count ? kBlock : D - kBlock * (count - 1);
+}
+
+// ---- building an index (include/snappy_mi355x_multi.h, smm_index_device) ----------------------
+// A stream's entries: D, the varint's bytes and fragment_count(D) when the length is no error mark,
+// the header parses and D fits the room; else all zero.
+struct IndexCount {
+  uint32_t D, hv, count;
+};
+SMC_HD inline IndexCount index_count(const uint8_t* p, uint32_t n, uint32_t cap) {
+  uint32_t D, hv;
+  if (n >= SM_OUT_LEN_ERROR) return {0, 0, 0};
+  if (smc::parse_varint32([&](uint32_t i) { return (uint32_t)p[i]; }, n, D, hv) != 0 || D > cap) return {0, 0, 0};
+  return {D, hv, fragment_count(D)};
+}
+
+// The positions of a stream that declares more than 64 KiB: the tag sizes from hv on, no copy made
+// and no offset or length checked.  A tag must start at every output multiple of 65536 below D;
+// pos[f] is where.  Bytes at or past n read as zero (the decoder's zero-padded lookahead), and
+// positions and outputs are 64-bit, so a literal length that wraps ends the walk at x >= n.  False,
+// with all `count` entries zero, when the stream ends first or a tag crosses such a multiple.
+inline bool index_walk(const uint8_t* p, uint32_t n, uint32_t hv, uint32_t count, uint32_t* pos) {
+  uint64_t x = hv, o = 0;
+  uint32_t f = 0;
+  while (x < n) {
+    const uint64_t at = (uint64_t)kBlock * f;
+    if (o > at) break;
+    if (o == at) {
+      pos[f++] = (uint32_t)x;
+      if (f == count) return true;
+    }
+    uint32_t tr = 0;
+    for (uint32_t k = 0; k < 4; ++k) tr |= (x + 1 + k < n ? (uint32_t)p[x + 1 + k] : 0u) << (8 * k);
+    const sm::Tag t = sm::decode_tag(p[x], tr);
+    x += t.size();
+    o += t.out_bytes();
+  }
+  for (f = 0; f < count; ++f) pos[f] = 0;
+  return false;
 }
 
 // ---- scratch (smc::Carve: a null base measures) ------------------------------------------------
@@ -134,12 +179,26 @@ inline DecodeScratch carve_decode(uint8_t* base, size_t n, size_t m) {
   s.end = c.p;
   return s;
 }
+struct IndexScratch {
+  uint32_t *D, *hv, *stop;  // per stream: the declared length (0: no entries) and the varint's bytes; the overflow word
+  uintptr_t end;
+};
+inline IndexScratch carve_index(uint8_t* base, size_t n) {
+  Carve c{reinterpret_cast<uintptr_t>(base)};
+  IndexScratch s;
+  s.D = c.take<uint32_t>(n);
+  s.hv = c.take<uint32_t>(n);
+  s.stop = c.take<uint32_t>(1);
+  s.end = c.p;
+  return s;
+}
 inline size_t compress_meta_bytes(size_t n, size_t m) { return (size_t)carve_compress(nullptr, n, m).end; }
 inline size_t decode_meta_bytes(size_t n, size_t m) { return (size_t)carve_decode(nullptr, n, m).end; }
+inline size_t index_scratch_bytes(size_t n) { return (size_t)carve_index(nullptr, n).end; }
 constexpr size_t kHeaderBytes = 256;
 inline size_t scratch_bytes(size_t n, size_t m) {
-  const size_t c = compress_meta_bytes(n, m) + m * kSlotPitch, d = decode_meta_bytes(n, m);
-  return kHeaderBytes + (c > d ? c : d);
+  const size_t c = compress_meta_bytes(n, m) + m * kSlotPitch, d = decode_meta_bytes(n, m), i = index_scratch_bytes(n);
+  return kHeaderBytes + (c > d ? (c > i ? c : i) : (d > i ? d : i));
 }
 
 #if defined(__HIPCC__)
@@ -184,6 +243,21 @@ hipError_t launch_decode_plan(const DecodePlan& p, hipStream_t st);
 hipError_t launch_reduce(const DecodePlan& p, hipStream_t st);
 // behind the fallback: the indexed streams' results over its own
 hipError_t launch_merge(const DecodePlan& p, hipStream_t st);
+
+struct IndexPlan {
+  const uint8_t* in;
+  const uint64_t* in_off;
+  const uint32_t* in_len;
+  uint32_t n, m;
+  const uint32_t* out_cap;  // NULL: no cap
+  uint32_t* frag_first;
+  uint32_t* frag_pos;
+  uint8_t* built;
+  int32_t* status;
+  IndexScratch s;
+};
+// smm_index.hip: the counts' scan with the short streams' entries, then a walk per long stream
+hipError_t launch_index(const IndexPlan& p, hipStream_t st);
 #endif
 
 }  // namespace smm

@@ -3,9 +3,12 @@ libsnappy_mi355x_multi.so, the companion of libsnappy_mi355x.so.
 
     compress_streams(list_of_bytes)         -> list of streams (and the fragment index when asked)
     uncompress_streams(streams, index=...)  -> (list of bytes-or-None, status array)
+    index_streams(streams)                  -> (frag_first, frag_pos, built): the index of streams
+                                               that came without one, built on the GPU
 
 and, on torch tensors resident in HBM: compress_streams_device, uncompress_streams_device (no host
-synchronisation), last_indexed.
+synchronisation), index_streams_device, last_indexed.  index_streams_host runs the same rule on the
+CPU.
 
 A stream of at most 64 KiB is what compress_batch gives, a longer one what compress gives; the
 index (frag_first, frag_pos) names every 64 KiB fragment's offset in its stream, and with it the
@@ -26,12 +29,13 @@ from . import HERE, MODES, SnappyError, _mode, _ptr, _stream, pack_blocks
 LIB_PATH = os.path.join(HERE, "libsnappy_mi355x_multi.so")
 BLOCK = 65536
 MAX_INPUT = 0x7FFFFFFF
+INDEX_STAGE = 4096  # kIndexStage (csrc/multi/smm_plan.h): the bytes the index walk stages per piece
 
 # exported symbols of include/snappy_mi355x_multi.h (checked by tests/test_multi_host.py)
 MULTI_ABI_SYMBOLS = (
     "smm_ctx_create", "smm_ctx_destroy", "smm_version", "smm_status_message", "smm_fragment_count", "smm_scratch_bytes",
     "smm_index_check", "smm_compress_device", "smm_uncompress_device", "smm_ctx_last_indexed", "smm_compress",
-    "smm_uncompress",
+    "smm_uncompress", "smm_index_host", "smm_index_device", "smm_index",
 )
 
 _lib = None
@@ -75,6 +79,12 @@ def lib():
         L.smm_compress.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, ctypes.c_int]
         L.smm_uncompress.restype = i32
         L.smm_uncompress.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+        L.smm_index_host.restype = i32
+        L.smm_index_host.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp]
+        L.smm_index_device.restype = i32
+        L.smm_index_device.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]
+        L.smm_index.restype = i32
+        L.smm_index.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -198,13 +208,92 @@ def _capacities(streams, capacities):
     return np.array(capacities, dtype=np.uint32)
 
 
+def _index_call(streams, capacities, max_fragments, call):
+    """The host arrays of an index call, and call(in, in_off, in_len, n, m, cap, first, pos, built,
+    status): (frag_first, frag_pos[:frag_first[-1]], built)."""
+    n = len(streams)
+    buf, in_off, in_len = pack_blocks(streams)
+    cap = None if capacities is None else np.array(capacities, dtype=np.uint32)
+    if max_fragments is None:
+        max_fragments = index_bound(streams, capacities)
+    first = np.zeros(n + 1, np.uint32)
+    pos = np.zeros(max(int(max_fragments), 1), np.uint32)
+    built = np.zeros(max(n, 1), np.uint8)
+    status = np.zeros(max(n, 1), np.int32)
+    keep = np.zeros(1, np.uint8)
+    st = call(_addr(buf) or keep.ctypes.data, _addr(in_off), _addr(in_len), n, int(max_fragments),
+              _addr(cap) if cap is not None else None, first.ctypes.data, pos.ctypes.data, built.ctypes.data,
+              status.ctypes.data)
+    if st:
+        raise SnappyError(st)
+    if status[:n].any():
+        raise SnappyError(int(status[np.nonzero(status)[0][0]]))
+    return first, pos[:int(first[-1])], built[:n]
+
+
+def index_bound(streams, capacities=None):
+    """A max_fragments that holds the index of these streams: every stream counted by the length
+    its header declares (as far as its capacity allows)."""
+    cap = _capacities(streams, None)
+    if capacities is not None:
+        cap = np.where(cap <= np.array(capacities, dtype=np.uint32), cap, 0)
+    return int(((cap.astype(np.uint64) + BLOCK - 1) // BLOCK).sum())
+
+
+def index_streams(streams, capacities=None, device=0, max_fragments=None):
+    """Build on the GPU the index of raw streams that came without one (a CPU compressor wrote them):
+    (frag_first, frag_pos, built), what uncompress_streams takes as index=(frag_first, frag_pos).
+    built[s] = 1 for a stream of more than 64 KiB in which a tag starts at every 64 KiB of output --
+    every block compressor's stream; the others decode in stream order.  capacities: the output room
+    per stream (a stream that declares more gets no entries); None: no cap.  Raises SnappyError(33)
+    when max_fragments (default: what the headers declare) is too small."""
+    ctx = context(device)
+    return _index_call(streams, capacities, max_fragments, lambda *a: lib().smm_index(ctx, *a))
+
+
+def index_streams_host(streams, capacities=None, max_fragments=None):
+    """index_streams on the CPU (smm_index_host): the same rule as a scalar loop, no device."""
+    return _index_call(streams, capacities, max_fragments, lib().smm_index_host)
+
+
+def _uncompress_building(buf, in_off, in_len, cap, out_off, out_len, status, out, device):
+    """uncompress_streams(index="build"): the streams go up once, and the two device calls run back
+    to back on one stream with the index staying in device memory."""
+    import torch
+    dev = torch.device("cuda", device)
+    n = in_len.size
+    m = int(((cap.astype(np.uint64) + BLOCK - 1) // BLOCK).sum())
+
+    def up(a, dtype):
+        return torch.from_numpy(np.array(a).view(dtype)).to(dev)  # (a copy: the packed bytes are read-only)
+
+    with torch.cuda.device(dev):
+        d_in = up(buf, np.uint8) if buf.size else torch.zeros(1, dtype=torch.uint8, device=dev)
+        d_in_off, d_in_len, d_cap = up(in_off, np.int64), up(in_len, np.int32), up(cap, np.int32)
+        d_out_off = up(out_off, np.int64)
+        d_out = torch.empty(out.size, dtype=torch.uint8, device=dev)
+        d_out_len = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_status = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_first = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+        d_pos = torch.zeros(max(m, 1), dtype=torch.int32, device=dev)
+        d_built = torch.zeros(n, dtype=torch.uint8, device=dev)
+        index_streams_device(d_in, d_in_off, d_in_len, m, d_first, d_pos, d_built, d_status, d_out_cap=d_cap)
+        uncompress_streams_device(d_in, d_in_off, d_in_len, m, d_out, d_out_off, d_cap, d_out_len, d_status, d_first, d_pos)
+        out_len[:] = d_out_len.cpu().numpy().view(np.uint32)
+        status[:] = d_status.cpu().numpy()
+        out[:] = d_out.cpu().numpy()
+
+
 def uncompress_streams(streams, index=None, capacities=None, device=0):
     """Decode independent raw Snappy streams of any length in one call on the GPU; returns (list
     of bytes-or-None, status array).  index: the (frag_first, frag_pos) compress_streams returned
-    for exactly these streams -- a hint that lets every fragment decode in parallel."""
+    for exactly these streams -- a hint that lets every fragment decode in parallel -- or "build":
+    the index is built on the device first (index_streams) and used from there."""
     n = len(streams)
     if n == 0:
         return [], np.zeros(0, np.int32)
+    if isinstance(index, str) and index != "build":
+        raise ValueError("index must be None, (frag_first, frag_pos) or 'build'")
     buf, in_off, in_len = pack_blocks(streams)
     cap = _capacities(streams, capacities)
     out_off = np.zeros(n, dtype=np.uint64)
@@ -214,6 +303,10 @@ def uncompress_streams(streams, index=None, capacities=None, device=0):
     out_len = np.zeros(n, np.uint32)
     status = np.zeros(n, np.int32)
     first = pos = None
+    if isinstance(index, str):
+        _uncompress_building(buf, in_off, in_len, cap, out_off, out_len, status, out, device)
+        res = [out[int(o): int(o) + int(l)].tobytes() if s == 0 else None for o, l, s in zip(out_off, out_len, status)]
+        return res, status
     if index is not None:
         first = np.ascontiguousarray(index[0], dtype=np.uint32)
         pos = np.ascontiguousarray(index[1], dtype=np.uint32)
@@ -264,6 +357,18 @@ def uncompress_streams_device(d_in, d_in_off, d_in_len, max_fragments, d_out, d_
         raise SnappyError(st)
 
 
+def index_streams_device(d_in, d_in_off, d_in_len, max_fragments, d_frag_first, d_frag_pos, d_built, d_status,
+                         d_out_cap=None, stream=None, device=None):
+    """smm_index_device (tensor types as in compress_streams_device; d_built uint8, nstreams
+    entries; d_frag_pos max_fragments entries; d_out_cap None: no cap).  Nothing is synchronised."""
+    dev = d_in.device.index if device is None else device
+    st = lib().smm_index_device(context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), d_in_len.numel(),
+                                int(max_fragments), _opt(d_out_cap), _ptr(d_frag_first), _ptr(d_frag_pos), _ptr(d_built),
+                                _ptr(d_status), ctypes.c_void_p(_stream(stream, dev)))
+    if st:
+        raise SnappyError(st)
+
+
 def last_indexed(device=0):
     """Diagnostic: how many streams the device's last uncompress call decoded by fragments (waits
     for the device); -1 before the first call."""
@@ -271,4 +376,5 @@ def last_indexed(device=0):
 
 
 __all__ = ["MULTI_ABI_SYMBOLS", "MODES", "compress_streams", "uncompress_streams", "compress_streams_device",
-           "uncompress_streams_device", "fragment_count", "scratch_bytes", "frag_first_of", "index_check", "last_indexed"]
+           "uncompress_streams_device", "index_streams", "index_streams_host", "index_streams_device",
+           "index_bound", "INDEX_STAGE", "fragment_count", "scratch_bytes", "frag_first_of", "index_check", "last_indexed"]
