@@ -27,6 +27,9 @@ import threading
 
 import numpy as np
 
+from ._binding import (RAW, check, collect, context_cache, device_caller, exclusive_scan, load, pack_blocks,
+                       slot_offsets)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 # SNAPPY_MI355X_LIB: alternate build of the same library (diagnostic/ablation builds only)
 LIB_PATH = os.environ.get("SNAPPY_MI355X_LIB") or os.path.join(HERE, "libsnappy_mi355x.so")
@@ -38,20 +41,7 @@ SM_ERR_DEVICE = 32
 SM_OUT_LEN_ERROR = 0xFFF00000  # d_out_len[b] >= this: block b failed (include/snappy_mi355x.h)
 MODES = {"reference": 0, "fast": 1, "dense": 2}
 
-# exported symbols of include/snappy_mi355x.h (checked by tests/test_abi.py)
-ABI_SYMBOLS = (
-    "sm_status_message", "sm_max_compressed_length", "sm_uncompressed_length", "sm_parse32",
-    "sm_encode32", "sm_ctx_create", "sm_ctx_destroy", "sm_ctx_stream", "sm_compress", "sm_uncompress",
-    "sm_compress_batch_device", "sm_uncompress_batch_device", "sm_compress_batch",
-    "sm_uncompress_batch", "sm_version", "sm_compress_fragments_device", "sm_batch_parts_plan",
-    "sm_ctx_last_batch_parts", "sm_ctx_last_path", "sm_ctx_set_small_decode",
-    "sm_ctx_set_split_compress", "sm_ctx_last_compress_split",
-    "sm_find_match_length", "sm_validate_batch_device", "sm_uncompressed_length_batch_device",
-    "sm_validate_compressed_buffer", "sm_compress_batch_sharded", "sm_uncompress_batch_sharded",
-    "sm_uncompress_fragments_device", "sm_place_fragments_device", "sm_snappy_compress", "sm_snappy_uncompress",
-    "sm_snappy_max_compressed_length", "sm_snappy_uncompressed_length", "sm_snappy_validate_compressed_buffer",
-    "sm_snappy_set_mode",
-)
+ABI_SYMBOLS = tuple(RAW)  # exported symbols of include/snappy_mi355x.h (checked by tests/test_abi.py)
 
 
 class SnappyError(Exception):
@@ -63,8 +53,6 @@ class SnappyError(Exception):
 
 
 _lib = None
-_ctx = {}
-_ctx_lock = threading.Lock()
 
 
 def library_path():
@@ -75,92 +63,14 @@ def lib():
     """Load libsnappy_mi355x.so (raises OSError if it was not built)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise OSError("libsnappy_mi355x.so not built (run __graft_entry__.build())")
-        _lib = load_library(LIB_PATH)
+        _lib = load(LIB_PATH, RAW, "libsnappy_mi355x.so not built (run __graft_entry__.build())")
     return _lib
 
 
 def load_library(path):
     """A build of the C ABI at `path` with its prototypes set (lib() uses the shipped one; the
     GPU tests also load diagnostic variants built by the Makefile, e.g. the error-mark build)."""
-    L = ctypes.CDLL(path)
-    vp, sz, i32, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_uint32
-    L.sm_status_message.restype = ctypes.c_char_p
-    L.sm_status_message.argtypes = [i32]
-    L.sm_max_compressed_length.restype = sz
-    L.sm_max_compressed_length.argtypes = [sz]
-    L.sm_uncompressed_length.restype = i32
-    L.sm_uncompressed_length.argtypes = [vp, sz, ctypes.POINTER(sz)]
-    L.sm_parse32.restype = i32
-    L.sm_parse32.argtypes = [vp, sz, sz, ctypes.POINTER(u32), ctypes.POINTER(sz)]
-    L.sm_encode32.restype = sz
-    L.sm_encode32.argtypes = [vp, u32]
-    L.sm_ctx_create.restype = vp
-    L.sm_ctx_create.argtypes = [ctypes.c_int]
-    L.sm_ctx_destroy.restype = None
-    L.sm_ctx_destroy.argtypes = [vp]
-    L.sm_ctx_stream.restype = vp
-    L.sm_ctx_stream.argtypes = [vp]
-    L.sm_compress.restype = i32
-    L.sm_compress.argtypes = [vp, vp, sz, vp, ctypes.POINTER(sz), ctypes.c_int]
-    L.sm_uncompress.restype = i32
-    L.sm_uncompress.argtypes = [vp, vp, sz, vp, ctypes.POINTER(sz)]
-    L.sm_compress_batch_device.restype = i32
-    L.sm_compress_batch_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, ctypes.c_int, vp]
-    L.sm_uncompress_batch_device.restype = i32
-    L.sm_uncompress_batch_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
-    L.sm_compress_batch.restype = i32
-    L.sm_compress_batch.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, ctypes.c_int]
-    L.sm_uncompress_batch.restype = i32
-    L.sm_uncompress_batch.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
-    L.sm_compress_batch_sharded.restype = i32
-    L.sm_compress_batch_sharded.argtypes = [vp, ctypes.c_int, vp, vp, vp, u32, vp, vp, vp, ctypes.c_int]
-    L.sm_uncompress_batch_sharded.restype = i32
-    L.sm_uncompress_batch_sharded.argtypes = [vp, ctypes.c_int, vp, vp, vp, u32, vp, vp, vp, vp, vp]
-    L.sm_find_match_length.restype = i32
-    L.sm_find_match_length.argtypes = [vp, sz, sz, sz, sz, ctypes.POINTER(sz)]
-    L.sm_ctx_last_path.restype = ctypes.c_int
-    L.sm_ctx_last_path.argtypes = [vp]
-    L.sm_ctx_set_small_decode.restype = ctypes.c_int
-    L.sm_ctx_set_small_decode.argtypes = [vp, ctypes.c_int]
-    L.sm_ctx_set_split_compress.restype = ctypes.c_int
-    L.sm_ctx_set_split_compress.argtypes = [vp, ctypes.c_int]
-    L.sm_ctx_last_compress_split.restype = ctypes.c_int
-    L.sm_ctx_last_compress_split.argtypes = [vp]
-    L.sm_version.restype = ctypes.c_char_p
-    L.sm_version.argtypes = []
-    L.sm_compress_fragments_device.restype = i32
-    L.sm_compress_fragments_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, ctypes.c_uint64, ctypes.c_int, vp]
-    L.sm_ctx_last_batch_parts.restype = ctypes.c_int
-    L.sm_ctx_last_batch_parts.argtypes = [vp]
-    L.sm_batch_parts_plan.restype = None
-    L.sm_batch_parts_plan.argtypes = [u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
-    L.sm_validate_batch_device.restype = i32
-    L.sm_validate_batch_device.argtypes = [vp, vp, vp, vp, u32, vp, vp]
-    L.sm_uncompressed_length_batch_device.restype = i32
-    L.sm_uncompressed_length_batch_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp]
-    L.sm_validate_compressed_buffer.restype = i32
-    L.sm_validate_compressed_buffer.argtypes = [vp, vp, sz]
-    L.sm_place_fragments_device.restype = i32
-    L.sm_place_fragments_device.argtypes = [vp, vp, vp, vp, u32, vp, ctypes.c_uint64, ctypes.c_int, vp,
-                                            ctypes.c_uint64, vp, vp, vp]
-    L.sm_uncompress_fragments_device.restype = i32
-    L.sm_uncompress_fragments_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp]
-    # snappy-c.h shape (test/libsnappy.jl:5-30): (char*, size_t, char*, size_t*) -> int
-    L.sm_snappy_compress.restype = i32
-    L.sm_snappy_compress.argtypes = [vp, sz, vp, ctypes.POINTER(sz)]
-    L.sm_snappy_uncompress.restype = i32
-    L.sm_snappy_uncompress.argtypes = [vp, sz, vp, ctypes.POINTER(sz)]
-    L.sm_snappy_max_compressed_length.restype = sz
-    L.sm_snappy_max_compressed_length.argtypes = [sz]
-    L.sm_snappy_uncompressed_length.restype = i32
-    L.sm_snappy_uncompressed_length.argtypes = [vp, sz, ctypes.POINTER(sz)]
-    L.sm_snappy_validate_compressed_buffer.restype = i32
-    L.sm_snappy_validate_compressed_buffer.argtypes = [vp, sz]
-    L.sm_snappy_set_mode.restype = i32
-    L.sm_snappy_set_mode.argtypes = [ctypes.c_int]
-    return L
+    return load(path, RAW)
 
 
 def status_message(code):
@@ -176,17 +86,9 @@ def _bytes(x):
     return np.frombuffer(bytes(x), dtype=np.uint8)
 
 
-def context(device=0):
-    """Per-device sm_ctx (one HIP stream + scratch; the library serialises host-buffer calls on
-    it).  Raises if no device is usable."""
-    with _ctx_lock:
-        c = _ctx.get(device)
-        if c is None:
-            c = lib().sm_ctx_create(device)
-            if not c:
-                raise SnappyError(32, "no usable HIP device %d for snappy_mi355x" % device)
-            _ctx[device] = c
-    return c
+# context(device=0): the per-device sm_ctx (one HIP stream + scratch; the library serialises
+# host-buffer calls on it).  Raises if no device is usable.
+_ctx, _ctx_lock, context = context_cache(lib, "sm_ctx_create", SnappyError, "no usable HIP device %d for snappy_mi355x")
 
 
 def contexts(devices):
@@ -197,14 +99,7 @@ def contexts(devices):
     for d in devices:
         k = seen.get(d, 0)
         seen[d] = k + 1
-        key = ("shard", d, k)
-        c = _ctx.get(key)
-        if c is None:
-            c = lib().sm_ctx_create(d)
-            if not c:
-                raise SnappyError(32, "no usable HIP device %d for snappy_mi355x" % d)
-            _ctx[key] = c
-        out.append(c)
+        out.append(context(("shard", d, k)))
     return (ctypes.c_void_p * len(out))(*out)
 
 
@@ -224,9 +119,8 @@ def parse32(buf, offset=0):
     a = _bytes(buf)
     v = ctypes.c_uint32(0)
     nx = ctypes.c_size_t(0)
-    st = lib().sm_parse32(a.ctypes.data if a.size else None, a.size, int(offset), ctypes.byref(v), ctypes.byref(nx))
-    if st:
-        raise SnappyError(st)
+    check(lib().sm_parse32(a.ctypes.data if a.size else None, a.size, int(offset), ctypes.byref(v), ctypes.byref(nx)),
+          SnappyError)
     return v.value, nx.value
 
 
@@ -287,10 +181,8 @@ def find_match_length(buf, i1, i2, limit):
     reference would read past buf."""
     src = _bytes(buf)
     res = ctypes.c_size_t(0)
-    st = lib().sm_find_match_length(src.ctypes.data if src.size else None, src.size, i1, i2, limit,
-                                    ctypes.byref(res))
-    if st:
-        raise SnappyError(st)
+    check(lib().sm_find_match_length(src.ctypes.data if src.size else None, src.size, i1, i2, limit, ctypes.byref(res)),
+          SnappyError)
     return res.value
 
 
@@ -304,17 +196,13 @@ def last_uncompress_path(device=0):
 
 def set_small_decode(enable, device=0):
     """Diagnostic: path 4 (small streams on the device) on or off for uncompress() on this device."""
-    st = lib().sm_ctx_set_small_decode(context(device), 1 if enable else 0)
-    if st:
-        raise SnappyError(st)
+    check(lib().sm_ctx_set_small_decode(context(device), 1 if enable else 0), SnappyError)
 
 
 def set_split_compress(enable, device=0):
     """Diagnostic: compress() of small fast-mode inputs parses each 64 KiB fragment in parts on
     their own workgroups (on by default; the same bytes either way)."""
-    st = lib().sm_ctx_set_split_compress(context(device), 1 if enable else 0)
-    if st:
-        raise SnappyError(st)
+    check(lib().sm_ctx_set_split_compress(context(device), 1 if enable else 0), SnappyError)
 
 
 def last_compress_split(device=0):
@@ -348,23 +236,17 @@ def uncompress(data, device=0):
 
 # ---- batched host API ---------------------------------------------------------------
 
-def pack_blocks(blocks):
-    """list of byte strings -> (packed u8 array, u64 offsets, u32 lengths)."""
-    lens = np.array([len(b) for b in blocks], dtype=np.uint32)
-    offs = np.zeros(len(blocks), dtype=np.uint64)
-    if len(blocks) > 1:
-        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
-    buf = np.frombuffer(b"".join(bytes(b) for b in blocks), dtype=np.uint8) if blocks else np.zeros(0, np.uint8)
-    return np.ascontiguousarray(buf), offs, lens
-
-
-def slot_offsets(in_len):
-    """Fixed output slots of max_compressed_length(len) bytes (16-B aligned)."""
-    caps = (32 + in_len.astype(np.uint64) + in_len.astype(np.uint64) // 6 + 15) // 16 * 16
-    offs = np.zeros(in_len.size, dtype=np.uint64)
-    if in_len.size > 1:
-        offs[1:] = np.cumsum(caps[:-1], dtype=np.uint64)
-    return offs, caps
+def _capacities(streams, capacities):
+    """The output room per stream as uint32; None: what each stream's header declares (0 where it
+    does not parse)."""
+    if capacities is None:
+        capacities = []
+        for s in streams:
+            try:
+                capacities.append(parse32(s)[0])
+            except SnappyError:
+                capacities.append(0)
+    return np.array(capacities, dtype=np.uint32)
 
 
 def compress_batch(blocks, mode="fast", device=0, devices=None):
@@ -373,20 +255,19 @@ def compress_batch(blocks, mode="fast", device=0, devices=None):
     buf, in_off, in_len = pack_blocks(blocks)
     if np.any(in_len > BLOCK_SIZE):
         raise ValueError("batch blocks must be <= 65536 bytes")
-    out_off, caps = slot_offsets(in_len)
-    out = np.empty(int(out_off[-1] + caps[-1]) if len(blocks) else 1, dtype=np.uint8)
-    out_len = np.zeros(len(blocks), dtype=np.uint32)
     if not blocks:
         return []
+    out_off, caps = slot_offsets(in_len)
+    out = np.empty(int(out_off[-1] + caps[-1]), dtype=np.uint8)
+    out_len = np.zeros(len(blocks), dtype=np.uint32)
     args = (buf.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, len(blocks), out.ctypes.data,
             out_off.ctypes.data, out_len.ctypes.data, _mode(mode))
     if devices is None:
         st = lib().sm_compress_batch(context(device), *args)
     else:  # one shard of the blocks per device, concurrently (sm_compress_batch_sharded)
         st = lib().sm_compress_batch_sharded(contexts(devices), len(devices), *args)
-    if st:
-        raise SnappyError(st)
-    return [out[int(o): int(o) + int(l)].tobytes() for o, l in zip(out_off, out_len)]
+    check(st, SnappyError)
+    return collect(out, out_off, out_len)
 
 
 def uncompress_batch(streams, capacities=None, device=0, devices=None):
@@ -395,19 +276,9 @@ def uncompress_batch(streams, capacities=None, device=0, devices=None):
     if not streams:
         return [], np.zeros(0, np.int32)
     buf, in_off, in_len = pack_blocks(streams)
-    if capacities is None:
-        caps = []
-        for s in streams:
-            try:
-                caps.append(parse32(s)[0])
-            except SnappyError:
-                caps.append(0)
-        capacities = caps
-    cap = np.array(capacities, dtype=np.uint32)
-    out_off = np.zeros(len(streams), dtype=np.uint64)
-    if len(streams) > 1:
-        out_off[1:] = np.cumsum(cap[:-1].astype(np.uint64), dtype=np.uint64)
-    out = np.empty(max(int(cap.astype(np.uint64).sum()), 1), dtype=np.uint8)
+    cap = _capacities(streams, capacities)
+    out_off = exclusive_scan(cap, total=True)
+    out = np.empty(max(int(out_off[-1]), 1), dtype=np.uint8)
     out_len = np.zeros(len(streams), dtype=np.uint32)
     status = np.zeros(len(streams), dtype=np.int32)
     args = (buf.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, len(streams), out.ctypes.data,
@@ -416,56 +287,28 @@ def uncompress_batch(streams, capacities=None, device=0, devices=None):
         st = lib().sm_uncompress_batch(context(device), *args)
     else:
         st = lib().sm_uncompress_batch_sharded(contexts(devices), len(devices), *args)
-    if st:
-        raise SnappyError(st)
-    res = [out[int(o): int(o) + int(l)].tobytes() if s == 0 else None for o, l, s in zip(out_off, out_len, status)]
-    return res, status
+    check(st, SnappyError)
+    return collect(out, out_off, out_len, status), status
 
 
 # ---- batched device API (torch tensors resident in HBM) -----------------------------
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream(stream, dev):
-    import torch
-    if stream is None:
-        return torch.cuda.current_stream(dev).cuda_stream
-    return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+_device = device_caller(lib, context, SnappyError)
 
 
 def compress_batch_device(d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_len, mode="fast", stream=None,
                           device=None):
     """All arguments are torch CUDA tensors (uint8 / int64 / int32).  Asynchronous on `stream`
     (a torch.cuda.Stream or raw hipStream_t int; default: torch's current stream)."""
-    import torch
-    dev = d_in.device.index if device is None else device
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    elif hasattr(stream, "cuda_stream"):
-        stream = stream.cuda_stream
-    st = lib().sm_compress_batch_device(context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), d_in_len.numel(),
-                                        _ptr(d_out), _ptr(d_out_off), _ptr(d_out_len), _mode(mode),
-                                        ctypes.c_void_p(stream))
-    if st:
-        raise SnappyError(st)
+    _device("sm_compress_batch_device", d_in, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), d_out,
+            d_out_off, d_out_len, _mode(mode))
 
 
 def compress_fragments_device(d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_len, total_len, mode="fast",
                               stream=None, device=None):
     """Fragments of ONE stream of total_len bytes (no per-fragment header; Q2 table size)."""
-    import torch
-    dev = d_in.device.index if device is None else device
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    elif hasattr(stream, "cuda_stream"):
-        stream = stream.cuda_stream
-    st = lib().sm_compress_fragments_device(context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len),
-                                            d_in_len.numel(), _ptr(d_out), _ptr(d_out_off), _ptr(d_out_len),
-                                            int(total_len), _mode(mode), ctypes.c_void_p(stream))
-    if st:
-        raise SnappyError(st)
+    _device("sm_compress_fragments_device", d_in, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), d_out,
+            d_out_off, d_out_len, int(total_len), _mode(mode))
 
 
 def batch_parts_plan(nblk, grid):
@@ -484,17 +327,8 @@ def last_batch_parts(device=0):
 
 def uncompress_batch_device(d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status,
                             stream=None, device=None):
-    import torch
-    dev = d_in.device.index if device is None else device
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
-    elif hasattr(stream, "cuda_stream"):
-        stream = stream.cuda_stream
-    st = lib().sm_uncompress_batch_device(context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len),
-                                          d_in_len.numel(), _ptr(d_out), _ptr(d_out_off), _ptr(d_out_cap),
-                                          _ptr(d_out_len), _ptr(d_status), ctypes.c_void_p(stream))
-    if st:
-        raise SnappyError(st)
+    _device("sm_uncompress_batch_device", d_in, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), d_out,
+            d_out_off, d_out_cap, d_out_len, d_status)
 
 
 def place_fragments_device(d_src, d_src_off, d_len, d_dst_off, d_dst, total_len, write_header, d_local_off=None,
@@ -507,49 +341,31 @@ def place_fragments_device(d_src, d_src_off, d_len, d_dst_off, d_dst, total_len,
     SM_ERR_DEVICE on an error-mark length, a fragment past d_dst's end or, with write_header, a
     fragment that would start inside the header (d_dst_off[b] < len(varint(total_len))); such a
     fragment is not copied, the others and the header are."""
-    dev = d_dst.device.index if device is None else device
     nfrag = d_len.numel()
-    nul = ctypes.c_void_p(0)
-    st = lib().sm_place_fragments_device(context(dev), _ptr(d_src) if nfrag else nul, _ptr(d_src_off) if nfrag else nul,
-                                         _ptr(d_len) if nfrag else nul, nfrag, _ptr(d_dst_off) if nfrag else nul,
-                                         int(total_len), 1 if write_header else 0, _ptr(d_dst), d_dst.numel(),
-                                         _ptr(d_local_off) if d_local_off is not None else nul,
-                                         _ptr(d_status) if d_status is not None else nul,
-                                         ctypes.c_void_p(_stream(stream, dev)))
-    if st:
-        raise SnappyError(st)
+    if not nfrag:  # (tensors of no fragments go as null pointers)
+        d_src = d_src_off = d_len = d_dst_off = None
+    _device("sm_place_fragments_device", d_dst, device, stream, d_src, d_src_off, d_len, nfrag, d_dst_off,
+            int(total_len), 1 if write_header else 0, d_dst, d_dst.numel(), d_local_off, d_status)
 
 
 def uncompress_fragments_device(d_in, d_in_off, d_in_len, d_out, d_out_off, d_frag_len, d_out_len, d_status,
                                 stream=None, device=None):
     """Fragments of ONE stream (no varint headers; sm_compress_fragments_device's output):
     fragment b must decode to exactly d_frag_len[b] bytes at d_out + d_out_off[b]."""
-    dev = d_in.device.index if device is None else device
-    st = lib().sm_uncompress_fragments_device(context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len),
-                                              d_in_len.numel(), _ptr(d_out), _ptr(d_out_off), _ptr(d_frag_len),
-                                              _ptr(d_out_len), _ptr(d_status), ctypes.c_void_p(_stream(stream, dev)))
-    if st:
-        raise SnappyError(st)
+    _device("sm_uncompress_fragments_device", d_in, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), d_out,
+            d_out_off, d_frag_len, d_out_len, d_status)
 
 
 def validate_batch_device(d_in, d_in_off, d_in_len, d_status, stream=None, device=None):
     """d_status[b] = the status uncompress(block b) would return (no output written):
     batched snappy_validate_compressed_buffer."""
-    dev = d_in.device.index if device is None else device
-    st = lib().sm_validate_batch_device(context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), d_in_len.numel(),
-                                        _ptr(d_status), ctypes.c_void_p(_stream(stream, dev)))
-    if st:
-        raise SnappyError(st)
+    _device("sm_validate_batch_device", d_in, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), d_status)
 
 
 def uncompressed_length_batch_device(d_in, d_in_off, d_in_len, d_len, d_status, stream=None, device=None):
     """Batched length_uncompressed (Snappy.jl:90-92): the varint header of every block."""
-    dev = d_in.device.index if device is None else device
-    st = lib().sm_uncompressed_length_batch_device(context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len),
-                                                   d_in_len.numel(), _ptr(d_len), _ptr(d_status),
-                                                   ctypes.c_void_p(_stream(stream, dev)))
-    if st:
-        raise SnappyError(st)
+    _device("sm_uncompressed_length_batch_device", d_in, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(),
+            d_len, d_status)
 
 
 def validate(data, device=0):

@@ -25,11 +25,13 @@ fallback: every codec call needs both HIP libraries and a device.
 """
 import ctypes
 import os
-import threading
 
 import numpy as np
 
-from . import HERE, MODES, SnappyError, _in_arg, _mode, _out_buffer, _ptr, _stream
+from . import HERE, MODES, SnappyError, _in_arg, _mode, _out_buffer
+from ._binding import (FRAMING, FRAMING_RANGE, FRAMING_STREAMS, INDEX_KEYS, Chunks, Summary, check, collect,
+                       context_cache, device_caller, exclusive_scan, load)
+from ._binding import lay_out as _lay_out
 
 LIB_PATH = os.path.join(HERE, "libsnappy_mi355x_framing.so")
 
@@ -41,39 +43,18 @@ SMF_ERR_CHUNK_TOO_LARGE = 52
 SMF_ERR_CRC = 53
 IDENTIFIER = b"\xff\x06\x00\x00sNaPpY"
 
-# exported symbols of include/snappy_mi355x_framing.h (checked by tests/test_framing_host.py)
-FRAMING_ABI_SYMBOLS = (
-    "smf_status_message", "smf_version", "smf_max_framed_length", "smf_crc32c", "smf_crc32c_mask", "smf_index",
-    "smf_uncompressed_length", "smf_ctx_create", "smf_ctx_destroy", "smf_crc32c_batch_device", "smf_compress_device",
-    "smf_index_device", "smf_uncompressed_length_device", "smf_uncompress_chunks_device", "smf_uncompress_device",
-    "smf_compress", "smf_uncompress", "smf_validate",
-) + (  # the seek index and the ranged decode (checked by tests/test_framing_range_host.py)
-    "smf_chunk_offsets", "smf_range_chunk_count", "smf_range_plan", "smf_range_scratch_bytes",
-    "smf_chunk_offsets_device", "smf_compress_indexed_device", "smf_uncompress_ranges_device", "smf_uncompress_range",
-)
-RANGE_ABI_SYMBOLS = FRAMING_ABI_SYMBOLS[-8:]
-# a batch of streams per call (checked by tests/test_framing_streams_host.py)
-STREAMS_ABI_SYMBOLS = (
-    "smf_max_data_chunks", "smf_streams_plan", "smf_streams_scratch_bytes", "smf_uncompress_streams_device",
-    "smf_compress_streams_device", "smf_compress_streams", "smf_uncompress_streams",
-)
-FRAMING_ABI_SYMBOLS += STREAMS_ABI_SYMBOLS
+# exported symbols of include/snappy_mi355x_framing.h (checked by tests/test_framing_host.py), among
+# them the seek index and the ranged decode (tests/test_framing_range_host.py) and a batch of
+# streams per call (tests/test_framing_streams_host.py)
+FRAMING_ABI_SYMBOLS = tuple(FRAMING)
+RANGE_ABI_SYMBOLS = tuple(FRAMING_RANGE)
+STREAMS_ABI_SYMBOLS = tuple(FRAMING_STREAMS)
 
-
-class Chunks(ctypes.Structure):
-    """smf_chunks: five parallel arrays, one entry per data chunk."""
-    _fields_ = [("type", ctypes.c_void_p), ("pay_off", ctypes.c_void_p), ("pay_len", ctypes.c_void_p),
-                ("crc", ctypes.c_void_p), ("ulen", ctypes.c_void_p)]
-
-
-class Summary(ctypes.Structure):
-    """smf_summary."""
-    _fields_ = [("total_length", ctypes.c_uint64), ("nchunks", ctypes.c_uint32), ("status", ctypes.c_int32)]
-
+# the index arrays' element types: as the C ABI declares them, and as torch tensors hold the same bits
+_UNSIGNED = dict(zip(INDEX_KEYS, (np.uint8, np.uint64, np.uint32, np.uint32, np.uint32)))
+_SIGNED = dict(zip(INDEX_KEYS, (np.uint8, np.int64, np.int32, np.int32, np.int32)))
 
 _lib = None
-_ctx = {}
-_ctx_lock = threading.Lock()
 
 
 def library_path():
@@ -84,78 +65,7 @@ def lib():
     """Load libsnappy_mi355x_framing.so (raises OSError if it was not built)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise OSError("libsnappy_mi355x_framing.so not built (run __graft_entry__.build())")
-        L = ctypes.CDLL(LIB_PATH)
-        vp, sz, i32, u32, u64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64
-        pch, psum = ctypes.POINTER(Chunks), ctypes.POINTER(Summary)
-        L.smf_status_message.restype = ctypes.c_char_p
-        L.smf_status_message.argtypes = [i32]
-        L.smf_version.restype = ctypes.c_char_p
-        L.smf_version.argtypes = []
-        L.smf_max_framed_length.restype = sz
-        L.smf_max_framed_length.argtypes = [sz]
-        L.smf_crc32c.restype = u32
-        L.smf_crc32c.argtypes = [vp, sz]
-        L.smf_crc32c_mask.restype = u32
-        L.smf_crc32c_mask.argtypes = [u32]
-        L.smf_index.restype = i32
-        L.smf_index.argtypes = [vp, sz, pch, u32, psum]
-        L.smf_uncompressed_length.restype = i32
-        L.smf_uncompressed_length.argtypes = [vp, sz, ctypes.POINTER(sz)]
-        L.smf_ctx_create.restype = vp
-        L.smf_ctx_create.argtypes = [ctypes.c_int]
-        L.smf_ctx_destroy.restype = None
-        L.smf_ctx_destroy.argtypes = [vp]
-        L.smf_crc32c_batch_device.restype = i32
-        L.smf_crc32c_batch_device.argtypes = [vp, vp, vp, vp, u32, vp, ctypes.c_int, vp]
-        L.smf_compress_device.restype = i32
-        L.smf_compress_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, ctypes.c_int, vp]
-        L.smf_index_device.restype = i32
-        L.smf_index_device.argtypes = [vp, vp, u64, pch, u32, vp, vp]
-        L.smf_uncompressed_length_device.restype = i32
-        L.smf_uncompressed_length_device.argtypes = [vp, vp, u64, vp, vp, vp]
-        L.smf_uncompress_chunks_device.restype = i32
-        L.smf_uncompress_chunks_device.argtypes = [vp, vp, pch, u32, vp, u64, vp, vp, vp, vp]
-        L.smf_uncompress_device.restype = i32
-        L.smf_uncompress_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp]
-        L.smf_compress.restype = i32
-        L.smf_compress.argtypes = [vp, vp, sz, vp, ctypes.POINTER(sz), ctypes.c_int]
-        L.smf_uncompress.restype = i32
-        L.smf_uncompress.argtypes = [vp, vp, sz, vp, ctypes.POINTER(sz)]
-        L.smf_validate.restype = i32
-        L.smf_validate.argtypes = [vp, vp, sz]
-        L.smf_chunk_offsets.restype = i32
-        L.smf_chunk_offsets.argtypes = [vp, u32, vp]
-        L.smf_range_chunk_count.restype = u64
-        L.smf_range_chunk_count.argtypes = [u64, u64]
-        L.smf_range_plan.restype = i32
-        L.smf_range_plan.argtypes = [pch, vp, u32, u64, vp, vp, u32, u32, vp, vp, vp, ctypes.POINTER(u64)]
-        L.smf_range_scratch_bytes.restype = sz
-        L.smf_range_scratch_bytes.argtypes = [u32, u32]
-        L.smf_chunk_offsets_device.restype = i32
-        L.smf_chunk_offsets_device.argtypes = [vp, vp, u32, vp, vp]
-        L.smf_compress_indexed_device.restype = i32
-        L.smf_compress_indexed_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, ctypes.c_int, pch, vp, u32, vp, vp]
-        L.smf_uncompress_ranges_device.restype = i32
-        L.smf_uncompress_ranges_device.argtypes = [vp, vp, u64, pch, vp, u32, vp, vp, u32, u32, vp, vp, vp, vp, vp]
-        L.smf_uncompress_range.restype = i32
-        L.smf_uncompress_range.argtypes = [vp, vp, sz, u64, u64, vp, ctypes.POINTER(sz)]
-        L.smf_max_data_chunks.restype = u64
-        L.smf_max_data_chunks.argtypes = [u64]
-        L.smf_streams_plan.restype = i32
-        L.smf_streams_plan.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp, vp, ctypes.POINTER(u64)]
-        L.smf_streams_scratch_bytes.restype = sz
-        L.smf_streams_scratch_bytes.argtypes = [u32, u32]
-        L.smf_uncompress_streams_device.restype = i32
-        L.smf_uncompress_streams_device.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.smf_compress_streams_device.restype = i32
-        L.smf_compress_streams_device.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, ctypes.c_int, vp]
-        L.smf_compress_streams.restype = i32
-        L.smf_compress_streams.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, ctypes.c_int]
-        L.smf_uncompress_streams.restype = i32
-        L.smf_uncompress_streams.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp]
-        _lib = L
+        _lib = load(LIB_PATH, FRAMING, "libsnappy_mi355x_framing.so not built (run __graft_entry__.build())")
     return _lib
 
 
@@ -174,16 +84,9 @@ class FramingError(SnappyError):
         super().__init__(code, status_message(code))
 
 
-def context(device=0):
-    """Per-device smf_ctx (an sm_ctx of its own plus scratch).  Raises if no device is usable."""
-    with _ctx_lock:
-        c = _ctx.get(device)
-        if c is None:
-            c = lib().smf_ctx_create(device)
-            if not c:
-                raise SnappyError(32, "no usable HIP device %d for snappy_mi355x_framing" % device)
-            _ctx[device] = c
-    return c
+# context(device=0): the per-device smf_ctx (an sm_ctx of its own plus scratch)
+_ctx, _ctx_lock, context = context_cache(lib, "smf_ctx_create", SnappyError,
+                                         "no usable HIP device %d for snappy_mi355x_framing")
 
 
 def max_framed_length(n):
@@ -211,15 +114,10 @@ def index_framed(data, max_chunks=None):
     if max_chunks is None:
         lib().smf_index(src, n, None, 0, ctypes.byref(s))
         max_chunks = s.nchunks
-    arrays = {"type": np.zeros(max_chunks, np.uint8), "pay_off": np.zeros(max_chunks, np.uint64),
-              "pay_len": np.zeros(max_chunks, np.uint32), "crc": np.zeros(max_chunks, np.uint32),
-              "ulen": np.zeros(max_chunks, np.uint32)}
-    ch = Chunks(*(arrays[k].ctypes.data for k in ("type", "pay_off", "pay_len", "crc", "ulen")))
+    arrays = {k: np.zeros(max_chunks, _UNSIGNED[k]) for k in INDEX_KEYS}
+    ch = Chunks(*(arrays[k].ctypes.data for k in INDEX_KEYS))
     lib().smf_index(src, n, ctypes.byref(ch), max_chunks, ctypes.byref(s))
     return s, arrays
-
-
-INDEX_KEYS = ("type", "pay_off", "pay_len", "crc", "ulen")
 
 
 class FramedIndex:
@@ -251,9 +149,7 @@ def chunk_offsets(ulen):
     """smf_chunk_offsets: the exclusive scan of ulen, with the total as the last entry (uint64)."""
     ulen = np.ascontiguousarray(ulen, dtype=np.uint32)
     off = np.zeros(ulen.size + 1, np.uint64)
-    st = lib().smf_chunk_offsets(ulen.ctypes.data, ulen.size, off.ctypes.data)
-    if st:
-        raise FramingError(st)
+    check(lib().smf_chunk_offsets(ulen.ctypes.data, ulen.size, off.ctypes.data), FramingError)
     return off
 
 
@@ -261,8 +157,7 @@ def seek_index_framed(data):
     """index_framed plus chunk_off, as a FramedIndex; raises SnappyError with the walk's
     structural error."""
     s, arrays = index_framed(data)
-    if s.status:
-        raise FramingError(s.status)
+    check(s.status, FramingError)
     return FramedIndex(arrays, chunk_offsets(arrays["ulen"]))
 
 
@@ -291,9 +186,7 @@ def length_uncompressed_framed(data):
     """The stream's total uncompressed length from its chunk headers (no device, no CRC check)."""
     src, n, keep = _in_arg(data)
     res = ctypes.c_size_t(0)
-    st = lib().smf_uncompressed_length(src, n, ctypes.byref(res))
-    if st:
-        raise FramingError(st)
+    check(lib().smf_uncompressed_length(src, n, ctypes.byref(res)), FramingError)
     return res.value
 
 
@@ -327,12 +220,18 @@ def uncompress_framed(data, device=0):
     return ctypes.string_at(ptr, ol.value)
 
 
-def _compress_framed_indexed(data, mode, device):
+def _upload(data, dev):
+    """(the bytes of `data` as a uint8 tensor on dev, their count)."""
     import torch
     src, n, keep = _in_arg(data)
-    dev = "cuda:%d" % device
     host = np.frombuffer(ctypes.string_at(src, n), np.uint8) if n else np.zeros(0, np.uint8)
-    d_in = torch.from_numpy(host.copy()).to(dev)
+    return torch.from_numpy(host.copy()).to(dev), n
+
+
+def _compress_framed_indexed(data, mode, device):
+    import torch
+    dev = "cuda:%d" % device
+    d_in, n = _upload(data, dev)
     nblk = (n + 65535) // 65536
     d_out = torch.empty(10 + 8 * nblk + n, dtype=torch.uint8, device=dev)
     d_len = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -340,8 +239,7 @@ def _compress_framed_indexed(data, mode, device):
     arrays, d_off = device_chunks(nblk, device), torch.zeros(nblk + 1, dtype=torch.int64, device=dev)
     d_nc = torch.zeros(1, dtype=torch.int32, device=dev)
     compress_framed_indexed_device(d_in, d_out, d_len, d_st, arrays, d_off, d_nc, mode=mode)
-    if int(d_st.item()):
-        raise FramingError(int(d_st.item()))
+    check(int(d_st.item()), FramingError)
     nc = int(d_nc.item())
     index = FramedIndex({k: arrays[k][:nc].cpu().numpy().view(_UNSIGNED[k]) for k in INDEX_KEYS},
                         d_off[:nc + 1].cpu().numpy().view(np.uint64))
@@ -355,17 +253,14 @@ def uncompress_framed_range(data, lo, length, index=None, device=0):
     (from compress_framed(..., return_index=True) or seek_index_framed) nothing is walked."""
     if index is not None:
         out, st = uncompress_framed_ranges(data, [(lo, length)], index=index, device=device)
-        if st[0]:
-            raise FramingError(int(st[0]))
+        check(int(st[0]), FramingError)
         return out[0]
     if int(lo) + int(length) > length_uncompressed_framed(data):  # (before any room is made for it)
         raise FramingError(33)
     src, n, keep = _in_arg(data)
     ptr, buf = _out_buffer(int(length))
     ol = ctypes.c_size_t(int(length))
-    st = lib().smf_uncompress_range(context(device), src, n, int(lo), int(length), ptr, ctypes.byref(ol))
-    if st:
-        raise FramingError(st)
+    check(lib().smf_uncompress_range(context(device), src, n, int(lo), int(length), ptr, ctypes.byref(ol)), FramingError)
     return ctypes.string_at(ptr, ol.value)
 
 
@@ -376,20 +271,18 @@ def uncompress_framed_ranges(data, ranges, index=None, device=0):
     import torch
     if index is None:
         index = seek_index_framed(data)
-    src, n, keep = _in_arg(data)
     dev = "cuda:%d" % device
     ranges = [(int(lo), int(ln)) for lo, ln in ranges]
     if not ranges:
         return [], np.zeros(0, np.int32)
+    d_in, n = _upload(data, dev)
     rc, _, count, status, total = range_plan(index, n, ranges)
-    host = np.frombuffer(ctypes.string_at(src, n), np.uint8) if n else np.zeros(0, np.uint8)
-    d_in = torch.from_numpy(host.copy()).to(dev)
     arrays = {k: torch.from_numpy(getattr(index, k).view(_SIGNED[k])).to(dev) for k in INDEX_KEYS}
     d_off = torch.from_numpy(index.chunk_off.view(np.int64)).to(dev)
     # outputs behind one another, each at a 16-byte boundary; a range that leaves the stream is
     # rejected before anything is written and gets no room
     room = [ln if lo + ln <= index.total_length else 0 for lo, ln in ranges]
-    out_off = np.concatenate([[0], np.cumsum([(r + 15) // 16 * 16 for r in room])]).astype(np.int64)
+    out_off = exclusive_scan([(r + 15) // 16 * 16 for r in room], np.int64, total=True)
     d_out = torch.empty(max(int(out_off[-1]), 1), dtype=torch.uint8, device=dev)
     d_lo = torch.tensor(np.array([r[0] for r in ranges], np.uint64).view(np.int64), device=dev)
     d_ln = torch.tensor(np.array([r[1] for r in ranges], np.uint64).view(np.int64), device=dev)
@@ -397,28 +290,13 @@ def uncompress_framed_ranges(data, ranges, index=None, device=0):
     d_ol = torch.zeros(len(ranges), dtype=torch.int64, device=dev)
     d_st = torch.zeros(len(ranges), dtype=torch.int32, device=dev)
     uncompress_ranges_device(d_in, arrays, d_off, index.nchunks, d_lo, d_ln, int(total), d_out, d_oo, d_ol, d_st, n=n)
-    st = d_st.cpu().numpy()
-    lens = d_ol.cpu().numpy()
-    out = d_out.cpu().numpy()
-    return [out[o:o + int(k)].tobytes() for o, k in zip(out_off[:-1].tolist(), lens.tolist())], st
+    return collect(d_out.cpu().numpy(), out_off, d_ol.cpu().numpy()), d_st.cpu().numpy()
 
 
 def max_data_chunks(n):
     """smf_max_data_chunks: the most data chunks an n-byte framed stream can hold, (n - 10) // 8.
     For a stream of this library's encoder ceil(uncompressed length / 65536) is the count."""
     return lib().smf_max_data_chunks(int(n))
-
-
-def _lay_out(datas):
-    """The buffers `datas` behind one another: (uint8 array, uint64 offsets, uint64 lengths)."""
-    parts = [np.frombuffer(d, np.uint8) if isinstance(d, (bytes, bytearray, memoryview)) else
-             np.ascontiguousarray(d).view(np.uint8).reshape(-1) for d in datas]
-    lens = np.array([p.size for p in parts], dtype=np.uint64)
-    offs = np.zeros(len(parts), np.uint64)
-    if len(parts) > 1:
-        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
-    buf = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
-    return (buf if buf.size else np.zeros(1, np.uint8)), offs, lens
 
 
 def streams_plan(streams, out_cap=None, max_chunks=0x7FFFFFFF):
@@ -444,19 +322,14 @@ def compress_framed_streams(datas, mode="fast", device=0):
     if not datas:
         return []
     buf, offs, lens = _lay_out(datas)
-    room = [10 + 8 * ((int(n) + 65535) // 65536) + int(n) for n in lens]
-    out_off = np.concatenate([[0], np.cumsum(room)]).astype(np.uint64)
+    out_off = exclusive_scan(10 + 8 * ((lens + 65535) // 65536) + lens, total=True)  # max_framed_length each
     out = np.empty(int(out_off[-1]), np.uint8)
     out_len, status = np.zeros(len(datas), np.uint64), np.zeros(len(datas), np.int32)
-    st = lib().smf_compress_streams(context(device), buf.ctypes.data, offs.ctypes.data, lens.ctypes.data, len(datas),
-                                    out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data, status.ctypes.data,
-                                    _mode(mode))
-    if st:
-        raise FramingError(st)
-    for s, code in enumerate(status.tolist()):
-        if code:
-            raise StreamError(code, s)
-    return [out[int(o):int(o) + int(n)].tobytes() for o, n in zip(out_off[:-1], out_len)]
+    check(lib().smf_compress_streams(context(device), buf.ctypes.data, offs.ctypes.data, lens.ctypes.data, len(datas),
+                                     out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data, status.ctypes.data,
+                                     _mode(mode)), FramingError)
+    _raise_first(status.tolist())
+    return collect(out, out_off, out_len)
 
 
 class StreamError(FramingError):
@@ -465,6 +338,12 @@ class StreamError(FramingError):
     def __init__(self, code, stream):
         super().__init__(code)
         self.stream = stream
+
+
+def _raise_first(codes):
+    for s, code in enumerate(codes):
+        if code:
+            raise StreamError(code, s)
 
 
 def uncompress_framed_streams(streams, device=0, return_status=False):
@@ -479,20 +358,16 @@ def uncompress_framed_streams(streams, device=0, return_status=False):
     k = len(streams)
     _, _, need, pre, _ = streams_plan(streams)
     cap = np.where(pre == 0, need, 0).astype(np.uint64)
-    out_off = np.concatenate([[0], np.cumsum(cap)]).astype(np.uint64)
+    out_off = exclusive_scan(cap, total=True)
     out = np.empty(max(int(out_off[-1]), 1), np.uint8)
     out_len, status = np.zeros(k, np.uint64), np.zeros(k, np.int32)
-    st = lib().smf_uncompress_streams(context(device), buf.ctypes.data, offs.ctypes.data, lens.ctypes.data, k,
-                                      out.ctypes.data, out_off.ctypes.data, cap.ctypes.data, out_len.ctypes.data,
-                                      status.ctypes.data)
-    if st:
-        raise FramingError(st)
+    check(lib().smf_uncompress_streams(context(device), buf.ctypes.data, offs.ctypes.data, lens.ctypes.data, k,
+                                       out.ctypes.data, out_off.ctypes.data, cap.ctypes.data, out_len.ctypes.data,
+                                       status.ctypes.data), FramingError)
     codes = status.tolist()
     if not return_status:
-        for s, code in enumerate(codes):
-            if code:
-                raise StreamError(code, s)
-    res = [None if code else out[int(o):int(o) + int(n)].tobytes() for code, o, n in zip(codes, out_off[:-1], out_len)]
+        _raise_first(codes)
+    res = collect(out, out_off, out_len, codes)
     return (res, codes) if return_status else res
 
 
@@ -504,66 +379,46 @@ def validate_framed(data, device=0):
 
 # ---- device API (torch tensors resident in HBM; asynchronous on `stream`) ---------------------
 
-def _dev(t, device):
-    return t.device.index if device is None else device
-
-
-def _sp(stream, dev):
-    return ctypes.c_void_p(_stream(stream, dev))
+_device = device_caller(lib, context, FramingError)
+_device_status = device_caller(lib, context, None)
 
 
 def device_chunks(max_chunks, device=0):
     """Index arrays for up to max_chunks data chunks on the device: a dict of torch tensors (type
     uint8, pay_off int64, pay_len / crc / ulen int32: the C ABI's unsigned values, bit for bit)."""
     import torch
-    dev = "cuda:%d" % device
     n = max(int(max_chunks), 1)
-    return {"type": torch.zeros(n, dtype=torch.uint8, device=dev), "pay_off": torch.zeros(n, dtype=torch.int64, device=dev),
-            "pay_len": torch.zeros(n, dtype=torch.int32, device=dev), "crc": torch.zeros(n, dtype=torch.int32, device=dev),
-            "ulen": torch.zeros(n, dtype=torch.int32, device=dev)}
+    return {k: torch.zeros(n, dtype=getattr(torch, np.dtype(_SIGNED[k]).name), device="cuda:%d" % device)
+            for k in INDEX_KEYS}
 
 
-def _chunks_struct(arrays):
-    return Chunks(*(arrays[k].data_ptr() for k in ("type", "pay_off", "pay_len", "crc", "ulen")))
-
-
-_SIGNED = {"type": np.uint8, "pay_off": np.int64, "pay_len": np.int32, "crc": np.int32, "ulen": np.int32}
-_UNSIGNED = {"type": np.uint8, "pay_off": np.uint64, "pay_len": np.uint32, "crc": np.uint32, "ulen": np.uint32}
+def _chunks_ref(arrays):
+    return ctypes.byref(Chunks(*(arrays[k].data_ptr() for k in INDEX_KEYS)))
 
 
 def crc32c_batch_device(d_in, d_off, d_len, d_crc, masked=False, stream=None, device=None):
     """d_crc[b] = CRC-32C of d_in[d_off[b] : d_off[b] + d_len[b]] (masked: the framing format's
     stored form).  d_in uint8, d_off int64, d_len / d_crc int32 CUDA tensors."""
-    dev = _dev(d_in, device)
-    st = lib().smf_crc32c_batch_device(context(dev), _ptr(d_in), _ptr(d_off), _ptr(d_len), d_len.numel(), _ptr(d_crc),
-                                       1 if masked else 0, _sp(stream, dev))
-    if st:
-        raise FramingError(st)
+    _device("smf_crc32c_batch_device", d_in, device, stream, d_in, d_off, d_len, d_len.numel(), d_crc,
+            1 if masked else 0)
 
 
 def compress_framed_device(d_in, d_out, d_out_len, d_status, mode="fast", stream=None, device=None):
     """Frame the uint8 tensor d_in into d_out (at least max_framed_length(d_in.numel()) bytes);
     d_out_len (int64[1]) and d_status (int32[1]) receive the stream's length and status."""
-    dev = _dev(d_out, device)
     n = d_in.numel()
-    st = lib().smf_compress_device(context(dev), _ptr(d_in) if n else None, n, _ptr(d_out), d_out.numel(),
-                                   _ptr(d_out_len), _ptr(d_status), _mode(mode), _sp(stream, dev))
-    if st:
-        raise FramingError(st)
+    _device("smf_compress_device", d_out, device, stream, d_in if n else None, n, d_out, d_out.numel(), d_out_len,
+            d_status, _mode(mode))
 
 
 def index_framed_device(d_in, arrays, d_summary, n=None, stream=None, device=None):
     """Walk the framed stream d_in[:n] on the device with one wave.  arrays: device_chunks(...) or
     None (count only); d_summary: 16 bytes (a uint8[16] or int64[2] tensor) receiving smf_summary
     -- read it with read_summary() after synchronising."""
-    dev = _dev(d_summary, device)
     n = d_in.numel() if n is None else int(n)
-    ch = _chunks_struct(arrays) if arrays is not None else None
-    cap = arrays["type"].numel() if arrays is not None else 0
-    st = lib().smf_index_device(context(dev), _ptr(d_in) if n else None, n, ctypes.byref(ch) if ch is not None else None,
-                                cap, _ptr(d_summary), _sp(stream, dev))
-    if st:
-        raise FramingError(st)
+    _device("smf_index_device", d_summary, device, stream, d_in if n else None, n,
+            _chunks_ref(arrays) if arrays is not None else None, arrays["type"].numel() if arrays is not None else 0,
+            d_summary)
 
 
 def read_summary(d_summary):
@@ -575,12 +430,8 @@ def read_summary(d_summary):
 def uncompressed_length_framed_device(d_in, d_len, d_status, n=None, stream=None, device=None):
     """d_len (int64[1]) = the total uncompressed length of the framed stream d_in[:n], d_status
     (int32[1]) = the walk's status."""
-    dev = _dev(d_len, device)
     n = d_in.numel() if n is None else int(n)
-    st = lib().smf_uncompressed_length_device(context(dev), _ptr(d_in) if n else None, n, _ptr(d_len), _ptr(d_status),
-                                              _sp(stream, dev))
-    if st:
-        raise FramingError(st)
+    _device("smf_uncompressed_length_device", d_len, device, stream, d_in if n else None, n, d_len, d_status)
 
 
 def uncompress_chunks_device(d_in, arrays, nchunks, d_out, d_chunk_status, d_out_len, d_status, stream=None,
@@ -588,13 +439,8 @@ def uncompress_chunks_device(d_in, arrays, nchunks, d_out, d_chunk_status, d_out
     """Decode the first nchunks indexed data chunks of d_in into d_out and check their CRCs
     (smf_uncompress_chunks_device): d_chunk_status int32[nchunks], d_out_len int64[1], d_status
     int32[1]."""
-    dev = _dev(d_out, device)
-    ch = _chunks_struct(arrays)
-    st = lib().smf_uncompress_chunks_device(context(dev), _ptr(d_in), ctypes.byref(ch), int(nchunks), _ptr(d_out),
-                                            d_out.numel(), _ptr(d_chunk_status), _ptr(d_out_len), _ptr(d_status),
-                                            _sp(stream, dev))
-    if st:
-        raise FramingError(st)
+    _device("smf_uncompress_chunks_device", d_out, device, stream, d_in, _chunks_ref(arrays), int(nchunks), d_out,
+            d_out.numel(), d_chunk_status, d_out_len, d_status)
 
 
 def uncompress_framed_device(d_in, d_out, d_out_len, d_status, n=None, stream=None, device=None):
@@ -602,10 +448,9 @@ def uncompress_framed_device(d_in, d_out, d_out_len, d_status, n=None, stream=No
     of `stream` between them.  Returns the host-known status (0, a structural error, or
     SM_BUFFER_TOO_SMALL with the needed size in d_out_len) instead of raising; the decode's own
     status (CRC, payload errors) arrives in d_status on the stream."""
-    dev = _dev(d_out, device)
     n = d_in.numel() if n is None else int(n)
-    return int(lib().smf_uncompress_device(context(dev), _ptr(d_in) if n else None, n, _ptr(d_out), d_out.numel(),
-                                           _ptr(d_out_len), _ptr(d_status), _sp(stream, dev)))
+    return _device_status("smf_uncompress_device", d_out, device, stream, d_in if n else None, n, d_out, d_out.numel(),
+                          d_out_len, d_status)
 
 
 def compress_framed_indexed_device(d_in, d_out, d_out_len, d_status, arrays, d_chunk_off, d_nchunks, mode="fast",
@@ -613,23 +458,15 @@ def compress_framed_indexed_device(d_in, d_out, d_out_len, d_status, arrays, d_c
     """compress_framed_device that also writes the stream's seek index (smf_compress_indexed_device):
     arrays = device_chunks(max_chunks), d_chunk_off int64[max_chunks + 1], d_nchunks int32[1];
     max_chunks is taken from d_chunk_off and must be at least ceil(d_in.numel() / 65536)."""
-    dev = _dev(d_out, device)
     n = d_in.numel()
-    ch = _chunks_struct(arrays)
-    st = lib().smf_compress_indexed_device(context(dev), _ptr(d_in) if n else None, n, _ptr(d_out), d_out.numel(),
-                                           _ptr(d_out_len), _ptr(d_status), _mode(mode), ctypes.byref(ch),
-                                           _ptr(d_chunk_off), d_chunk_off.numel() - 1, _ptr(d_nchunks), _sp(stream, dev))
-    if st:
-        raise FramingError(st)
+    _device("smf_compress_indexed_device", d_out, device, stream, d_in if n else None, n, d_out, d_out.numel(),
+            d_out_len, d_status, _mode(mode), _chunks_ref(arrays), d_chunk_off, d_chunk_off.numel() - 1, d_nchunks)
 
 
 def chunk_offsets_device(d_ulen, nchunks, d_chunk_off, stream=None, device=None):
     """d_chunk_off (int64[nchunks + 1]) = the exclusive scan of d_ulen[:nchunks] (int32, as
     device_chunks()["ulen"]): completes an index_framed_device index."""
-    dev = _dev(d_chunk_off, device)
-    st = lib().smf_chunk_offsets_device(context(dev), _ptr(d_ulen), int(nchunks), _ptr(d_chunk_off), _sp(stream, dev))
-    if st:
-        raise FramingError(st)
+    _device("smf_chunk_offsets_device", d_chunk_off, device, stream, d_ulen, int(nchunks), d_chunk_off)
 
 
 def uncompress_ranges_device(d_in, arrays, d_chunk_off, nchunks, d_lo, d_len, max_range_chunks, d_out, d_out_off,
@@ -637,15 +474,10 @@ def uncompress_ranges_device(d_in, arrays, d_chunk_off, nchunks, d_lo, d_len, ma
     """Batched ranged decode (smf_uncompress_ranges_device) of the indexed framed stream d_in[:n]:
     range r = bytes [d_lo[r], d_lo[r] + d_len[r]) of the content, written to d_out[d_out_off[r]:];
     d_lo / d_len / d_out_off / d_out_len int64[nranges], d_range_status int32[nranges]."""
-    dev = _dev(d_out, device)
     n = d_in.numel() if n is None else int(n)
-    ch = _chunks_struct(arrays)
-    st = lib().smf_uncompress_ranges_device(context(dev), _ptr(d_in) if n else None, n, ctypes.byref(ch),
-                                            _ptr(d_chunk_off), int(nchunks), _ptr(d_lo), _ptr(d_len), d_lo.numel(),
-                                            int(max_range_chunks), _ptr(d_out), _ptr(d_out_off), _ptr(d_out_len),
-                                            _ptr(d_range_status), _sp(stream, dev))
-    if st:
-        raise FramingError(st)
+    _device("smf_uncompress_ranges_device", d_out, device, stream, d_in if n else None, n, _chunks_ref(arrays),
+            d_chunk_off, int(nchunks), d_lo, d_len, d_lo.numel(), int(max_range_chunks), d_out, d_out_off, d_out_len,
+            d_range_status)
 
 
 def compress_framed_streams_device(d_in, d_in_off, d_in_len, max_blocks, d_out, d_out_off, d_out_len, d_status,
@@ -654,12 +486,8 @@ def compress_framed_streams_device(d_in, d_in_off, d_in_len, max_blocks, d_out, 
     d_in_len[s]] becomes one framed stream at d_out[d_out_off[s]:], where max_framed_length(d_in_len[s])
     bytes are left for it.  d_in / d_out uint8, d_in_off / d_in_len / d_out_off / d_out_len
     int64[nstreams], d_status int32[nstreams]; max_blocks bounds the sum of ceil(d_in_len[s] / 65536)."""
-    dev = _dev(d_out, device)
-    st = lib().smf_compress_streams_device(context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), d_in_len.numel(),
-                                           int(max_blocks), _ptr(d_out), _ptr(d_out_off), _ptr(d_out_len),
-                                           _ptr(d_status), _mode(mode), _sp(stream, dev))
-    if st:
-        raise FramingError(st)
+    _device("smf_compress_streams_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(),
+            int(max_blocks), d_out, d_out_off, d_out_len, d_status, _mode(mode))
 
 
 def uncompress_framed_streams_device(d_in, d_in_off, d_in_len, max_chunks, d_out, d_out_off, d_out_cap, d_out_len,
@@ -669,14 +497,8 @@ def uncompress_framed_streams_device(d_in, d_in_off, d_in_len, max_chunks, d_out
     stream d_out_len (int64) and d_status (int32) as uncompress_framed_device leaves them for that
     stream alone.  max_chunks bounds the data chunks summed over the streams that are decoded.
     Optional, both or neither: d_chunk_first int32[nstreams + 1], d_chunk_status int32[max_chunks]."""
-    dev = _dev(d_out, device)
-    st = lib().smf_uncompress_streams_device(
-        context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), d_in_len.numel(), int(max_chunks), _ptr(d_out),
-        _ptr(d_out_off), _ptr(d_out_cap), _ptr(d_out_len), _ptr(d_status),
-        None if d_chunk_first is None else _ptr(d_chunk_first),
-        None if d_chunk_status is None else _ptr(d_chunk_status), _sp(stream, dev))
-    if st:
-        raise FramingError(st)
+    _device("smf_uncompress_streams_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(),
+            int(max_chunks), d_out, d_out_off, d_out_cap, d_out_len, d_status, d_chunk_first, d_chunk_status)
 
 
 __all__ = ["FRAMING_ABI_SYMBOLS", "MODES", "compress_framed_streams", "uncompress_framed_streams", "streams_plan",

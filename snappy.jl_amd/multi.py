@@ -18,29 +18,21 @@ never correctness (the stream is then decoded in stream order).
 The package imports without this library; it is loaded on the first call here.  No CPU fallback:
 every codec call needs both HIP libraries and a device.
 """
-import ctypes
 import os
-import threading
 
 import numpy as np
 
-from . import HERE, MODES, SnappyError, _mode, _ptr, _stream, pack_blocks
+from . import HERE, MODES, SnappyError, _capacities, _mode, pack_blocks, slot_offsets
+from ._binding import MULTI, check, collect, context_cache, device_caller, exclusive_scan, load
 
 LIB_PATH = os.path.join(HERE, "libsnappy_mi355x_multi.so")
 BLOCK = 65536
 MAX_INPUT = 0x7FFFFFFF
 INDEX_STAGE = 4096  # kIndexStage (csrc/multi/smm_plan.h): the bytes the index walk stages per piece
 
-# exported symbols of include/snappy_mi355x_multi.h (checked by tests/test_multi_host.py)
-MULTI_ABI_SYMBOLS = (
-    "smm_ctx_create", "smm_ctx_destroy", "smm_version", "smm_status_message", "smm_fragment_count", "smm_scratch_bytes",
-    "smm_index_check", "smm_compress_device", "smm_uncompress_device", "smm_ctx_last_indexed", "smm_compress",
-    "smm_uncompress", "smm_index_host", "smm_index_device", "smm_index",
-)
+MULTI_ABI_SYMBOLS = tuple(MULTI)  # exported symbols of include/snappy_mi355x_multi.h (checked by tests/test_multi_host.py)
 
 _lib = None
-_ctx = {}
-_ctx_lock = threading.Lock()
 
 
 def library_path():
@@ -51,41 +43,7 @@ def lib():
     """Load libsnappy_mi355x_multi.so (raises OSError if it was not built)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise OSError("libsnappy_mi355x_multi.so not built (run __graft_entry__.build())")
-        L = ctypes.CDLL(LIB_PATH)
-        vp, sz, i32, u32, u64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64
-        L.smm_ctx_create.restype = vp
-        L.smm_ctx_create.argtypes = [ctypes.c_int]
-        L.smm_ctx_destroy.restype = None
-        L.smm_ctx_destroy.argtypes = [vp]
-        L.smm_version.restype = ctypes.c_char_p
-        L.smm_version.argtypes = []
-        L.smm_status_message.restype = ctypes.c_char_p
-        L.smm_status_message.argtypes = [i32]
-        L.smm_fragment_count.restype = u32
-        L.smm_fragment_count.argtypes = [u64]
-        L.smm_scratch_bytes.restype = sz
-        L.smm_scratch_bytes.argtypes = [u32, u32]
-        L.smm_index_check.restype = i32
-        L.smm_index_check.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp]
-        L.smm_compress_device.restype = i32
-        L.smm_compress_device.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, ctypes.c_int, vp]
-        L.smm_uncompress_device.restype = i32
-        L.smm_uncompress_device.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.smm_ctx_last_indexed.restype = ctypes.c_int
-        L.smm_ctx_last_indexed.argtypes = [vp]
-        L.smm_compress.restype = i32
-        L.smm_compress.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, ctypes.c_int]
-        L.smm_uncompress.restype = i32
-        L.smm_uncompress.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]
-        L.smm_index_host.restype = i32
-        L.smm_index_host.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp]
-        L.smm_index_device.restype = i32
-        L.smm_index_device.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]
-        L.smm_index.restype = i32
-        L.smm_index.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp]
-        _lib = L
+        _lib = load(LIB_PATH, MULTI, "libsnappy_mi355x_multi.so not built (run __graft_entry__.build())")
     return _lib
 
 
@@ -97,16 +55,9 @@ def status_message(code):
     return lib().smm_status_message(int(code)).decode()
 
 
-def context(device=0):
-    """Per-device smm_ctx (an sm_ctx of its own plus scratch).  Raises if no device is usable."""
-    with _ctx_lock:
-        c = _ctx.get(device)
-        if c is None:
-            c = lib().smm_ctx_create(device)
-            if not c:
-                raise SnappyError(32, "no usable HIP device %d for snappy_mi355x_multi" % device)
-            _ctx[device] = c
-    return c
+# context(device=0): the per-device smm_ctx (an sm_ctx of its own plus scratch)
+_ctx, _ctx_lock, context = context_cache(lib, "smm_ctx_create", SnappyError,
+                                         "no usable HIP device %d for snappy_mi355x_multi")
 
 
 def fragment_count(n):
@@ -122,11 +73,17 @@ def frag_first_of(lengths):
     """The index's frag_first for inputs of these lengths, on the host: the exclusive scan of
     fragment_count (nstreams + 1 entries)."""
     counts = [(int(n) + BLOCK - 1) // BLOCK if int(n) <= MAX_INPUT else 0 for n in lengths]
-    return np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.uint32)
+    return exclusive_scan(counts, np.uint32, total=True)
 
 
 def _addr(a):
     return a.ctypes.data if a is not None and a.size else None
+
+
+def _raise_first(status):
+    """SnappyError with the first status of a batch that is not 0."""
+    if status.any():
+        raise SnappyError(int(status[np.nonzero(status)[0][0]]))
 
 
 def index_check(streams, index, capacities=None, max_fragments=None):
@@ -144,23 +101,13 @@ def index_check(streams, index, capacities=None, max_fragments=None):
         raise ValueError("frag_pos is shorter than max_fragments")
     out = np.zeros(len(streams), np.uint8)
     keep = np.zeros(1, np.uint8)
-    st = lib().smm_index_check(_addr(buf) or keep.ctypes.data, _addr(in_off), _addr(in_len), len(streams),
-                               int(max_fragments), _addr(cap), first.ctypes.data if first is not None else None,
-                               (_addr(pos) or keep.ctypes.data) if pos is not None else None, _addr(out))
-    if st:
-        raise SnappyError(st)
+    check(lib().smm_index_check(_addr(buf) or keep.ctypes.data, _addr(in_off), _addr(in_len), len(streams),
+                                int(max_fragments), _addr(cap), first.ctypes.data if first is not None else None,
+                                (_addr(pos) or keep.ctypes.data) if pos is not None else None, _addr(out)), SnappyError)
     return out
 
 
 # ---- host buffers -----------------------------------------------------------------------
-
-def _slots(in_len):
-    caps = (32 + in_len.astype(np.uint64) + in_len.astype(np.uint64) // 6 + 15) // 16 * 16
-    offs = np.zeros(in_len.size, dtype=np.uint64)
-    if in_len.size > 1:
-        offs[1:] = np.cumsum(caps[:-1], dtype=np.uint64)
-    return offs, caps
-
 
 def compress_streams(datas, mode="fast", device=0, return_index=False):
     """Compress independent inputs of any length (each at most 2^31 - 1 bytes) in one call on the
@@ -177,35 +124,20 @@ def compress_streams(datas, mode="fast", device=0, return_index=False):
     pos = np.zeros(max(entries, 1), np.uint32)
     outs = []
     if n:
-        out_off, caps = _slots(in_len)
+        out_off, caps = slot_offsets(in_len)
         out = np.empty(int(out_off[-1] + caps[-1]), dtype=np.uint8)
         out_len = np.zeros(n, np.uint32)
         status = np.zeros(n, np.int32)
         keep = np.zeros(1, np.uint8)
-        st = lib().smm_compress(context(device), _addr(buf) or keep.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, n,
-                                out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data, status.ctypes.data,
-                                first.ctypes.data if return_index else None, pos.ctypes.data if return_index else None,
-                                _mode(mode))
-        if st:
-            raise SnappyError(st)
-        if status.any():
-            raise SnappyError(int(status[np.nonzero(status)[0][0]]))
-        outs = [out[int(o): int(o) + int(l)].tobytes() for o, l in zip(out_off, out_len)]
+        check(lib().smm_compress(context(device), _addr(buf) or keep.ctypes.data, in_off.ctypes.data, in_len.ctypes.data,
+                                 n, out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data, status.ctypes.data,
+                                 first.ctypes.data if return_index else None, pos.ctypes.data if return_index else None,
+                                 _mode(mode)), SnappyError)
+        _raise_first(status)
+        outs = collect(out, out_off, out_len)
     if return_index:
         return outs, (first, pos[:entries])
     return outs
-
-
-def _capacities(streams, capacities):
-    if capacities is None:
-        from . import parse32
-        capacities = []
-        for s in streams:
-            try:
-                capacities.append(parse32(s)[0])
-            except SnappyError:
-                capacities.append(0)
-    return np.array(capacities, dtype=np.uint32)
 
 
 def _index_call(streams, capacities, max_fragments, call):
@@ -221,13 +153,9 @@ def _index_call(streams, capacities, max_fragments, call):
     built = np.zeros(max(n, 1), np.uint8)
     status = np.zeros(max(n, 1), np.int32)
     keep = np.zeros(1, np.uint8)
-    st = call(_addr(buf) or keep.ctypes.data, _addr(in_off), _addr(in_len), n, int(max_fragments),
-              _addr(cap) if cap is not None else None, first.ctypes.data, pos.ctypes.data, built.ctypes.data,
-              status.ctypes.data)
-    if st:
-        raise SnappyError(st)
-    if status[:n].any():
-        raise SnappyError(int(status[np.nonzero(status)[0][0]]))
+    check(call(_addr(buf) or keep.ctypes.data, _addr(in_off), _addr(in_len), n, int(max_fragments), _addr(cap),
+               first.ctypes.data, pos.ctypes.data, built.ctypes.data, status.ctypes.data), SnappyError)
+    _raise_first(status[:n])
     return first, pos[:int(first[-1])], built[:n]
 
 
@@ -296,17 +224,14 @@ def uncompress_streams(streams, index=None, capacities=None, device=0):
         raise ValueError("index must be None, (frag_first, frag_pos) or 'build'")
     buf, in_off, in_len = pack_blocks(streams)
     cap = _capacities(streams, capacities)
-    out_off = np.zeros(n, dtype=np.uint64)
-    if n > 1:
-        out_off[1:] = np.cumsum(cap[:-1].astype(np.uint64), dtype=np.uint64)
-    out = np.empty(max(int(cap.astype(np.uint64).sum()), 1), dtype=np.uint8)
+    out_off = exclusive_scan(cap, total=True)
+    out = np.empty(max(int(out_off[-1]), 1), dtype=np.uint8)
     out_len = np.zeros(n, np.uint32)
     status = np.zeros(n, np.int32)
     first = pos = None
     if isinstance(index, str):
-        _uncompress_building(buf, in_off, in_len, cap, out_off, out_len, status, out, device)
-        res = [out[int(o): int(o) + int(l)].tobytes() if s == 0 else None for o, l, s in zip(out_off, out_len, status)]
-        return res, status
+        _uncompress_building(buf, in_off, in_len, cap, out_off[:-1], out_len, status, out, device)
+        return collect(out, out_off, out_len, status), status
     if index is not None:
         first = np.ascontiguousarray(index[0], dtype=np.uint32)
         pos = np.ascontiguousarray(index[1], dtype=np.uint32)
@@ -315,20 +240,15 @@ def uncompress_streams(streams, index=None, capacities=None, device=0):
         if pos.size == 0:
             pos = np.zeros(1, np.uint32)
     keep = np.zeros(1, np.uint8)
-    st = lib().smm_uncompress(context(device), _addr(buf) or keep.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, n,
-                              out.ctypes.data, out_off.ctypes.data, cap.ctypes.data, out_len.ctypes.data,
-                              status.ctypes.data, first.ctypes.data if first is not None else None,
-                              pos.ctypes.data if pos is not None else None)
-    if st:
-        raise SnappyError(st)
-    res = [out[int(o): int(o) + int(l)].tobytes() if s == 0 else None for o, l, s in zip(out_off, out_len, status)]
-    return res, status
+    check(lib().smm_uncompress(context(device), _addr(buf) or keep.ctypes.data, in_off.ctypes.data, in_len.ctypes.data, n,
+                               out.ctypes.data, out_off.ctypes.data, cap.ctypes.data, out_len.ctypes.data,
+                               status.ctypes.data, _addr(first), _addr(pos)), SnappyError)
+    return collect(out, out_off, out_len, status), status
 
 
 # ---- device API (torch tensors resident in HBM; asynchronous on `stream`) ---------------------
 
-def _opt(t):
-    return _ptr(t) if t is not None else None
+_device = device_caller(lib, context, SnappyError)
 
 
 def compress_streams_device(d_in, d_in_off, d_in_len, max_fragments, d_out, d_out_off, d_out_len, d_status,
@@ -336,37 +256,24 @@ def compress_streams_device(d_in, d_in_off, d_in_len, max_fragments, d_out, d_ou
     """smm_compress_device: d_in / d_out uint8, d_in_off / d_out_off int64, d_in_len / d_out_len /
     d_status int32 CUDA tensors (the C ABI's unsigned values, bit for bit); the index tensors
     (int32, nstreams + 1 and max_fragments entries) both or neither.  Nothing is synchronised."""
-    dev = d_out.device.index if device is None else device
-    st = lib().smm_compress_device(context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), d_in_len.numel(),
-                                   int(max_fragments), _ptr(d_out), _ptr(d_out_off), _ptr(d_out_len), _ptr(d_status),
-                                   _opt(d_frag_first), _opt(d_frag_pos), _mode(mode), ctypes.c_void_p(_stream(stream, dev)))
-    if st:
-        raise SnappyError(st)
+    _device("smm_compress_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), int(max_fragments),
+            d_out, d_out_off, d_out_len, d_status, d_frag_first, d_frag_pos, _mode(mode))
 
 
 def uncompress_streams_device(d_in, d_in_off, d_in_len, max_fragments, d_out, d_out_off, d_out_cap, d_out_len, d_status,
                               d_frag_first=None, d_frag_pos=None, stream=None, device=None):
     """smm_uncompress_device (tensor types as in compress_streams_device).  max_fragments: the
     entries of d_frag_pos.  Nothing is synchronised."""
-    dev = d_out.device.index if device is None else device
-    st = lib().smm_uncompress_device(context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), d_in_len.numel(),
-                                     int(max_fragments), _ptr(d_out), _ptr(d_out_off), _ptr(d_out_cap), _ptr(d_out_len),
-                                     _ptr(d_status), _opt(d_frag_first), _opt(d_frag_pos),
-                                     ctypes.c_void_p(_stream(stream, dev)))
-    if st:
-        raise SnappyError(st)
+    _device("smm_uncompress_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(),
+            int(max_fragments), d_out, d_out_off, d_out_cap, d_out_len, d_status, d_frag_first, d_frag_pos)
 
 
 def index_streams_device(d_in, d_in_off, d_in_len, max_fragments, d_frag_first, d_frag_pos, d_built, d_status,
                          d_out_cap=None, stream=None, device=None):
     """smm_index_device (tensor types as in compress_streams_device; d_built uint8, nstreams
     entries; d_frag_pos max_fragments entries; d_out_cap None: no cap).  Nothing is synchronised."""
-    dev = d_in.device.index if device is None else device
-    st = lib().smm_index_device(context(dev), _ptr(d_in), _ptr(d_in_off), _ptr(d_in_len), d_in_len.numel(),
-                                int(max_fragments), _opt(d_out_cap), _ptr(d_frag_first), _ptr(d_frag_pos), _ptr(d_built),
-                                _ptr(d_status), ctypes.c_void_p(_stream(stream, dev)))
-    if st:
-        raise SnappyError(st)
+    _device("smm_index_device", d_in, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), int(max_fragments),
+            d_out_cap, d_frag_first, d_frag_pos, d_built, d_status)
 
 
 def last_indexed(device=0):
