@@ -1,4 +1,4 @@
-"""What the three ctypes bindings of this package share (__init__.py, framing.py, multi.py): the
+"""What the four ctypes bindings of this package share (__init__.py, framing.py, multi.py, blocks.py): the
 prototype table of each library, the loader and the per-device context cache, the status, stream
 and device rules of the device wrappers, and the layout of a batch in one host buffer.
 
@@ -7,9 +7,10 @@ A prototype is "<return> <arguments>", one letter per C type:
     v void        c const char* (a returned text)     p any other pointer, as an address
     i int         s sm_status / int32_t               u uint32_t     q uint64_t     z size_t
     Z size_t*     U uint32_t*    Q uint64_t*          (results the wrappers pass by reference)
-    C smf_chunks*                S smf_summary*
+    C smf_chunks*                S smf_summary* / smb_summary* (one layout)       B smb_chunks*
 
-tests/test_bindings.py holds every entry against the declaration in include/*.h.
+tests/test_bindings.py holds every entry against the declaration in include/*.h
+(tests/test_blocks_host.py: the BLOCKS table).
 """
 import ctypes
 import os
@@ -25,8 +26,13 @@ class Chunks(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in INDEX_KEYS]
 
 
+class BlockChunks(ctypes.Structure):
+    """smb_chunks: three parallel arrays, one entry per chunk."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("pay_off", "pay_len", "ulen")]
+
+
 class Summary(ctypes.Structure):
-    """smf_summary."""
+    """smf_summary, and smb_summary with the same fields."""
     _fields_ = [("total_length", ctypes.c_uint64), ("nchunks", ctypes.c_uint32), ("status", ctypes.c_int32)]
 
 
@@ -34,7 +40,7 @@ CTYPES = {
     "v": None, "c": ctypes.c_char_p, "p": ctypes.c_void_p, "i": ctypes.c_int, "s": ctypes.c_int32,
     "u": ctypes.c_uint32, "q": ctypes.c_uint64, "z": ctypes.c_size_t, "Z": ctypes.POINTER(ctypes.c_size_t),
     "U": ctypes.POINTER(ctypes.c_uint32), "Q": ctypes.POINTER(ctypes.c_uint64), "C": ctypes.POINTER(Chunks),
-    "S": ctypes.POINTER(Summary),
+    "S": ctypes.POINTER(Summary), "B": ctypes.POINTER(BlockChunks),
 }
 
 RAW = {  # include/snappy_mi355x.h
@@ -134,6 +140,24 @@ MULTI = {  # include/snappy_mi355x_multi.h
     "smm_index_host": "s pppuuppppp",
     "smm_index_device": "s ppppuupppppp",
     "smm_index": "s ppppuuppppp",
+}
+
+BLOCKS = {  # include/snappy_mi355x_blocks.h
+    "smb_status_message": "c s",
+    "smb_version": "c",
+    "smb_max_length": "z zi",
+    "smb_max_chunks": "q qi",
+    "smb_index": "s pziBuS",
+    "smb_uncompressed_length": "s pziZ",
+    "smb_streams_plan": "s pppuipupppQQ",
+    "smb_streams_scratch_bytes": "z uuu",
+    "smb_ctx_create": "p i",
+    "smb_ctx_destroy": "v p",
+    "smb_ctx_last_indexed": "i p",
+    "smb_uncompress_streams_device": "s pipppuuupppppppp",
+    "smb_compress_streams_device": "s pipppuuppppip",
+    "smb_compress_streams": "s pipppuppppi",
+    "smb_uncompress_streams": "s pipppuppppp",
 }
 
 

@@ -1,7 +1,8 @@
 # The body of a companion library's Makefile (../framing, ../multi): libsnappy_mi355x_$(LIB).so
 # (gfx950 only) next to the package, linking libsnappy_mi355x.so by name (found beside it through
 # $ORIGIN; ../Makefile builds it first).  The including Makefile sets LIB, PFX (the sources' and
-# the ABI's prefix), VERSION_MACRO, SRCS, HOSTSRCS and its own HDRS.
+# the ABI's prefix), VERSION_MACRO, SRCS, HOSTSRCS and its own HDRS; optionally LINK, the further
+# companions it links by name (../blocks: multi), which their own Makefiles build first.
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 MK = ../common/companion.mk
@@ -11,6 +12,7 @@ VERSION ?= src-$(shell (cat $(SRCS) $(HOSTSRCS) $(HDRS) Makefile $(MK); echo '$(
 EXTRA ?=
 BASE = --offload-arch=$(ARCH) -O3 -std=c++17 -fno-strict-aliasing -fPIC -Wall $(EXTRA)
 MAIN = ../../libsnappy_mi355x.so
+LINK ?=
 OUT ?= ../../libsnappy_mi355x_$(LIB).so
 OBJ ?= build
 OBJS = $(patsubst %.hip,$(OBJ)/%.o,$(SRCS)) $(patsubst %.cpp,$(OBJ)/%.o,$(HOSTSRCS))
@@ -36,8 +38,8 @@ $(OBJ)/%.o: %.cpp $(HDRS) Makefile $(MK)
 	@mkdir -p $(OBJ)
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -c -o $@ $<
 
-$(OUT): $(OBJS) $(MAIN)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $(OBJS) -L../.. -l:libsnappy_mi355x.so -Wl,-rpath,'$$ORIGIN'
+$(OUT): $(OBJS) $(MAIN) $(LINK:%=../../libsnappy_mi355x_%.so)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -o $@ $(OBJS) -L../.. $(LINK:%=-l:libsnappy_mi355x_%.so) -l:libsnappy_mi355x.so -Wl,-rpath,'$$ORIGIN'
 
 # The host-only file and its stand-alone driver under AddressSanitizer and UBSan (CPU only;
 # nothing here touches a device).
