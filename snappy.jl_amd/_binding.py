@@ -10,7 +10,7 @@ A prototype is "<return> <arguments>", one letter per C type:
     C smf_chunks*                S smf_summary* / smb_summary* (one layout)       B smb_chunks*
 
 tests/test_bindings.py holds every entry against the declaration in include/*.h
-(tests/test_blocks_host.py: the BLOCKS table).
+(tests/test_blocks_host.py: the BLOCKS table; tests/test_multi_range_host.py: MULTI_RANGE).
 """
 import ctypes
 import os
@@ -140,6 +140,14 @@ MULTI = {  # include/snappy_mi355x_multi.h
     "smm_index_host": "s pppuuppppp",
     "smm_index_device": "s ppppuupppppp",
     "smm_index": "s ppppuuppppp",
+}
+
+MULTI_RANGE = {  # include/snappy_mi355x_multi_range.h: the ranged decode, exported by the multi library
+    "smm_range_fragment_count": "u uu",
+    "smm_range_scratch_bytes": "z uu",
+    "smm_range_plan": "s pppuppupppuupppQ",
+    "smm_uncompress_ranges_device": "s ppppuppupppuuppppp",
+    "smm_uncompress_ranges": "s ppppupppppupppp",
 }
 
 BLOCKS = {  # include/snappy_mi355x_blocks.h

@@ -1,6 +1,7 @@
 // smm_api.hip -- C ABI of the multi-stream library (include/snappy_mi355x_multi.h) over the raw
 // codec's public batched device calls (libsnappy_mi355x.so, linked by name) and the kernels of
-// smm_kernels.hip and smm_index.hip.  The host-only entry points live in smm_host.cpp.
+// smm_kernels.hip, smm_index.hip and smm_range.hip (the ranged decode of
+// include/snappy_mi355x_multi_range.h).  The host-only entry points live in smm_host.cpp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -11,6 +12,7 @@
 
 #include "../common/smc_hip_host.h"
 #include "smm_plan.h"
+#include "smm_range.h"
 
 #ifndef SMM_VERSION_STR
 #define SMM_VERSION_STR "dev"
@@ -29,7 +31,7 @@ struct smm_ctx {
   int device = 0;
   hipStream_t stream = nullptr;  // the sm_ctx's: the host-buffer calls run on it
   DevBuf hdr;                    // smm::Header
-  DevBuf meta, slots;            // the per-call arrays; compress: the fragments' output slots
+  DevBuf meta, slots;            // the per-call arrays; compress: the fragments' output slots, ranges: the edge slots
   DevBuf io_in, io_out, io_meta; // the host-buffer calls' staging
   bool called = false;           // an uncompress call has been made (smm_ctx_last_indexed)
   std::mutex mu;                 // serialises the host-buffer entry points
@@ -168,6 +170,36 @@ sm_status smm_index_device(smm_ctx* ctx, const uint8_t* d_in, const uint64_t* d_
   return SM_OK;
 }
 
+// Launch sequence: find, scan, slots, the raw fragment decoder once over all slots (its output base
+// the edge slots: smm_range.hip, k_mrange_slots), trim, verdict, result.
+sm_status smm_uncompress_ranges_device(smm_ctx* ctx, const uint8_t* d_in, const uint64_t* d_in_off,
+                                       const uint32_t* d_in_len, uint32_t nstreams, const uint32_t* d_frag_first,
+                                       const uint32_t* d_frag_pos, uint32_t nentries, const uint32_t* d_range_stream,
+                                       const uint32_t* d_lo, const uint32_t* d_len, uint32_t nranges,
+                                       uint32_t max_range_fragments, uint8_t* d_out, const uint64_t* d_out_off,
+                                       uint32_t* d_out_len, int32_t* d_status, void* stream) {
+  if (!ctx) return SM_ERR_ARGUMENT;
+  if (nranges == 0) return SM_OK;
+  if (!d_in || !d_in_off || !d_in_len || !d_frag_first || !d_frag_pos || !d_range_stream || !d_lo || !d_len || !d_out ||
+      !d_out_off || !d_out_len || !d_status)
+    return SM_ERR_ARGUMENT;
+  hipStream_t s = (hipStream_t)stream;
+  DeviceGuard g(ctx->device);
+  const uint32_t n = nranges, m = max_range_fragments;
+  SM_CHECK(ctx->meta.ensure(smm::range_arrays_bytes(n, m)));
+  SM_CHECK(ctx->slots.ensure(smm::range_edge_slots(n, m) * (size_t)smm::kEdgePitch));
+  const smm::RangeArgs a{d_in,  d_in_off, d_in_len, nstreams,  d_frag_first, d_frag_pos,
+                         nentries, d_range_stream, d_lo, d_len, n, m,
+                         d_out, d_out_off, d_out_len, d_status,  (uint8_t*)ctx->slots.p,
+                         smm::carve_range((uint8_t*)ctx->meta.p, n, m)};
+  SM_CHECK(smm::launch_range_plan(a, s));
+  if (m)
+    SM_PASS(sm_uncompress_fragments_device(ctx->sm, d_in, a.s.f_in_off, a.s.f_in_len, m, a.edge, a.s.f_out_off, a.s.f_len,
+                                           a.s.f_out_len, a.s.f_status, stream));
+  SM_CHECK(smm::launch_range_finish(a, s));
+  return SM_OK;
+}
+
 // ---- host buffers ------------------------------------------------------------------------------
 
 namespace {  // (its functions are static: inside extern "C" the unnamed namespace alone still exports them)
@@ -226,6 +258,30 @@ static sm_status copy_out(smm_ctx* ctx, uint8_t* out, const uint64_t* out_off, c
   }
   SM_CHECK(hipStreamSynchronize(s));
   return SM_OK;
+}
+
+// the device copies of a ranged host call's arrays, in ctx->io_meta (n streams, k ranges)
+struct RangeHostArrays {
+  uint64_t *in_off, *out_off;
+  uint32_t *in_len, *first, *pos, *range_stream, *lo, *len, *out_len;
+  int32_t* status;
+  uintptr_t end;
+};
+static RangeHostArrays carve_range_host(uintptr_t base, size_t n, size_t entries, size_t k) {
+  smm::Carve c{base};
+  RangeHostArrays a;
+  a.in_off = c.take<uint64_t>(n);
+  a.out_off = c.take<uint64_t>(k);
+  a.in_len = c.take<uint32_t>(n);
+  a.first = c.take<uint32_t>(n + 1);
+  a.pos = c.take<uint32_t>(entries);
+  a.range_stream = c.take<uint32_t>(k);
+  a.lo = c.take<uint32_t>(k);
+  a.len = c.take<uint32_t>(k);
+  a.out_len = c.take<uint32_t>(k);
+  a.status = c.take<int32_t>(k);
+  a.end = c.p;
+  return a;
 }
 
 }  // namespace
@@ -341,6 +397,82 @@ sm_status smm_index(smm_ctx* ctx, const uint8_t* in, const uint64_t* in_off, con
   const size_t entries = frag_first[n];  // (at most max_fragments: the device's own scan)
   if (entries > m) return SM_ERR_DEVICE;
   if (entries) SM_CHECK(hipMemcpy(frag_pos, a.pos, 4 * entries, hipMemcpyDeviceToHost));
+  return SM_OK;
+}
+
+// The stream-level rule runs here first (the device's own code, smm_range.h): it names the streams
+// that some range can be served from -- those alone go up, whole, at their own offsets, with their
+// index entries -- and counts the slots.  A range the rule refuses here is final, and the device
+// reads no stream for it.  The ranges' outputs lie behind one another in ctx->io_out, each at a
+// 16-byte boundary.
+sm_status smm_uncompress_ranges(smm_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len,
+                                uint32_t nstreams, const uint32_t* frag_first, const uint32_t* frag_pos,
+                                const uint32_t* range_stream, const uint32_t* lo, const uint32_t* len, uint32_t nranges,
+                                uint8_t* out, const uint64_t* out_off, uint32_t* out_len, int32_t* status) {
+  if (!ctx) return SM_ERR_ARGUMENT;
+  if (nranges == 0) return SM_OK;
+  if (!in || !in_off || !in_len || !frag_first || !frag_pos || !range_stream || !lo || !len || !out || !out_off ||
+      !out_len || !status)
+    return SM_ERR_ARGUMENT;
+  const size_t n = nstreams, k = nranges;
+  const size_t entries = frag_first[n];
+  if (entries > 0x7fffffffull) return SM_ERR_ARGUMENT;
+  std::vector<uint8_t> named(n, 0);
+  std::vector<uint64_t> d_off(k, 0);
+  std::vector<uint32_t> d_stream(range_stream, range_stream + k);
+  uint64_t slots = 0, out_total = 0;
+  size_t in_total = 0;
+  for (size_t r = 0; r < k; ++r) {
+    smm::Candidate c;
+    const smm::RangeSpan sp =
+        smm::range_span(in, in_off, in_len, nstreams, frag_first, (uint32_t)entries, range_stream[r], lo[r], len[r], c);
+    // A range that failed here is settled: the device gets it with a stream number past the last,
+    // which its rule refuses with the same status before it reads a byte -- so it never looks at
+    // a stream that did not go up.
+    if (sp.status != SM_OK) d_stream[r] = nstreams;
+    if (sp.status != SM_OK || sp.count == 0) continue;
+    const uint32_t s = range_stream[r];
+    named[s] = 1;
+    const size_t ie = in_off[s] + in_len[s];
+    if (ie > in_total) in_total = ie;
+    slots += sp.count;
+    d_off[r] = out_total;
+    out_total += ((uint64_t)len[r] + 15) / 16 * 16;
+  }
+  if (slots > 0x7fffffffull) return SM_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  SM_CHECK(ctx->io_meta.ensure(carve_range_host(0, n, entries, k).end));
+  const RangeHostArrays a = carve_range_host((uintptr_t)ctx->io_meta.p, n, entries, k);
+  SM_CHECK(ctx->io_in.ensure(in_total + 16));
+  SM_CHECK(ctx->io_out.ensure((size_t)out_total + 16));
+  for (size_t i = 0; i < n; ++i) {
+    if (!named[i]) continue;
+    if (in_len[i])
+      SM_CHECK(hipMemcpyAsync((uint8_t*)ctx->io_in.p + in_off[i], in + in_off[i], in_len[i], hipMemcpyHostToDevice, s));
+    const uint32_t e0 = frag_first[i], e1 = frag_first[i + 1];  // (in order and inside frag_pos: the rule passed)
+    if (e1 > e0) SM_CHECK(hipMemcpyAsync(a.pos + e0, frag_pos + e0, 4 * (size_t)(e1 - e0), hipMemcpyHostToDevice, s));
+  }
+  SM_CHECK(hipMemcpyAsync(a.in_off, in_off, 8 * n, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(a.in_len, in_len, 4 * n, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(a.first, frag_first, 4 * (n + 1), hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(a.out_off, d_off.data(), 8 * k, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(a.range_stream, d_stream.data(), 4 * k, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(a.lo, lo, 4 * k, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(a.len, len, 4 * k, hipMemcpyHostToDevice, s));
+  SM_PASS(smm_uncompress_ranges_device(ctx, (const uint8_t*)ctx->io_in.p, a.in_off, a.in_len, nstreams, a.first, a.pos,
+                                       (uint32_t)entries, a.range_stream, a.lo, a.len, nranges, (uint32_t)slots,
+                                       (uint8_t*)ctx->io_out.p, a.out_off, a.out_len, a.status, s));
+  SM_CHECK(hipMemcpyAsync(out_len, a.out_len, 4 * k, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(status, a.status, 4 * k, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipStreamSynchronize(s));  // (also lets the pageable uploads above leave d_off and d_stream)
+  for (size_t r = 0; r < k; ++r) {
+    if (status[r] != SM_OK || out_len[r] == 0) continue;
+    if (out_len[r] != len[r] || d_off[r] + len[r] > out_total) return SM_ERR_DEVICE;  // (never: the device's own rule)
+    SM_CHECK(hipMemcpyAsync(out + out_off[r], (const uint8_t*)ctx->io_out.p + d_off[r], len[r], hipMemcpyDeviceToHost, s));
+  }
+  SM_CHECK(hipStreamSynchronize(s));
   return SM_OK;
 }
 

@@ -4,6 +4,9 @@
 // value could cause.  The rules are the device plan's own code (smm_plan.h).  Then smm_index_host,
 // the rule that builds an index, over streams built from tag bytes on heap buffers of exactly the
 // streams' size: a walk that read past a stream's end, or wrote past its entries, stops here.
+// Then smm_range_plan, the plan of the ranged decode (smm_range.h): every case alone on heap arrays
+// of exactly the documented sizes, so an entry or a frag_first word read that the rules do not allow
+// is a read past an array.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -12,6 +15,7 @@
 #include <vector>
 
 #include "smm_plan.h"
+#include "smm_range.h"
 
 namespace {
 
@@ -246,6 +250,214 @@ void index_cases() {
   }
 }
 
+// ---- smm_range_plan ------------------------------------------------------------------------------------
+struct Range {
+  uint32_t s, lo, len;
+};
+struct PlanResult {
+  sm_status st;
+  U first, count;
+  std::vector<int32_t> status;
+  uint64_t total;
+};
+const uint32_t kAll = 0xffffffffu;
+
+// One call: the streams' bytes, frag_first, nentries entries of pos and the ranges each on a heap
+// array of exactly its size.  len_as: a length to pass instead of stream 1's own.
+PlanResult plan_run(const std::vector<Stream>& streams, const U& first, const U& pos, const std::vector<Range>& ranges,
+                    uint32_t bound = kAll, uint32_t len_as = 0) {
+  B in;
+  std::vector<uint64_t> off;
+  U len, rs, lo, ln;
+  for (const Stream& s : streams) {
+    off.push_back(in.size());
+    len.push_back((uint32_t)s.bytes.size());
+    in.insert(in.end(), s.bytes.begin(), s.bytes.end());
+  }
+  if (len_as) len[1] = len_as;
+  for (const Range& r : ranges) {
+    rs.push_back(r.s);
+    lo.push_back(r.lo);
+    ln.push_back(r.len);
+  }
+  const uint32_t n = (uint32_t)streams.size(), k = (uint32_t)ranges.size();
+  EXPECT(first.size() == n + 1);
+  auto d_in = exact(in);
+  auto d_off = exact(off);
+  auto d_len = exact(len);
+  auto d_first = exact(first);
+  auto d_pos = exact(pos);
+  auto d_rs = exact(rs);
+  auto d_lo = exact(lo);
+  auto d_ln = exact(ln);
+  auto o_first = exact(U(k, kGuard));
+  auto o_count = exact(U(k, kGuard));
+  auto o_status = exact(std::vector<int32_t>(k, -1));
+  PlanResult r;
+  r.total = 77;
+  r.st = smm_range_plan(d_in.get(), d_off.get(), d_len.get(), n, d_first.get(), d_pos.get(), (uint32_t)pos.size(),
+                        d_rs.get(), d_lo.get(), d_ln.get(), k, bound, o_first.get(), o_count.get(), o_status.get(), &r.total);
+  r.first.assign(o_first.get(), o_first.get() + k);
+  r.count.assign(o_count.get(), o_count.get() + k);
+  r.status.assign(o_status.get(), o_status.get() + k);
+  // every output pointer may be NULL: the same return
+  EXPECT(smm_range_plan(d_in.get(), d_off.get(), d_len.get(), n, d_first.get(), d_pos.get(), (uint32_t)pos.size(),
+                        d_rs.get(), d_lo.get(), d_ln.get(), k, bound, nullptr, nullptr, nullptr, nullptr) == r.st);
+  return r;
+}
+
+void range_cases() {
+  const uint32_t K = 65536, D3 = 196600, A = SM_ERR_ARGUMENT;
+  typedef std::vector<int32_t> S;
+  EXPECT(smm_range_fragment_count(65535, 2) == 2 && smm_range_fragment_count(65536, 65536) == 1);
+  EXPECT(smm_range_fragment_count(0xffffffffu, 2) == 2 && smm_range_fragment_count(0, 0xffffffffu) == 65536);
+  EXPECT(smm_range_fragment_count(0, 0) == 0 && smm_range_fragment_count(12345, 0) == 0 && smm_range_fragment_count(0xffffffffu, 0) == 0);
+  EXPECT(smm_range_fragment_count(0, 1) == 1 && smm_range_fragment_count(0, K) == 1 && smm_range_fragment_count(0, K + 1) == 2);
+  EXPECT(smm_range_fragment_count(0xffffffffu, 0xffffffffu) == 65537);
+  EXPECT(smm_range_scratch_bytes(1, 17) >= 2 * K && smm_range_scratch_bytes(1, 17) < 3 * K);
+  EXPECT(smm_range_scratch_bytes(10, 3) >= 3 * K && smm_range_scratch_bytes(10, 3) < 4 * K);
+  EXPECT(smm_range_scratch_bytes(0, 0) >= K && smm_range_scratch_bytes(3, 9) - smm_range_scratch_bytes(3, 5) > K);
+  {  // the placement: a 3-fragment stream with D = 131,073, range (1, 131,072)
+    const smm::Place p0 = smm::fragment_place(131073, 0, 3, 1, 131072), p1 = smm::fragment_place(131073, 1, 3, 1, 131072),
+                     p2 = smm::fragment_place(131073, 2, 3, 1, 131072);
+    EXPECT(p0.edge == 1 && p0.src == 1 && p0.n == 65535 && p0.dst == 0);
+    EXPECT(p1.edge == 0 && p1.n == K && p1.dst == 65535);
+    EXPECT(p2.edge == 1 && p2.src == 0 && p2.n == 1 && p2.dst == 131071);
+    EXPECT(smm::range_edges(131073, 3, 0, 3, 1, 131072) == 2 && smm::edge_which(131073, 3, 0, 2, 1, 131072) == 1);
+    EXPECT(smm::range_edges(131073, 3, 0, 3, 0, 131073) == 1 && smm::range_edges(131073, 3, 0, 2, 0, 131072) == 0);
+    EXPECT(smm::range_edges(131073, 3, 1, 2, K, K + 1) == 1);  // the short last fragment, even whole: an edge slot
+    EXPECT(smm::range_edges(131072, 2, 0, 2, 0, 131072) == 0 && smm::range_edges(131073, 3, 0, 1, 5, 7) == 1);
+    EXPECT(smm::edge_which(131073, 3, 0, 1, 0, K + 5) == 0);   // the first fragment direct: the last takes slot 0
+  }
+  // a short stream (1 entry), a three-fragment stream, an empty stream (0 entries), a two-fragment one
+  const std::vector<Stream> base = {make(100, 60, 0), make(D3, 300, 0), make(0, 1, 0), make(65537, 90, 0)};
+  const U first = {0, 1, 4, 4, 6};
+  const U pos = {1, 3, 100, 200, 3, 89};
+  const std::vector<Range> all = {{1, 0, D3}, {1, 65535, 2}, {1, K, K}, {0, 10, 90}, {3, K, 1}, {1, D3 - 1, 1}, {3, 0, 65537}};
+  {
+    const PlanResult r = plan_run(base, first, pos, all);
+    EXPECT(r.st == SM_OK && r.total == 3 + 2 + 1 + 1 + 1 + 1 + 2);
+    EXPECT(r.first == (U{0, 0, 1, 0, 1, 2, 0}) && r.count == (U{3, 2, 1, 1, 1, 1, 2}) && r.status == S(7, SM_OK));
+  }
+  // one range per call from here on: {first, count, status}
+  auto one = [&](const std::vector<Stream>& v, const U& f, const U& p, Range g, uint32_t wf, uint32_t wc, int32_t ws,
+                 uint32_t len_as = 0) {
+    const PlanResult r = plan_run(v, f, p, {g}, kAll, len_as);
+    EXPECT(r.st == SM_OK && r.first == U{wf} && r.count == U{wc} && r.status == S{ws} && r.total == wc);
+  };
+  {  // hostile frag_first: decreasing; past nentries; wild words of streams the range does not name
+    U f = {0, 4, 1, 4, 6};
+    one(base, f, pos, {1, 0, 10}, 0, 0, A);
+    one(base, f, pos, {0, 0, 10}, 0, 0, A);  // (entries [0, 4) of a stream that declares 100)
+    one(base, f, pos, {3, K, 1}, 1, 1, SM_OK);
+    f = {0, 1, 4, 4, 7};
+    one(base, f, pos, {3, K, 1}, 0, 0, A);
+    one(base, f, pos, {1, K, 1}, 1, 1, SM_OK);
+    f = {0xfffffff0u, 1, 4, 0xffffffffu, 0};
+    one(base, f, pos, {1, K, 1}, 1, 1, SM_OK);
+    one(base, f, pos, {0, 0, 1}, 0, 0, A);
+    one(base, f, pos, {3, 0, 1}, 0, 0, A);
+    f = {0, 1, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+    one(base, f, pos, {1, 0, 1}, 0, 0, A);
+  }
+  {  // positions: zero, decreasing, equal, at and past n, a first position that is not hv
+    U p = pos;
+    p[2] = 0;  // 3, 0, 200
+    one(base, first, p, {1, K, 10}, 1, 1, A);
+    one(base, first, p, {1, 0, 10}, 0, 1, A);        // (fragment 0 ends where fragment 1 starts)
+    one(base, first, p, {1, 2 * K, 10}, 2, 1, SM_OK);  // (the last fragment reads its own entry alone)
+    one(base, first, U{1, 0, 0, 0, 3, 89}, {1, 0, D3}, 0, 3, A);  // zeroed entries: no index was built
+    p = pos;
+    p[2] = 250;  // 3, 250, 200
+    one(base, first, p, {1, 0, 10}, 0, 1, SM_OK);
+    one(base, first, p, {1, K, 10}, 1, 1, A);
+    one(base, first, p, {1, 2 * K, 10}, 2, 1, SM_OK);
+    one(base, first, p, {1, 0, D3}, 0, 3, A);
+    p = pos;
+    p[3] = 100;  // 3, 100, 100
+    one(base, first, p, {1, K, 10}, 1, 1, A);
+    one(base, first, p, {1, 0, 10}, 0, 1, SM_OK);
+    one(base, first, p, {1, 2 * K, 10}, 2, 1, SM_OK);
+    p[3] = 300;  // at n
+    one(base, first, p, {1, 2 * K, 10}, 2, 1, A);
+    one(base, first, p, {1, K, 10}, 1, 1, SM_OK);
+    p[3] = 299;
+    one(base, first, p, {1, 2 * K, 10}, 2, 1, SM_OK);
+    p[3] = 0xffffffffu;
+    one(base, first, p, {1, 2 * K, 10}, 2, 1, A);
+    one(base, first, p, {1, K, 10}, 1, 1, A);
+    one(base, first, p, {1, 0, 10}, 0, 1, SM_OK);
+    p = pos;
+    p[1] = 2;  // not hv
+    one(base, first, p, {1, 0, 10}, 0, 1, A);
+    one(base, first, p, {1, K, 10}, 1, 1, SM_OK);
+    p[1] = 4;
+    one(base, first, p, {1, 0, 10}, 0, 1, A);
+    p = pos;
+    p[0] = 0;  // the short stream's one entry
+    one(base, first, p, {0, 0, 100}, 0, 1, A);
+    p[0] = 1;
+    one(base, first, p, {0, 0, 100}, 0, 1, SM_OK);
+    p[1] = 1;  // a position below hv in a later fragment
+    p[2] = 2;
+    one(base, first, p, {1, K, 10}, 1, 1, A);
+  }
+  {  // a count mismatch, either way (the neighbour keeps its own count)
+    U f = {0, 1, 3, 3, 5}, p = {1, 3, 100, 3, 89};
+    one(base, f, p, {1, 0, 10}, 0, 0, A);
+    one(base, f, p, {3, 0, 10}, 0, 1, SM_OK);
+    f = {0, 1, 5, 5, 7};
+    p = {1, 3, 100, 200, 250, 3, 89};
+    one(base, f, p, {1, 0, 10}, 0, 0, A);
+    one(base, f, p, {3, 0, 10}, 0, 1, SM_OK);
+  }
+  // lo + len past D, and past 2^32
+  one(base, first, pos, {1, D3 - 1, 2}, 0, 0, A);
+  one(base, first, pos, {1, D3, 1}, 0, 0, A);
+  one(base, first, pos, {1, 0, D3 + 1}, 0, 0, A);
+  one(base, first, pos, {1, 0xffffffffu, 2}, 0, 0, A);
+  one(base, first, pos, {1, 1, 0xffffffffu}, 0, 0, A);
+  one(base, first, pos, {1, 0xffffffffu, 0xffffffffu}, 0, 0, A);
+  one(base, first, pos, {2, 0, 1}, 0, 0, A);   // D = 0 holds no byte
+  one(base, first, pos, {4, 0, 1}, 0, 0, A);   // the stream number is nstreams
+  one(base, first, pos, {kAll, 0, 1}, 0, 0, A);
+  {  // len == 0: SM_OK whatever else holds, nothing read
+    std::vector<Stream> v = base;
+    v[1].bytes = {0x85, 0x80};  // a varint that does not end
+    one(v, first, pos, {1, 0, 1}, 0, 0, A);
+    one(v, first, pos, {1, 0, 0}, 0, 0, SM_OK);
+    one(v, first, pos, {1, 0xffffffffu, 0}, 0, 0, SM_OK);
+    one(v, first, pos, {99, 5, 0}, 0, 0, SM_OK);
+    one(base, U{9, 8, 7, 6, 5}, pos, {1, 7, 0}, 0, 0, SM_OK);
+    v[1].bytes = {0xff, 0xff, 0xff, 0xff, 0x10, 0, 0, 0};
+    one(v, first, pos, {1, 0, 1}, 0, 0, A);
+    v[1].bytes.clear();
+    one(v, first, pos, {1, 0, 1}, 0, 0, A);
+    // a length that is an error mark: nothing of the stream is read (its three bytes would parse)
+    v[1].bytes = {0x85, 0x80, 0x0c};
+    one(v, first, pos, {1, 0, 1}, 0, 0, A, 0xfff00000u);
+    one(v, first, pos, {1, 0, 0}, 0, 0, SM_OK, 0xfff00000u);
+  }
+  {  // the bound: one below the need, the need
+    PlanResult r = plan_run(base, first, pos, all, 10);
+    EXPECT(r.st == SM_BUFFER_TOO_SMALL && r.total == 11 && r.status == S(7, A) && r.count == (U{3, 2, 1, 1, 1, 1, 2}));
+    r = plan_run(base, first, pos, all, 11);
+    EXPECT(r.st == SM_OK && r.total == 11 && r.status == S(7, SM_OK));
+    r = plan_run(base, first, pos, {{1, 0, 1}, {1, 5, 0}}, 0);  // (an empty range's status too)
+    EXPECT(r.st == SM_BUFFER_TOO_SMALL && r.total == 1 && r.status == S(2, A));
+    r = plan_run(base, first, pos, {{1, 5, 0}, {9, 0, 1}}, 0);  // nothing to decode fits a bound of 0
+    EXPECT(r.st == SM_OK && r.total == 0 && r.status == (S{SM_OK, A}));
+  }
+  {  // no ranges; NULL inputs
+    uint64_t total = 5;
+    EXPECT(smm_range_plan(nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr,
+                          nullptr, nullptr, &total) == SM_OK && total == 0);
+    const uint32_t z = 0;
+    EXPECT(smm_range_plan(nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, &z, &z, &z, 1, 0, nullptr, nullptr, nullptr,
+                          &total) == SM_ERR_ARGUMENT);
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -348,6 +560,7 @@ int main() {
     EXPECT(smm_index_check(d_in.get(), &off, &len, 1, 3, &cap, f, nullptr, &idx) == SM_ERR_ARGUMENT);
   }
   index_cases();
+  range_cases();
   if (failures) {
     fprintf(stderr, "smm_host_check: %d failure(s)\n", failures);
     return 1;

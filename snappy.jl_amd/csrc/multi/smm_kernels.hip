@@ -22,18 +22,6 @@ using smc::sat32;
 
 constexpr uint32_t kThreads = 256;
 
-// the stream that owns slot j: the largest s < n with first[s] <= j (first: an exclusive scan from
-// 0, n + 1 entries, j < first[n]) -- a stream with no slots is never the largest
-__device__ inline uint32_t owner(const uint32_t* first, uint32_t n, uint32_t j) {
-  uint32_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (first[mid] <= j) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 inline uint32_t blocks_for(uint32_t n) { return (n + kThreads - 1) / kThreads; }
 
 }  // namespace

@@ -202,6 +202,19 @@ inline size_t scratch_bytes(size_t n, size_t m) {
 }
 
 #if defined(__HIPCC__)
+// the stream (smm_kernels.hip) or the range (smm_range.hip) that owns slot j: the largest s < n with
+// first[s] <= j (first: an exclusive scan from 0, n + 1 entries, j < first[n]) -- one with no slots
+// is never the largest
+__device__ inline uint32_t owner(const uint32_t* first, uint32_t n, uint32_t j) {
+  uint32_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (first[mid] <= j) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
 // ---- launchers (smm_kernels.hip); all pointers are device pointers -----------------------------
 struct CompressPlan {
   const uint8_t* in;

@@ -6,9 +6,13 @@ libsnappy_mi355x_multi.so, the companion of libsnappy_mi355x.so.
     index_streams(streams)                  -> (frag_first, frag_pos, built): the index of streams
                                                that came without one, built on the GPU
 
+    uncompress_stream_ranges(streams, index, ranges) -> the bytes of each (stream, lo, len), decoding
+                                               only the 64 KiB fragments the ranges touch
+
 and, on torch tensors resident in HBM: compress_streams_device, uncompress_streams_device (no host
-synchronisation), index_streams_device, last_indexed.  index_streams_host runs the same rule on the
-CPU.
+synchronisation), index_streams_device, uncompress_stream_ranges_device, last_indexed.
+index_streams_host runs the index rule on the CPU, range_plan the ranged decode's plan
+(include/snappy_mi355x_multi_range.h).
 
 A stream of at most 64 KiB is what compress_batch gives, a longer one what compress gives; the
 index (frag_first, frag_pos) names every 64 KiB fragment's offset in its stream, and with it the
@@ -18,12 +22,13 @@ never correctness (the stream is then decoded in stream order).
 The package imports without this library; it is loaded on the first call here.  No CPU fallback:
 every codec call needs both HIP libraries and a device.
 """
+import ctypes
 import os
 
 import numpy as np
 
 from . import HERE, MODES, SnappyError, _capacities, _mode, pack_blocks, slot_offsets
-from ._binding import MULTI, check, collect, context_cache, device_caller, exclusive_scan, load
+from ._binding import MULTI, MULTI_RANGE, check, collect, context_cache, device_caller, exclusive_scan, load
 
 LIB_PATH = os.path.join(HERE, "libsnappy_mi355x_multi.so")
 BLOCK = 65536
@@ -31,6 +36,7 @@ MAX_INPUT = 0x7FFFFFFF
 INDEX_STAGE = 4096  # kIndexStage (csrc/multi/smm_plan.h): the bytes the index walk stages per piece
 
 MULTI_ABI_SYMBOLS = tuple(MULTI)  # exported symbols of include/snappy_mi355x_multi.h (checked by tests/test_multi_host.py)
+RANGE_ABI_SYMBOLS = tuple(MULTI_RANGE)  # ... of include/snappy_mi355x_multi_range.h (tests/test_multi_range_host.py)
 
 _lib = None
 
@@ -43,7 +49,7 @@ def lib():
     """Load libsnappy_mi355x_multi.so (raises OSError if it was not built)."""
     global _lib
     if _lib is None:
-        _lib = load(LIB_PATH, MULTI, "libsnappy_mi355x_multi.so not built (run __graft_entry__.build())")
+        _lib = load(LIB_PATH, {**MULTI, **MULTI_RANGE}, "libsnappy_mi355x_multi.so not built (run __graft_entry__.build())")
     return _lib
 
 
@@ -246,6 +252,81 @@ def uncompress_streams(streams, index=None, capacities=None, device=0):
     return collect(out, out_off, out_len, status), status
 
 
+# ---- ranged decode (include/snappy_mi355x_multi_range.h) ----------------------------------------------
+
+def range_fragment_count(lo, length):
+    """The 64 KiB fragments that bytes [lo, lo + length) of a stream's content touch; 0 for length 0."""
+    return lib().smm_range_fragment_count(int(lo), int(length))
+
+
+def range_scratch_bytes(nranges, max_range_fragments):
+    return lib().smm_range_scratch_bytes(int(nranges), int(max_range_fragments))
+
+
+def _range_arrays(streams, index, ranges):
+    """The host arrays of a ranged call: (buf, in_off, in_len, first, pos, range_stream, lo, len); buf and
+    pos hold an element at the least."""
+    buf, in_off, in_len = pack_blocks(streams)
+    first = np.ascontiguousarray(index[0], dtype=np.uint32)
+    pos = np.ascontiguousarray(index[1], dtype=np.uint32)
+    if first.size != len(streams) + 1:
+        raise ValueError("frag_first does not fit the streams")
+    r = np.array([tuple(int(x) for x in t) for t in ranges], dtype=np.uint32).reshape(-1, 3)
+    cols = [np.ascontiguousarray(r[:, k]) for k in range(3)]
+    return (buf if buf.size else np.zeros(1, np.uint8), in_off, in_len, first,
+            pos if pos.size else np.zeros(1, np.uint32), *cols)
+
+
+def range_plan(streams, index, ranges, max_range_fragments=None, nentries=None):
+    """The plan of uncompress_stream_ranges on the host (smm_range_plan: the device's rules, nothing
+    decoded): (first, count, status, total) -- per range the touched fragments [first, first + count)
+    of its stream and what is known before any of them is decoded (0, or 33), and the slots of all
+    ranges.  index = (frag_first, frag_pos), of which nentries entries (default: all) may be read;
+    over max_range_fragments (default: no bound) every status is 33."""
+    buf, in_off, in_len, first, pos, rs, lo, ln = _range_arrays(streams, index, ranges)
+    k = rs.size
+    if nentries is None:
+        nentries = np.asarray(index[1]).size
+    if int(nentries) > np.asarray(index[1]).size:
+        raise ValueError("frag_pos is shorter than nentries")
+    bound = 0xFFFFFFFF if max_range_fragments is None else int(max_range_fragments)
+    f = np.zeros(max(k, 1), np.uint32)
+    c = np.zeros(max(k, 1), np.uint32)
+    st = np.zeros(max(k, 1), np.int32)
+    total = ctypes.c_uint64(0)
+    rc = lib().smm_range_plan(buf.ctypes.data, _addr(in_off), _addr(in_len), len(streams), first.ctypes.data,
+                              pos.ctypes.data, int(nentries), _addr(rs), _addr(lo), _addr(ln), k, bound, f.ctypes.data,
+                              c.ctypes.data, st.ctypes.data, ctypes.byref(total))
+    if rc not in (0, 2):  # (2: over the bound, which the statuses say)
+        raise SnappyError(rc)
+    return f[:k], c[:k], st[:k], int(total.value)
+
+
+def uncompress_stream_ranges(streams, index, ranges, device=0):
+    """Bytes [lo, lo + len) of the decoded content of streams[stream] for every (stream, lo, len) of
+    `ranges`, in one call on the GPU that decodes only the 64 KiB fragments the ranges touch; a list
+    of bytes.  index: the (frag_first, frag_pos) of exactly these streams, from compress_streams or
+    index_streams.  A stream that no range names is not read.  Raises SnappyError with the first
+    failing range's status: there is no fallback, and a stream whose index could not be built is
+    decoded whole (uncompress_streams)."""
+    buf, in_off, in_len, first, pos, rs, lo, ln = _range_arrays(streams, index, ranges)
+    k = rs.size
+    if k == 0:
+        return []
+    if pos.size < int(first[-1]):
+        raise ValueError("index does not fit the streams")
+    out_off = exclusive_scan(ln, total=True)
+    out = np.empty(max(int(out_off[-1]), 1), dtype=np.uint8)
+    out_len = np.zeros(k, np.uint32)
+    status = np.zeros(k, np.int32)
+    check(lib().smm_uncompress_ranges(context(device), buf.ctypes.data, _addr(in_off), _addr(in_len), len(streams),
+                                      first.ctypes.data, pos.ctypes.data, rs.ctypes.data, lo.ctypes.data, ln.ctypes.data, k,
+                                      out.ctypes.data, out_off.ctypes.data, out_len.ctypes.data, status.ctypes.data),
+          SnappyError)
+    _raise_first(status)
+    return collect(out, out_off, out_len)
+
+
 # ---- device API (torch tensors resident in HBM; asynchronous on `stream`) ---------------------
 
 _device = device_caller(lib, context, SnappyError)
@@ -276,6 +357,18 @@ def index_streams_device(d_in, d_in_off, d_in_len, max_fragments, d_frag_first, 
             d_out_cap, d_frag_first, d_frag_pos, d_built, d_status)
 
 
+def uncompress_stream_ranges_device(d_in, d_in_off, d_in_len, d_frag_first, d_frag_pos, d_range_stream, d_lo, d_len,
+                                    max_range_fragments, d_out, d_out_off, d_out_len, d_status, nentries=None,
+                                    stream=None, device=None):
+    """smm_uncompress_ranges_device (tensor types as in compress_streams_device; d_range_stream, d_lo,
+    d_len, d_out_len and d_status int32 with an entry per range, d_out_off int64).  nentries: the
+    entries of d_frag_pos (default: all of the tensor).  max_range_fragments: at least the sum of
+    range_fragment_count over the ranges.  Nothing is synchronised."""
+    _device("smm_uncompress_ranges_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), d_frag_first,
+            d_frag_pos, d_frag_pos.numel() if nentries is None else int(nentries), d_range_stream, d_lo, d_len,
+            d_lo.numel(), int(max_range_fragments), d_out, d_out_off, d_out_len, d_status)
+
+
 def last_indexed(device=0):
     """Diagnostic: how many streams the device's last uncompress call decoded by fragments (waits
     for the device); -1 before the first call."""
@@ -284,4 +377,6 @@ def last_indexed(device=0):
 
 __all__ = ["MULTI_ABI_SYMBOLS", "MODES", "compress_streams", "uncompress_streams", "compress_streams_device",
            "uncompress_streams_device", "index_streams", "index_streams_host", "index_streams_device",
-           "index_bound", "INDEX_STAGE", "fragment_count", "scratch_bytes", "frag_first_of", "index_check", "last_indexed"]
+           "index_bound", "INDEX_STAGE", "fragment_count", "scratch_bytes", "frag_first_of", "index_check", "last_indexed",
+           "RANGE_ABI_SYMBOLS", "range_fragment_count", "range_scratch_bytes", "range_plan", "uncompress_stream_ranges",
+           "uncompress_stream_ranges_device"]
