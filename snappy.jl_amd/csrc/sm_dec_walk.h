@@ -12,6 +12,18 @@ namespace sm {
 typedef uint16_t __attribute__((aligned(1))) du16u;
 typedef uint32_t __attribute__((aligned(1))) du32u;
 typedef uint64_t __attribute__((aligned(1))) du64u;
+typedef uint32_t __attribute__((ext_vector_type(4), aligned(1))) du128u;
+
+// 16 bytes at any address: one global_load_dwordx4 / global_store_dwordx4
+__device__ inline uint4 ld16u(const uint8_t* p) {
+  const du128u v = *reinterpret_cast<const du128u*>(p);
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ inline void st16u(uint8_t* p, uint4 v) {
+  du128u t;
+  t.x = v.x, t.y = v.y, t.z = v.z, t.w = v.w;
+  *reinterpret_cast<du128u*>(p) = t;
+}
 
 constexpr uint32_t kMaxBatchLit = 200;  // longer literals stop a window walk (size 255)
 constexpr int kWalkLevels = 5;  // tables J0..J4 in LDS; J5 (bit 5 of a lane's chain index) = J4 o J4

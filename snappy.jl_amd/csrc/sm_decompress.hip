@@ -22,7 +22,9 @@
 //  * tags execute lane-parallel in 16-byte pieces into a linear LDS output window (sources in
 //    the window or, older, in HBM), the few copies whose source overlaps the batch's own
 //    output (or offset < 16) in stream order after them; whole 16-byte blocks go to HBM when
-//    a batch ends.
+//    a batch ends;
+//  * the first piece of every HBM source is loaded before the rest of the batch runs, and the next
+//    batch's tag walk stands between that load and its use (it needs only where this batch ends).
 // Literals longer than 64 bytes are copied by the whole wave.
 // Streams declaring > 64 KiB use a simple per-tag engine (also straight into HBM).
 //
@@ -166,9 +168,7 @@ __device__ inline void win_flush(uint8_t* out, const uint8_t* win, uint32_t wbas
   const uint32_t nb = (to - from) >> 4;
   for (uint32_t k = lane; k < nb; k += kWave) {
     const uint32_t x = from + 16 * k;
-    const uint4 v = *reinterpret_cast<const uint4*>(win + (x - wbase));
-    *reinterpret_cast<du64u*>(out + x) = ((uint64_t)v.y << 32) | v.x;
-    *reinterpret_cast<du64u*>(out + x + 8) = ((uint64_t)v.w << 32) | v.z;
+    st16u(out + x, *reinterpret_cast<const uint4*>(win + (x - wbase)));
   }
   from += nb << 4;
   if (lane < to - from) out[from + lane] = win[from + lane - wbase];
@@ -208,7 +208,9 @@ __device__ int32_t decode_stream_batch(const uint8_t* __restrict__ in, uint32_t 
   win_init(win, lane);
   const uint32_t winA = lds_addr(win), ringA = lds_addr(ring);
   const bool in_al = (((uintptr_t)in) & 3) == 0;
-  const int64_t Nm1 = min((int64_t)N - 1, (int64_t)ip_end);  // parse limit
+  // parse limit: tags start below min(N - 1, ip_end) (nothing for N = 0), a 32-bit value, so that the
+  // uniform tests against it are scalar compares (a 64-bit `<` has no scalar form)
+  const uint32_t Nm1 = min(N ? N - 1 : 0u, ip_end);
 
   // every batch consumes input (ip strictly increases): more than N batches means the wave is
   // not whole (a caller that split it) -- a status, never a hang
@@ -216,25 +218,44 @@ __device__ int32_t decode_stream_batch(const uint8_t* __restrict__ in, uint32_t 
   // streams of 2 GiB and more, and declared lengths within 64 KiB of 2^32, take every batch
   // through the full checks (no reasoning about wrap: a batch makes at most 64 * 200 bytes)
   const bool narrow = N < 0x80000000u && size <= 0xffff0000u;
-  while ((int64_t)ip < Nm1 && (kWhole || op < op_lim)) {
+  // the ring slot after the ring's three: pre1 into the ring, pre2 takes its place, and the slot
+  // after that is asked for (fetch_pre2) once nothing freshly issued can be waited on
+  auto ring_advance = [&]() {
+    ring_put(ring, wb + 768, pre1, lane);
+    pre1 = pre2;
+    asm volatile("" : "+v"(pre1));  // (the move here: after the load into pre2 it would wait for that load)
+    wb += 256;
+    issue_pre2 = true;  // [wb+1024, wb+1280)
+  };
+  // (a whole slot inside the stream at a 4-aligned base: one plain load, the test uniform)
+  auto fetch_pre2 = [&]() {
+    pre2 = (in_al && wb + 1280 <= N) ? reinterpret_cast<const uint32_t*>(in + wb + 1024)[lane]
+                                     : load_word(in, N, wb + 1024 + 4 * lane);
+    issue_pre2 = false;
+  };
+  // The walk of the batch at ip: its tag count and, in lane t, tag t's window position and size.
+  // A batch that will be followed by another batch walks that one while its own far copy sources
+  // load (below), and hands the walk to the next trip: `walked` says that it is in hand.
+  bool walked = false;
+  uint32_t ntok = 0, cpos = 0, csz = 0, sizes = 0;
+  while (ip < Nm1 && (kWhole || op < op_lim)) {
     if (__builtin_expect(--guard == 0, 0)) return kErrDevice;
-    if (ip >= wb + 256) {
-      if (__builtin_expect(ip < wb + 512, 1)) {
-        ring_put(ring, wb + 768, pre1, lane);
-        pre1 = pre2;
-        wb += 256;
-        issue_pre2 = true;  // [wb+1024, wb+1280) loads after this batch
-      } else {  // jumped (long literal): refill
-        wb = ip & ~255u;
-        ring_fill(in, N, wb, ring, pre1, pre2, lane);
-        issue_pre2 = false;
-      }
-    }
     // the window [ip, ip+256) (inside the ring: ip < wb+256; a batch's literals end before
     // ip+256+200 < wb+768)
-    const uint32_t wlim = (int64_t)(ip + 256) < Nm1 ? ip + 256 : (uint32_t)Nm1;
-    uint32_t cpos, csz, sizes;
-    const uint32_t ntok = walk_window(ring_get8(ring, ip + 4 * lane), wlim - ip, jt, lane, cpos, csz, sizes);
+    const uint32_t wlim = ip + 256 < Nm1 ? ip + 256 : Nm1;
+    if (!walked) {
+      if (ip >= wb + 256) {
+        if (__builtin_expect(ip < wb + 512, 1)) {
+          ring_advance();  // (its load goes out after this batch's checks)
+        } else {  // jumped (long literal): refill
+          wb = ip & ~255u;
+          ring_fill(in, N, wb, ring, pre1, pre2, lane);
+          issue_pre2 = false;
+        }
+      }
+      ntok = walk_window(ring_get8(ring, ip + 4 * lane), wlim - ip, jt, lane, cpos, csz, sizes);
+    }
+    walked = false;
     uint32_t tpos = 0, ipw = ip, tnext = 0;
     bool big = false;
     if (__builtin_expect(ntok != 0, 1)) {
@@ -338,10 +359,34 @@ __device__ int32_t decode_stream_batch(const uint8_t* __restrict__ in, uint32_t 
       const uint64_t copym = copya & all;
       const uint64_t longm = ballot(litlen > 64) & ~copym & all;
       const uint64_t gm = ballot(slo < wbase) & copym;
-      const bool gsrc = inverse_ballot(gm);
       uint64_t done = longm | ~all;
+      // the tags one round runs (below), and those of them whose source is in HBM
+      const uint64_t rm = ~done & (~copym | (ballot(shi <= O0) & ballot(offset >= 16)));
+      const uint64_t fm = gm & rm;
+      const uint32_t L = iscopy ? len : litlen;
+      const uint32_t da = winA + (opt - wbase);
+      const uint8_t* gs = out + slo;
+
+      // Another batch follows this one in the ring's reach: its walk needs the position after this
+      // batch (fixed above, cap included) and the input ring, nothing this batch's copies make, so
+      // it runs between the far loads and their use.  Not when a big literal follows, the parse or
+      // the fragment ends here, or the ring must be refilled: then the loop top walks as ever.
+      const bool early = !big && ipw < Nm1 && (kWhole || O0 + X < op_lim) && ipw < wb + 512;
+      // The ring moves before the far loads go out, and the slot asked for with it: the wait for the
+      // far pieces is then a wait for the youngest loads, and covers no fresh prefetch.  (The slot
+      // given up holds bytes before wb <= ip; this batch's literals read at and after ip.)
+      if (issue_pre2) fetch_pre2();
+      if (early && ipw >= wb + 256) {
+        ring_advance();
+        fetch_pre2();
+      }
+
       // HBM sources: this wave's earlier flushes (and big literals) must have landed
       if (gm) __threadfence_block();
+      // the far lanes' first 16-byte piece, in flight over the rest of the round and the walk (two
+      // or three pieces ahead cost registers -- 6 waves per SIMD -- and measured slower)
+      uint4 fv = make_uint4(0, 0, 0, 0);
+      if (inverse_ballot(fm)) fv = ld16u(gs);
 
       // long literals (65..200 B, no dependencies, inside the input ring): whole-wave passes
       uint64_t lm = longm;
@@ -360,30 +405,30 @@ __device__ int32_t decode_stream_batch(const uint8_t* __restrict__ in, uint32_t 
       // output byte j - offset = out[slo + j], written by an earlier 16-byte pass.  So every tag
       // reads out[slo + j] (or its literal bytes) in 16-byte pieces.  The writes never touch
       // bytes another ready tag reads.
-      if (__builtin_expect(done != ~0ull, 1)) {
-        const uint64_t rm = ~done & (~copym | (ballot(shi <= O0) & ballot(offset >= 16)));
-        const uint32_t L = iscopy ? len : litlen;
+      // The next batch's walk, while the far pieces arrive (the ring moved above).
+      if (__builtin_expect(early, 1)) {
+        const uint32_t wl2 = ipw + 256 < Nm1 ? ipw + 256 : Nm1;
+        ntok = walk_window(ring_get8(ring, ipw + 4 * lane), wl2 - ipw, jt, lane, cpos, csz, sizes);
+        walked = true;
+      }
+      // The round's pieces, every lane in one pass per 16 bytes: a far lane's first piece is the one
+      // loaded above, its later ones (a copy longer than 16 bytes) a load and its use each.
+      if (__builtin_expect(rm != 0, 1)) {
+        const bool gsrc = inverse_ballot(fm);
         const uint32_t sa = iscopy ? winA + (slo - wbase) : ringA + (lsrc & (kRing - 1));
-        const uint32_t da = winA + (opt - wbase);
-        const uint8_t* gs = out + slo;
 #pragma unroll
         for (uint32_t base = 0; base < 64; base += 16) {
           const uint64_t am = rm & ballot(L > base);
           if (!am) break;
           if (inverse_ballot(am)) {
             uint4 v;
-            if (gsrc) {
-              const du64u* g = reinterpret_cast<const du64u*>(gs + base);
-              const uint64_t a = g[0], b = g[1];
-              v = make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
-            } else {
-              v = lds_get16(sa, base);
-            }
+            if (gsrc) v = base == 0 ? fv : ld16u(gs + base);
+            else v = lds_get16(sa, base);
             lds_or16(da, base, trim16(v, min(L - base, 16u)));
           }
         }
-        done |= rm;
       }
+      done |= rm;
       // The copies left -- their source overlaps earlier tags of this batch, or offset < 16 --
       // run in stream order, one tag at a time, a byte per lane: byte k = S[k mod offset] with S
       // final by then (LDS accesses of a wave are serviced in order).
@@ -409,12 +454,7 @@ __device__ int32_t decode_stream_batch(const uint8_t* __restrict__ in, uint32_t 
       flushed = max(flushed, op & ~15u);
       ip = ipw;
     }
-    if (issue_pre2) {
-      // (a whole slot inside the stream at a 4-aligned base: one plain load, the test uniform)
-      pre2 = (in_al && wb + 1280 <= N) ? reinterpret_cast<const uint32_t*>(in + wb + 1024)[lane]
-                                       : load_word(in, N, wb + 1024 + 4 * lane);
-      issue_pre2 = false;
-    }
+    if (issue_pre2) fetch_pre2();  // (no batch at ip: the ring moved for a big literal alone)
 
     if (__builtin_expect(big && (kWhole || op < op_lim), 0)) {  // (at op_lim the literal opens the next fragment)
       // one literal too long for the batch path (or a wrapped length): straight to HBM
@@ -459,16 +499,9 @@ __device__ int32_t decode_stream_batch(const uint8_t* __restrict__ in, uint32_t 
 #pragma unroll
         for (uint32_t j = 0; j < kLit; ++j) v[j] = s16[k + j * kWave];
 #pragma unroll
-        for (uint32_t j = 0; j < kLit; ++j) {
-          *reinterpret_cast<du64u*>(d + 16 * (k + j * kWave)) = ((uint64_t)v[j].y << 32) | v[j].x;
-          *reinterpret_cast<du64u*>(d + 16 * (k + j * kWave) + 8) = ((uint64_t)v[j].w << 32) | v[j].z;
-        }
+        for (uint32_t j = 0; j < kLit; ++j) st16u(d + 16 * (k + j * kWave), v[j]);
       }
-      for (; k < n16; k += kWave) {
-        uint4 v0 = s16[k];
-        *reinterpret_cast<du64u*>(d + 16 * k) = ((uint64_t)v0.y << 32) | v0.x;
-        *reinterpret_cast<du64u*>(d + 16 * k + 8) = ((uint64_t)v0.w << 32) | v0.z;
-      }
+      for (; k < n16; k += kWave) st16u(d + 16 * k, s16[k]);
       const uint32_t done16 = head + (n16 << 4);
       if (lane < litlen - done16) out[op + done16 + lane] = s[done16 + lane];
       // the window restarts at nb = the 16-byte output boundary at or below op + litlen - kKeep
@@ -510,7 +543,7 @@ __device__ int32_t decode_stream_batch(const uint8_t* __restrict__ in, uint32_t 
 }
 
 #ifndef SM_DEC_OCC
-#define SM_DEC_OCC 7  // waves per SIMD: 62 VGPRs, 5.0 KB LDS per wave (8: no spill either, 1.365 against 1.28 ms)
+#define SM_DEC_OCC 7  // waves per SIMD: 70 VGPRs, 5.0 KB LDS per wave (6: 1.29 against 1.25 ms; 8 would spill)
 #endif
 // one stream of the batch (block b) by one wave
 template <uint32_t kLit = 4>
