@@ -1,4 +1,4 @@
-"""What the four ctypes bindings of this package share (__init__.py, framing.py, multi.py, blocks.py): the
+"""What the five ctypes bindings of this package share (__init__.py, framing.py, multi.py, blocks.py, orc.py): the
 prototype table of each library, the loader and the per-device context cache, the status, stream
 and device rules of the device wrappers, and the layout of a batch in one host buffer.
 
@@ -7,10 +7,12 @@ A prototype is "<return> <arguments>", one letter per C type:
     v void        c const char* (a returned text)     p any other pointer, as an address
     i int         s sm_status / int32_t               u uint32_t     q uint64_t     z size_t
     Z size_t*     U uint32_t*    Q uint64_t*          (results the wrappers pass by reference)
-    C smf_chunks*                S smf_summary* / smb_summary* (one layout)       B smb_chunks*
+    C smf_chunks*                S smf_summary* / smb_summary* / smo_summary* (one layout)
+    B smb_chunks*                O smo_chunks*
 
 tests/test_bindings.py holds every entry against the declaration in include/*.h
-(tests/test_blocks_host.py: the BLOCKS table; tests/test_multi_range_host.py: MULTI_RANGE).
+(tests/test_blocks_host.py: the BLOCKS table; tests/test_orc_host.py: ORC;
+tests/test_multi_range_host.py: MULTI_RANGE).
 """
 import ctypes
 import os
@@ -31,8 +33,13 @@ class BlockChunks(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("pay_off", "pay_len", "ulen")]
 
 
+class OrcChunks(ctypes.Structure):
+    """smo_chunks: four parallel arrays, one entry per chunk."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("pay_off", "pay_len", "ulen", "original")]
+
+
 class Summary(ctypes.Structure):
-    """smf_summary, and smb_summary with the same fields."""
+    """smf_summary, and smb_summary and smo_summary with the same fields."""
     _fields_ = [("total_length", ctypes.c_uint64), ("nchunks", ctypes.c_uint32), ("status", ctypes.c_int32)]
 
 
@@ -40,7 +47,7 @@ CTYPES = {
     "v": None, "c": ctypes.c_char_p, "p": ctypes.c_void_p, "i": ctypes.c_int, "s": ctypes.c_int32,
     "u": ctypes.c_uint32, "q": ctypes.c_uint64, "z": ctypes.c_size_t, "Z": ctypes.POINTER(ctypes.c_size_t),
     "U": ctypes.POINTER(ctypes.c_uint32), "Q": ctypes.POINTER(ctypes.c_uint64), "C": ctypes.POINTER(Chunks),
-    "S": ctypes.POINTER(Summary), "B": ctypes.POINTER(BlockChunks),
+    "S": ctypes.POINTER(Summary), "B": ctypes.POINTER(BlockChunks), "O": ctypes.POINTER(OrcChunks),
 }
 
 RAW = {  # include/snappy_mi355x.h
@@ -166,6 +173,24 @@ BLOCKS = {  # include/snappy_mi355x_blocks.h
     "smb_compress_streams_device": "s pipppuuppppip",
     "smb_compress_streams": "s pipppuppppi",
     "smb_uncompress_streams": "s pipppuppppp",
+}
+
+ORC = {  # include/snappy_mi355x_orc.h
+    "smo_status_message": "c s",
+    "smo_version": "c",
+    "smo_max_length": "z zu",
+    "smo_max_chunks": "q q",
+    "smo_index": "s pzuOuS",
+    "smo_uncompressed_length": "s pzuZ",
+    "smo_streams_plan": "s pppuupupppQQ",
+    "smo_streams_scratch_bytes": "z uuuu",
+    "smo_ctx_create": "p i",
+    "smo_ctx_destroy": "v p",
+    "smo_ctx_last_indexed": "i p",
+    "smo_uncompress_streams_device": "s pupppuuupppppppp",
+    "smo_compress_streams_device": "s pupppuuppppip",
+    "smo_compress_streams": "s pupppuppppi",
+    "smo_uncompress_streams": "s pupppuppppp",
 }
 
 
