@@ -1,4 +1,5 @@
-"""What the five ctypes bindings of this package share (__init__.py, framing.py, multi.py, blocks.py, orc.py): the
+"""What the six ctypes bindings of this package share (__init__.py, framing.py, multi.py, blocks.py, orc.py,
+parquet.py): the
 prototype table of each library, the loader and the per-device context cache, the status, stream
 and device rules of the device wrappers, and the layout of a batch in one host buffer.
 
@@ -7,12 +8,12 @@ A prototype is "<return> <arguments>", one letter per C type:
     v void        c const char* (a returned text)     p any other pointer, as an address
     i int         s sm_status / int32_t               u uint32_t     q uint64_t     z size_t
     Z size_t*     U uint32_t*    Q uint64_t*          (results the wrappers pass by reference)
-    C smf_chunks*                S smf_summary* / smb_summary* / smo_summary* (one layout)
-    B smb_chunks*                O smo_chunks*
+    C smf_chunks*                S smf_summary* / smb_summary* / smo_summary* / smq_summary* (one layout)
+    B smb_chunks*                O smo_chunks*                G smq_pages*
 
 tests/test_bindings.py holds every entry against the declaration in include/*.h
 (tests/test_blocks_host.py: the BLOCKS table; tests/test_orc_host.py: ORC;
-tests/test_multi_range_host.py: MULTI_RANGE).
+tests/test_multi_range_host.py: MULTI_RANGE; tests/test_parquet_host.py: PARQUET).
 """
 import ctypes
 import os
@@ -38,8 +39,16 @@ class OrcChunks(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("pay_off", "pay_len", "ulen", "original")]
 
 
+PAGE_KEYS = ("hdr_off", "hdr_len", "body_len", "usize", "levels", "out_off", "num_values", "type", "encoding", "flags", "crc")
+
+
+class Pages(ctypes.Structure):
+    """smq_pages: eleven parallel arrays, one entry per page."""
+    _fields_ = [(k, ctypes.c_void_p) for k in PAGE_KEYS]
+
+
 class Summary(ctypes.Structure):
-    """smf_summary, and smb_summary and smo_summary with the same fields."""
+    """smf_summary, and smb_summary, smo_summary and smq_summary (npages for nchunks) with the same fields."""
     _fields_ = [("total_length", ctypes.c_uint64), ("nchunks", ctypes.c_uint32), ("status", ctypes.c_int32)]
 
 
@@ -48,6 +57,7 @@ CTYPES = {
     "u": ctypes.c_uint32, "q": ctypes.c_uint64, "z": ctypes.c_size_t, "Z": ctypes.POINTER(ctypes.c_size_t),
     "U": ctypes.POINTER(ctypes.c_uint32), "Q": ctypes.POINTER(ctypes.c_uint64), "C": ctypes.POINTER(Chunks),
     "S": ctypes.POINTER(Summary), "B": ctypes.POINTER(BlockChunks), "O": ctypes.POINTER(OrcChunks),
+    "G": ctypes.POINTER(Pages),
 }
 
 RAW = {  # include/snappy_mi355x.h
@@ -191,6 +201,22 @@ ORC = {  # include/snappy_mi355x_orc.h
     "smo_compress_streams_device": "s pupppuuppppip",
     "smo_compress_streams": "s pupppuppppi",
     "smo_uncompress_streams": "s pupppuppppp",
+}
+
+PARQUET = {  # include/snappy_mi355x_parquet.h
+    "smq_status_message": "c s",
+    "smq_version": "c",
+    "smq_max_pages": "q q",
+    "smq_index": "s pzGuS",
+    "smq_uncompressed_length": "s pzZ",
+    "smq_chunks_plan": "s pppupupppQQ",
+    "smq_chunks_scratch_bytes": "z uuu",
+    "smq_ctx_create": "p i",
+    "smq_ctx_destroy": "v p",
+    "smq_ctx_last_indexed": "i p",
+    "smq_uncompress_chunks_device": "s ppppuuuippppppGpp",
+    "smq_crc32_device": "s ppppupp",
+    "smq_uncompress_chunks": "s ppppuippppp",
 }
 
 

@@ -1,0 +1,220 @@
+// smq_api.hip -- C ABI of the Parquet page library (include/snappy_mi355x_parquet.h) over the multi
+// library's public device calls (libsnappy_mi355x_multi.so, linked by name) and the kernels of
+// smq_kernels.hip and smq_crc.hip.  The host-only entry points live in smq_host.cpp.
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "../../../include/snappy_mi355x_multi.h"
+#include "../common/smc_hip_host.h"
+#include "../common/smc_layout.h"
+#include "smq_chunks.h"
+#include "smq_crc.h"
+#include "smq_format.h"
+#include "smq_internal.h"
+
+#ifndef SMQ_VERSION_STR
+#define SMQ_VERSION_STR "dev"
+#endif
+
+namespace {
+
+struct ChunkCallArrays {  // per chunk, what a host-buffer call hands the device call (ctx->sarg)
+  uint64_t *in_off, *in_len, *out_off, *out_cap, *out_len;
+  int32_t* status;
+  uintptr_t end;
+};
+constexpr ChunkCallArrays carve_chunk_call(uintptr_t base, size_t n) {
+  smc::Carve c{base};
+  ChunkCallArrays m{};
+  m.in_off = c.take<uint64_t>(n);
+  m.in_len = c.take<uint64_t>(n);
+  m.out_off = c.take<uint64_t>(n);
+  m.out_cap = c.take<uint64_t>(n);
+  m.out_len = c.take<uint64_t>(n);
+  m.status = c.take<int32_t>(n);
+  m.end = c.p;
+  return m;
+}
+constexpr size_t chunk_call_bytes(size_t n) { return carve_chunk_call(0, n).end; }
+
+}  // namespace
+
+struct smq_ctx {
+  smm_ctx* smm = nullptr;
+  int device = 0;
+  hipStream_t stream = nullptr;  // the host-buffer call runs on it
+  DevBuf lut;                    // the CRC tables (smq::CrcLut)
+  DevBuf meta;                   // a *_device call's per-slot and per-chunk arrays
+  DevBuf io_in, io_out, sarg;    // the host-buffer call's staging and its own arrays
+  std::mutex mu;                 // serialises the host-buffer entry point
+};
+
+extern "C" {
+
+const char* smq_status_message(sm_status st) {
+  const char* m = smq::host_message(st);
+  return m ? m : sm_status_message(st);
+}
+
+const char* smq_version(void) { return "snappy_mi355x_parquet gfx950 " SMQ_VERSION_STR; }
+
+smq_ctx* smq_ctx_create(int device) {
+  smm_ctx* smm = smm_ctx_create(device);
+  if (!smm) return nullptr;
+  smq_ctx* ctx = new (std::nothrow) smq_ctx();
+  if (!ctx) {
+    smm_ctx_destroy(smm);
+    return nullptr;
+  }
+  ctx->smm = smm;
+  ctx->device = device;
+  bool ok;
+  {
+    DeviceGuard g(device);
+    ok = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) == hipSuccess;
+    if (!ok) ctx->stream = nullptr;
+    std::unique_ptr<smq::CrcLut> lut(new (std::nothrow) smq::CrcLut);
+    ok = ok && lut && ctx->lut.ensure(sizeof(smq::CrcLut)) == hipSuccess;
+    if (ok) {
+      smq::build_crc_lut(lut.get());
+      ok = hipMemcpy(ctx->lut.p, lut.get(), sizeof(smq::CrcLut), hipMemcpyHostToDevice) == hipSuccess;
+    }
+  }
+  if (!ok) {
+    smq_ctx_destroy(ctx);
+    return nullptr;
+  }
+  return ctx;
+}
+
+void smq_ctx_destroy(smq_ctx* ctx) {
+  if (!ctx) return;
+  {
+    DeviceGuard g(ctx->device);
+    (void)hipDeviceSynchronize();  // (the *_device calls ran on the callers' streams)
+    for (DevBuf* b : {&ctx->lut, &ctx->meta, &ctx->io_in, &ctx->io_out, &ctx->sarg}) b->release();
+    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+  }
+  smm_ctx_destroy(ctx->smm);
+  delete ctx;
+}
+
+int smq_ctx_last_indexed(smq_ctx* ctx) { return ctx ? smm_ctx_last_indexed(ctx->smm) : -1; }
+
+// Launch sequence: the counting walk, the scan, the storing walk (and the scan of the CRC
+// segments); the multi library's index builder and its decoder, once each over all slots (a slot
+// without a compressed section is an empty one to them); the copies, the CRC segments, the slots'
+// verdicts, the chunks' results.
+sm_status smq_uncompress_chunks_device(smq_ctx* ctx, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                       uint32_t nchunks, uint32_t max_pages, uint32_t max_fragments, int verify_crc,
+                                       uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap,
+                                       uint64_t* d_out_len, int32_t* d_status, uint32_t* d_page_first,
+                                       const smq_pages* d_pages, int32_t* d_page_status, void* stream) {
+  if (!ctx || nchunks > smq::kMaxChunks || max_pages > smq::kMaxChunks) return SM_ERR_ARGUMENT;
+  if (!d_page_first != !d_page_status) return SM_ERR_ARGUMENT;
+  if (d_pages && !smq::valid_pages(*d_pages)) return SM_ERR_ARGUMENT;
+  if (nchunks == 0) return SM_OK;
+  if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status) return SM_ERR_ARGUMENT;
+  hipStream_t s = (hipStream_t)stream;
+  DeviceGuard g(ctx->device);
+  const uint32_t m = max_pages;
+  SM_CHECK(ctx->meta.ensure(smq::decode_chunks_bytes(nchunks, m, max_fragments)));
+  const smq::DecodeChunksArgs a{d_in,      d_in_off,  d_in_len,  nchunks,  m,            verify_crc ? 1u : 0u,
+                                d_out,     d_out_off, d_out_cap, d_out_len, d_status,    d_page_first,
+                                d_page_status, d_pages != nullptr, d_pages ? *d_pages : smq_pages{},
+                                smq::carve_decode_chunks((uint8_t*)ctx->meta.p, nchunks, m, max_fragments)};
+  SM_CHECK(smq::launch_decode_plan(a, s));
+  if (m) {
+    // the index of every compressed section that a block compressor wrote (over max_fragments: the
+    // empty index), then the decode, by fragments where the index allows.  With no fragments allowed
+    // the index would be the empty one, which decodes as no index does: it is not built.
+    const bool index = max_fragments != 0;
+    if (index)
+      SM_PASS(smm_index_device(ctx->smm, d_in, a.s.in_off, a.s.in_len, m, max_fragments, a.s.cap, a.s.frag_first, a.s.frag_pos,
+                               a.s.built, a.s.index_status, stream));
+    SM_PASS(smm_uncompress_device(ctx->smm, d_in, a.s.in_off, a.s.in_len, m, max_fragments, d_out, a.s.out_off, a.s.cap,
+                                  a.s.out_len, a.s.dec_status, index ? a.s.frag_first : nullptr,
+                                  index ? a.s.frag_pos : nullptr, stream));
+  }
+  SM_CHECK(smq::launch_decode_result(a, (const smq::CrcLut*)ctx->lut.p, s));
+  return SM_OK;
+}
+
+sm_status smq_crc32_device(smq_ctx* ctx, const uint8_t* d_in, const uint64_t* d_off, const uint64_t* d_len, uint32_t n,
+                           uint32_t* d_crc, void* stream) {
+  if (!ctx || n > smq::kMaxChunks) return SM_ERR_ARGUMENT;
+  if (n == 0) return SM_OK;
+  if (!d_in || !d_off || !d_len || !d_crc) return SM_ERR_ARGUMENT;
+  DeviceGuard g(ctx->device);
+  SM_CHECK(ctx->meta.ensure(smq::crc_ranges_bytes(n)));
+  SM_CHECK(smq::launch_crc_ranges(d_in, d_off, d_len, n, d_crc, smq::carve_crc_ranges((uint8_t*)ctx->meta.p, n),
+                                  (const smq::CrcLut*)ctx->lut.p, (hipStream_t)stream));
+  return SM_OK;
+}
+
+// ---- host buffers --------------------------------------------------------------------------------
+// The chunks' bytes packed behind one another in one staging block (one upload), and room for every
+// chunk's output at a 16-byte boundary of the device buffer (one download; each chunk's own bytes
+// then go to the caller's place), as the ORC library's host-buffer calls.
+sm_status smq_uncompress_chunks(smq_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len,
+                                uint32_t nchunks, int verify_crc, uint8_t* out, const uint64_t* out_off,
+                                const uint64_t* out_cap, uint64_t* out_len, int32_t* status) {
+  if (!ctx || nchunks > smq::kMaxChunks) return SM_ERR_ARGUMENT;
+  if (nchunks == 0) return SM_OK;
+  if (!in_off || !in_len || !out_off || !out_cap || !out_len || !status) return SM_ERR_ARGUMENT;
+  // the plan on the host: the two bounds, and the room each decoded chunk needs on the device
+  std::vector<uint64_t> room(nchunks);
+  uint64_t pages = 0, fragments = 0;
+  const sm_status planned =
+      smq_chunks_plan(in, in_off, in_len, nchunks, out_cap, smq::kMaxChunks, nullptr, room.data(), status, &pages, &fragments);
+  if (planned != SM_OK) return planned == SM_BUFFER_TOO_SMALL ? (sm_status)SM_ERR_INPUT_TOO_LARGE : planned;
+  std::vector<uint64_t> h_in_off(nchunks), h_out_off(nchunks);
+  uint64_t in_total = 0, out_total = 0;
+  for (uint32_t r = 0; r < nchunks; ++r) {
+    if (status[r] != SM_OK) room[r] = 0;  // (not decoded)
+    if (room[r] && !out) return SM_ERR_ARGUMENT;
+    h_in_off[r] = in_total;
+    in_total += in_len[r];
+    h_out_off[r] = out_total;
+    out_total += (room[r] + 15) / 16 * 16;
+  }
+  if (fragments > smq::kMaxChunks) fragments = 0;  // (a hint: such a batch decodes in stream order)
+  std::vector<uint8_t> bytes((size_t)in_total);
+  for (uint32_t r = 0; r < nchunks; ++r)
+    if (in_len[r]) memcpy(bytes.data() + h_in_off[r], in + in_off[r], (size_t)in_len[r]);
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  // (a byte of each at the least: the device call wants both pointers)
+  SM_CHECK(ctx->io_in.ensure(std::max<size_t>(bytes.size(), 1)));
+  SM_CHECK(ctx->io_out.ensure(std::max<size_t>((size_t)out_total, 1)));
+  SM_CHECK(ctx->sarg.ensure(chunk_call_bytes(nchunks)));
+  const ChunkCallArrays d = carve_chunk_call((uintptr_t)ctx->sarg.p, nchunks);
+  const size_t n8 = 8 * (size_t)nchunks;
+  if (!bytes.empty()) SM_CHECK(hipMemcpyAsync(ctx->io_in.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(d.in_off, h_in_off.data(), n8, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(d.in_len, in_len, n8, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(d.out_off, h_out_off.data(), n8, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(d.out_cap, out_cap, n8, hipMemcpyHostToDevice, s));
+  SM_PASS(smq_uncompress_chunks_device(ctx, (const uint8_t*)ctx->io_in.p, d.in_off, d.in_len, nchunks, (uint32_t)pages,
+                                       (uint32_t)fragments, verify_crc, (uint8_t*)ctx->io_out.p, d.out_off, d.out_cap, d.out_len,
+                                       d.status, nullptr, nullptr, nullptr, s));
+  std::vector<uint8_t> decoded((size_t)out_total);
+  SM_CHECK(hipMemcpyAsync(out_len, d.out_len, n8, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(status, d.status, 4 * (size_t)nchunks, hipMemcpyDeviceToHost, s));
+  if (!decoded.empty()) SM_CHECK(hipMemcpyAsync(decoded.data(), ctx->io_out.p, decoded.size(), hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipStreamSynchronize(s));
+  for (uint32_t r = 0; r < nchunks; ++r)
+    if (room[r]) memcpy(out + out_off[r], decoded.data() + h_out_off[r], (size_t)room[r]);
+  return SM_OK;
+}
+
+}  // extern "C"

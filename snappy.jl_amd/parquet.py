@@ -1,0 +1,204 @@
+"""The pages of Parquet column chunks written with compression=SNAPPY over
+include/snappy_mi355x_parquet.h -- libsnappy_mi355x_parquet.so, the companion of
+libsnappy_mi355x_multi.so and libsnappy_mi355x.so.  A column chunk is a run of pages, each a Thrift
+compact-protocol PageHeader and a body: a raw Snappy stream, behind the stored level bytes of a v2
+data page.  The caller supplies each chunk's byte range (from the footer's ColumnMetaData: start =
+dictionary_page_offset if present, else data_page_offset; length = total_compressed_size) and
+promises that its codec is SNAPPY -- no footer, schema or encoding is parsed here.
+
+    uncompress_column_chunk(x)                 -> (bytes, page table)   one chunk (a batch of one)
+    uncompress_column_chunks(xs)               -> list of (bytes, page table)   one batched call
+    index_column_chunk(x)                      -> (summary, arrays)     the host walk
+    chunks_plan(xs), max_pages(n), length_uncompressed(x)               (host, no device)
+
+and, on torch tensors resident in HBM: uncompress_column_chunks_device, crc32_device (no host
+synchronisation), last_indexed.
+
+A chunk's output is its pages' uncompressed bytes back to back, what a CPU reader holds after
+decompression; the page table says where each page's bytes lie and what its header declares.
+
+The package imports without this library; it is loaded on the first call here.  No CPU fallback:
+every decode needs the three HIP libraries and a device.
+"""
+import ctypes
+import os
+
+import numpy as np
+
+from . import HERE, SnappyError, _in_arg
+from ._binding import PAGE_KEYS, PARQUET, Pages, Summary, check, collect, context_cache, device_caller, exclusive_scan, lay_out, load
+
+LIB_PATH = os.path.join(HERE, "libsnappy_mi355x_parquet.so")
+
+SMQ_ERR_HEADER = 72
+SMQ_ERR_TRUNCATED = 73
+SMQ_ERR_SIZE_MISMATCH = 74
+SMQ_ERR_CRC = 75
+PAGE_DATA, PAGE_INDEX, PAGE_DICTIONARY, PAGE_DATA_V2 = 0, 1, 2, 3
+PAGE_HAS_CRC, PAGE_COMPRESSED = 1, 2
+INDEX_KEYS = PAGE_KEYS  # smq_pages' arrays, in its order
+PAGE_DTYPES = {"hdr_off": np.uint64, "hdr_len": np.uint32, "body_len": np.uint32, "usize": np.uint32, "levels": np.uint32,
+               "out_off": np.uint64, "num_values": np.int32, "type": np.int32, "encoding": np.int32, "flags": np.uint32,
+               "crc": np.uint32}
+
+PARQUET_ABI_SYMBOLS = tuple(PARQUET)  # exported symbols of include/snappy_mi355x_parquet.h (tests/test_parquet_host.py)
+
+_lib = None
+
+
+def library_path():
+    return LIB_PATH
+
+
+def lib():
+    """Load libsnappy_mi355x_parquet.so (raises OSError if it was not built)."""
+    global _lib
+    if _lib is None:
+        _lib = load(LIB_PATH, PARQUET, "libsnappy_mi355x_parquet.so not built (run __graft_entry__.build())")
+    return _lib
+
+
+def status_message(code):
+    return lib().smq_status_message(int(code)).decode()
+
+
+def version():
+    return lib().smq_version().decode()
+
+
+class ParquetError(SnappyError):
+    """A SnappyError whose message comes from smq_status_message (the SMQ_ERR_* texts too); for a
+    chunk of a batch `chunk` is its number in the batch, else None."""
+
+    def __init__(self, code, chunk=None):
+        super().__init__(code, status_message(code))
+        self.chunk = chunk
+
+
+# context(device=0): the per-device smq_ctx (an smm_ctx of its own, the CRC tables and scratch)
+_ctx, _ctx_lock, context = context_cache(lib, "smq_ctx_create", SnappyError,
+                                         "no usable HIP device %d for snappy_mi355x_parquet")
+
+
+# ---- host helpers (no device) ---------------------------------------------------------------
+
+def max_pages(n):
+    """smq_max_pages: the most pages an n-byte chunk can hold (7 bytes each at the least)."""
+    return lib().smq_max_pages(int(n))
+
+
+def index_column_chunk(data, max_pages=None):
+    """The host walk (smq_index): (Summary, dict of numpy arrays, keyed as INDEX_KEYS, of the pages).
+    max_pages=None sizes the arrays by a counting walk first."""
+    src, n, keep = _in_arg(data)
+    s = Summary()
+    if max_pages is None:
+        s.status = lib().smq_index(src, n, None, 0, ctypes.byref(s))
+        max_pages = s.nchunks
+    arrays = {k: np.zeros(max_pages, PAGE_DTYPES[k]) for k in INDEX_KEYS}
+    pages = Pages(*(arrays[k].ctypes.data for k in INDEX_KEYS))
+    s.status = lib().smq_index(src, n, ctypes.byref(pages), max_pages, ctypes.byref(s))
+    return s, arrays
+
+
+def length_uncompressed(data):
+    """The chunk's total uncompressed length from its page headers (no device)."""
+    src, n, keep = _in_arg(data)
+    res = ctypes.c_size_t(0)
+    check(lib().smq_uncompressed_length(src, n, ctypes.byref(res)), ParquetError)
+    return res.value
+
+
+def chunks_plan(chunks, out_cap=None, max_pages=0x7FFFFFFF):
+    """smq_chunks_plan, the device's decode plan on the host, for a list of chunks: (rc, first,
+    out_len, status, total_pages, total_fragments) -- per chunk what is known before any byte is
+    decoded (the walk's error, SM_BUFFER_TOO_SMALL against out_cap[c], or 0), the size needed, the
+    exclusive scan of the slots (len(chunks) + 1 entries), and the device call's two bounds."""
+    buf, offs, lens = lay_out(chunks)
+    k = len(chunks)
+    cap = None if out_cap is None else np.ascontiguousarray(out_cap, dtype=np.uint64)
+    first, out_len, status = np.zeros(k + 1, np.uint32), np.zeros(k, np.uint64), np.zeros(k, np.int32)
+    pages, fragments = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = lib().smq_chunks_plan(buf.ctypes.data, offs.ctypes.data, lens.ctypes.data, k, None if cap is None else cap.ctypes.data,
+                               int(max_pages), first.ctypes.data, out_len.ctypes.data, status.ctypes.data, ctypes.byref(pages),
+                               ctypes.byref(fragments))
+    return int(rc), first, out_len, status, pages.value, fragments.value
+
+
+# ---- host buffers -----------------------------------------------------------------------
+
+def uncompress_column_chunks(chunks, verify_crc=True, device=0, statuses=False):
+    """Decode a list of column chunks in one batched call (smq_uncompress_chunks): a list of (bytes,
+    page table), the table a dict of numpy arrays as index_column_chunk gives it.  With verify_crc
+    the pages whose header carries a crc are checked on the device.  A failing chunk raises
+    ParquetError (the first failing chunk's status, its number as `.chunk`); with statuses=True
+    nothing is raised and the result is (that list, with None for a failing chunk's bytes; list of
+    statuses)."""
+    chunks = list(chunks)
+    if not chunks:
+        return ([], []) if statuses else []
+    buf, offs, lens = lay_out(chunks)
+    k = len(chunks)
+    _, _, need, pre, _, _ = chunks_plan(chunks)
+    cap = np.where(pre == 0, need, 0).astype(np.uint64)
+    out_off = exclusive_scan(cap, total=True)
+    out = np.empty(max(int(out_off[-1]), 1), np.uint8)
+    out_len, status = np.zeros(k, np.uint64), np.zeros(k, np.int32)
+    check(lib().smq_uncompress_chunks(context(device), buf.ctypes.data, offs.ctypes.data, lens.ctypes.data, k,
+                                      1 if verify_crc else 0, out.ctypes.data, out_off.ctypes.data, cap.ctypes.data,
+                                      out_len.ctypes.data, status.ctypes.data), ParquetError)
+    codes = status.tolist()
+    if not statuses:
+        for c, code in enumerate(codes):
+            if code:
+                raise ParquetError(code, c)
+    res = list(zip(collect(out, out_off, out_len, codes), [index_column_chunk(c)[1] for c in chunks]))
+    return (res, codes) if statuses else res
+
+
+def uncompress_column_chunk(data, verify_crc=True, device=0):
+    """One column chunk: (its pages' uncompressed bytes back to back, the page table)."""
+    try:
+        return uncompress_column_chunks([data], verify_crc=verify_crc, device=device)[0]
+    except ParquetError as e:
+        raise ParquetError(e.code) from None  # (a chunk alone has no number)
+
+
+# ---- device API (torch tensors resident in HBM; asynchronous on `stream`) ---------------------
+
+_device = device_caller(lib, context, ParquetError)
+
+
+def uncompress_column_chunks_device(d_in, d_in_off, d_in_len, max_pages, max_fragments, d_out, d_out_off, d_out_cap, d_out_len,
+                                    d_status, verify_crc=True, d_page_first=None, d_page_status=None, d_pages=None, stream=None,
+                                    device=None):
+    """smq_uncompress_chunks_device: chunk c = d_in[d_in_off[c] : d_in_off[c] + d_in_len[c]] decodes
+    into d_out[d_out_off[c] : d_out_off[c] + d_out_cap[c]]; per chunk d_out_len (int64) and d_status
+    (int32).  max_pages bounds the pages summed over the chunks that are decoded; max_fragments
+    (chunks_plan's second total, or 0) lets compressed sections of more than 64 KiB decode by
+    fragments.  Optional, both or neither: d_page_first int32[nchunks + 1], d_page_status
+    int32[max_pages].  Optional: d_pages, a dict of tensors of max_pages entries keyed as INDEX_KEYS
+    (int64 for hdr_off and out_off, int32 for the others), the page table.  Nothing is synchronised."""
+    pages = None
+    if d_pages is not None:
+        pages = ctypes.byref(Pages(*(d_pages[k].data_ptr() for k in INDEX_KEYS)))
+    _device("smq_uncompress_chunks_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), int(max_pages),
+            int(max_fragments), 1 if verify_crc else 0, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_page_first, pages,
+            d_page_status)
+
+
+def crc32_device(d_in, d_off, d_len, d_crc, stream=None, device=None):
+    """smq_crc32_device: d_crc[i] (int32, the CRC's 32 bits) = the CRC-32 (zlib.crc32) of
+    d_in[d_off[i] : d_off[i] + d_len[i]]; d_off and d_len int64.  Nothing is synchronised."""
+    _device("smq_crc32_device", d_crc, device, stream, d_in, d_off, d_len, d_len.numel(), d_crc)
+
+
+def last_indexed(device=0):
+    """Diagnostic (smq_ctx_last_indexed): how many values sections the device's last decode call
+    took by fragments (waits for the device); -1 before the first call."""
+    return int(lib().smq_ctx_last_indexed(context(device)))
+
+
+__all__ = ["PARQUET_ABI_SYMBOLS", "INDEX_KEYS", "ParquetError", "uncompress_column_chunk", "uncompress_column_chunks",
+           "index_column_chunk", "length_uncompressed", "chunks_plan", "max_pages", "uncompress_column_chunks_device",
+           "crc32_device", "last_indexed", "status_message", "version"]
