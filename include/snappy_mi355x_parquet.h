@@ -8,7 +8,8 @@
  * promises that its codec is SNAPPY.  The range is in the footer's ColumnMetaData: it starts at
  * dictionary_page_offset if present, else at data_page_offset, and is total_compressed_size long.
  * No footer, schema, encoding (RLE, dictionary, delta), bloom filter, column or offset index,
- * encryption or other codec is parsed here, and nothing is written: there is no encoder.
+ * encryption or other codec is parsed here, and nothing is written: the page encoder of this library
+ * has a header of its own, snappy_mi355x_parquet_write.h.
  *
  * It is layered on the multi library's public smm_*_device entry points and links that library and
  * the main one by name; all three must sit in one directory.  Status codes are snappy_mi355x.h's

@@ -13,7 +13,8 @@ A prototype is "<return> <arguments>", one letter per C type:
 
 tests/test_bindings.py holds every entry against the declaration in include/*.h
 (tests/test_blocks_host.py: the BLOCKS table; tests/test_orc_host.py: ORC;
-tests/test_multi_range_host.py: MULTI_RANGE; tests/test_parquet_host.py: PARQUET).
+tests/test_multi_range_host.py: MULTI_RANGE; tests/test_parquet_host.py: PARQUET;
+tests/test_parquet_write_host.py: PARQUET_WRITE).
 """
 import ctypes
 import os
@@ -217,6 +218,17 @@ PARQUET = {  # include/snappy_mi355x_parquet.h
     "smq_uncompress_chunks_device": "s ppppuuuippppppGpp",
     "smq_crc32_device": "s ppppupp",
     "smq_uncompress_chunks": "s ppppuippppp",
+}
+
+PARQUET_WRITE = {  # include/snappy_mi355x_parquet_write.h: the page encoder, exported by the parquet library
+    "smqe_max_chunk_length": "q qq",
+    "smqe_stage_bound": "q qq",
+    "smqe_rewrite_header": "s pzqupzZ",
+    "smqe_index": "s pzGpuS",
+    "smqe_chunks_plan": "s pppuupppQQQ",
+    "smqe_scratch_bytes": "z uuq",
+    "smqe_compress_chunks_device": "s ppppuuquppppppGpip",
+    "smqe_compress_chunks": "s ppppupppppi",
 }
 
 

@@ -17,6 +17,7 @@
 #include "../common/smc_layout.h"
 #include "smq_chunks.h"
 #include "smq_crc.h"
+#include "smq_encode.h"
 #include "smq_format.h"
 #include "smq_internal.h"
 
@@ -160,6 +161,39 @@ sm_status smq_crc32_device(smq_ctx* ctx, const uint8_t* d_in, const uint64_t* d_
   return SM_OK;
 }
 
+// ---- the page encoder (include/snappy_mi355x_parquet_write.h) ----------------------------------------
+// Launch sequence: the counting walk, the scan, the storing walk, the scan of the stage slots and
+// the fragments; the multi library's compressor once over all slots (a slot without a section is an
+// empty stream to it); the level bytes, the bodies' lengths and statuses, the CRC segments, the sizes
+// with the chunks' results, the pack.
+sm_status smqe_compress_chunks_device(smq_ctx* ctx, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_in_len,
+                                      uint32_t nchunks, uint32_t max_pages, uint64_t stage_bytes, uint32_t max_fragments,
+                                      uint8_t* d_out, const uint64_t* d_out_off, const uint64_t* d_out_cap, uint64_t* d_out_len,
+                                      int32_t* d_status, uint32_t* d_page_first, const smq_pages* d_pages,
+                                      int32_t* d_page_status, int mode, void* stream) {
+  if (!ctx || nchunks > smq::kMaxChunks || max_pages > smq::kMaxChunks) return SM_ERR_ARGUMENT;
+  if (mode != SM_MODE_REFERENCE && mode != SM_MODE_FAST && mode != SM_MODE_FAST_DENSE) return SM_ERR_ARGUMENT;
+  if (!d_page_first != !d_page_status) return SM_ERR_ARGUMENT;
+  if (d_pages && !smq::valid_pages(*d_pages)) return SM_ERR_ARGUMENT;
+  if (nchunks == 0) return SM_OK;
+  if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_out_len || !d_status) return SM_ERR_ARGUMENT;
+  hipStream_t s = (hipStream_t)stream;
+  DeviceGuard g(ctx->device);
+  const uint32_t m = max_pages;
+  SM_CHECK(ctx->meta.ensure(smq::encode_chunks_bytes(nchunks, m, (size_t)stage_bytes)));
+  const smq::EncodeChunksArgs a{d_in,     d_in_off,     d_in_len,      nchunks,            m,
+                                stage_bytes, max_fragments, d_out,      d_out_off,          d_out_cap,
+                                d_out_len, d_status,     d_page_first,  d_page_status,      d_pages != nullptr,
+                                d_pages ? *d_pages : smq_pages{},
+                                smq::carve_encode_chunks((uint8_t*)ctx->meta.p, nchunks, m, (size_t)stage_bytes)};
+  SM_CHECK(smq::launch_encode_plan(a, s));
+  if (m)
+    SM_PASS(smm_compress_device(ctx->smm, d_in, a.s.in_off, a.s.in_len, m, max_fragments, a.s.stage, a.s.comp_off, a.s.comp_len,
+                                a.s.comp_status, nullptr, nullptr, mode, stream));
+  SM_CHECK(smq::launch_encode_result(a, (const smq::CrcLut*)ctx->lut.p, s));
+  return SM_OK;
+}
+
 // ---- host buffers --------------------------------------------------------------------------------
 // The chunks' bytes packed behind one another in one staging block (one upload), and room for every
 // chunk's output at a 16-byte boundary of the device buffer (one download; each chunk's own bytes
@@ -214,6 +248,59 @@ sm_status smq_uncompress_chunks(smq_ctx* ctx, const uint8_t* in, const uint64_t*
   SM_CHECK(hipStreamSynchronize(s));
   for (uint32_t r = 0; r < nchunks; ++r)
     if (room[r]) memcpy(out + out_off[r], decoded.data() + h_out_off[r], (size_t)room[r]);
+  return SM_OK;
+}
+
+// The encoder's twin: the plan on the host gives the three bounds and, per chunk, room that always
+// suffices -- the smaller of the caller's room and the plan's bound.
+sm_status smqe_compress_chunks(smq_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len,
+                               uint32_t nchunks, uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap,
+                               uint64_t* out_len, int32_t* status, int mode) {
+  if (!ctx || nchunks > smq::kMaxChunks) return SM_ERR_ARGUMENT;
+  if (nchunks == 0) return SM_OK;
+  if (!in_off || !in_len || !out_off || !out_cap || !out_len || !status) return SM_ERR_ARGUMENT;
+  std::vector<uint64_t> room(nchunks);
+  uint64_t pages = 0, stage = 0, fragments = 0;
+  const sm_status planned =
+      smqe_chunks_plan(in, in_off, in_len, nchunks, smq::kMaxChunks, nullptr, status, room.data(), &pages, &stage, &fragments);
+  if (planned != SM_OK) return planned == SM_BUFFER_TOO_SMALL ? (sm_status)SM_ERR_INPUT_TOO_LARGE : planned;
+  if (fragments > smq::kMaxChunks) return SM_ERR_INPUT_TOO_LARGE;
+  std::vector<uint64_t> h_in_off(nchunks), h_out_off(nchunks);
+  uint64_t in_total = 0, out_total = 0;
+  for (uint32_t r = 0; r < nchunks; ++r) {
+    room[r] = std::min(room[r], out_cap[r]);
+    if (room[r] && !out) return SM_ERR_ARGUMENT;
+    h_in_off[r] = in_total;
+    in_total += in_len[r];
+    h_out_off[r] = out_total;
+    out_total += (room[r] + 15) / 16 * 16;
+  }
+  std::vector<uint8_t> bytes((size_t)in_total);
+  for (uint32_t r = 0; r < nchunks; ++r)
+    if (in_len[r]) memcpy(bytes.data() + h_in_off[r], in + in_off[r], (size_t)in_len[r]);
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  DeviceGuard g(ctx->device);
+  hipStream_t s = ctx->stream;
+  SM_CHECK(ctx->io_in.ensure(std::max<size_t>(bytes.size(), 1)));
+  SM_CHECK(ctx->io_out.ensure(std::max<size_t>((size_t)out_total, 1)));
+  SM_CHECK(ctx->sarg.ensure(chunk_call_bytes(nchunks)));
+  const ChunkCallArrays d = carve_chunk_call((uintptr_t)ctx->sarg.p, nchunks);
+  const size_t n8 = 8 * (size_t)nchunks;
+  if (!bytes.empty()) SM_CHECK(hipMemcpyAsync(ctx->io_in.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(d.in_off, h_in_off.data(), n8, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(d.in_len, in_len, n8, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(d.out_off, h_out_off.data(), n8, hipMemcpyHostToDevice, s));
+  SM_CHECK(hipMemcpyAsync(d.out_cap, out_cap, n8, hipMemcpyHostToDevice, s));
+  SM_PASS(smqe_compress_chunks_device(ctx, (const uint8_t*)ctx->io_in.p, d.in_off, d.in_len, nchunks, (uint32_t)pages, stage,
+                                      (uint32_t)fragments, (uint8_t*)ctx->io_out.p, d.out_off, d.out_cap, d.out_len, d.status,
+                                      nullptr, nullptr, nullptr, mode, s));
+  std::vector<uint8_t> packed((size_t)out_total);
+  SM_CHECK(hipMemcpyAsync(out_len, d.out_len, n8, hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipMemcpyAsync(status, d.status, 4 * (size_t)nchunks, hipMemcpyDeviceToHost, s));
+  if (!packed.empty()) SM_CHECK(hipMemcpyAsync(packed.data(), ctx->io_out.p, packed.size(), hipMemcpyDeviceToHost, s));
+  SM_CHECK(hipStreamSynchronize(s));
+  for (uint32_t r = 0; r < nchunks; ++r)
+    if (status[r] == SM_OK && out_len[r]) memcpy(out + out_off[r], packed.data() + h_out_off[r], (size_t)out_len[r]);
   return SM_OK;
 }
 

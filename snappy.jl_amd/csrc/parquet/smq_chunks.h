@@ -1,13 +1,17 @@
 // smq_chunks.h -- the rules of the batched call (smq_uncompress_chunks_device), shared by its kernels
 // (smq_kernels.hip) and the host (smq_chunks_plan in smq_host.cpp, which the sanitizer driver runs):
 // what a walked chunk of a batch gets, a slot's and a chunk's verdict, the tiling of the copies and
-// the scratch layout.  The walk itself is walk_pages (smq_format.h).  Plain functions, compiled for
+// the scratch layout -- and the encoder's slots and their carve (smqe_compress_chunks_device; its
+// rules are smq_encode.h's).  The walk itself is walk_pages (smq_format.h).  Plain functions, compiled for
 // the host and the device alike, so the host checker tests the code the kernels run.  Not part of
 // the public ABI.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
+#include "../../../include/snappy_mi355x_parquet_write.h"
 #include "smq_format.h"
 
 namespace smq {
@@ -134,6 +138,51 @@ inline DecodeChunks carve_decode_chunks(uint8_t* buf, size_t nchunks, size_t m, 
 }
 inline size_t decode_chunks_bytes(size_t nchunks, size_t m, size_t max_fragments) {
   return (size_t)carve_decode_chunks(nullptr, nchunks, m, max_fragments).end;
+}
+
+// ---- the encoder's scratch (smqe_compress_chunks_device) ---------------------------------------------
+// The stage's first bytes belong to no page: a slot without a section is an empty stream to the raw
+// compressor, which wants room for sm_max_compressed_length(0) bytes wherever it writes.
+constexpr uint64_t kStageDump = 32;
+struct EncodeChunks {
+  Header* hdr;
+  // per slot (m = max_pages).  The page in the input: its header's place (relative to d_in), the
+  // lengths and the patch sites; the raw compressor's arguments and results (a slot without a section
+  // -- a page that is stepped over, a slot no page took -- is an empty stream that compresses to the
+  // stage's dump bytes); the staged body (relative to the stage); the page in the output
+  uint64_t *hdr_in, *in_off, *comp_off, *body_off, *page_out, *stage_len;
+  uint32_t *hdr_len, *old_body, *levels, *in_len, *comp_len, *new_body, *new_hdr, *chunk, *flags, *crc_acc, *seg_first;
+  uint32_t* sites;  // SMQE_SITES words a slot
+  int32_t *comp_status, *slot_status;
+  // per chunk
+  uint32_t *count, *first, *fail, *go;
+  int32_t* pre;
+  uint8_t* stage;  // stage_bytes (kStageDump at the least), from a 16-byte boundary
+  uintptr_t end;
+};
+
+inline EncodeChunks carve_encode_chunks(uint8_t* buf, size_t nchunks, size_t m, size_t stage_bytes) {
+  smc::Carve c{reinterpret_cast<uintptr_t>(buf)};
+  EncodeChunks s;
+  s.hdr = c.take<Header>(1);
+  for (uint64_t** a : {&s.hdr_in, &s.in_off, &s.comp_off, &s.body_off, &s.page_out, &s.stage_len}) *a = c.take<uint64_t>(m);
+  for (uint32_t** a : {&s.hdr_len, &s.old_body, &s.levels, &s.in_len, &s.comp_len, &s.new_body, &s.new_hdr, &s.chunk, &s.flags, &s.crc_acc})
+    *a = c.take<uint32_t>(m);
+  s.seg_first = c.take<uint32_t>(m + 1);
+  s.sites = c.take<uint32_t>(m * SMQE_SITES);
+  s.comp_status = c.take<int32_t>(m);
+  s.slot_status = c.take<int32_t>(m);
+  s.count = c.take<uint32_t>(nchunks);
+  s.first = c.take<uint32_t>(nchunks + 1);
+  s.fail = c.take<uint32_t>(nchunks);
+  s.go = c.take<uint32_t>(nchunks);
+  s.pre = c.take<int32_t>(nchunks);
+  s.stage = c.take<uint8_t>(stage_bytes < kStageDump ? kStageDump : stage_bytes);
+  s.end = c.p;
+  return s;
+}
+inline size_t encode_chunks_bytes(size_t nchunks, size_t m, size_t stage_bytes) {
+  return (size_t)carve_encode_chunks(nullptr, nchunks, m, stage_bytes).end;
 }
 
 // smq_crc32_device's own arrays: per range the scan of its segments and its register

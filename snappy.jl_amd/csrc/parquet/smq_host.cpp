@@ -4,6 +4,7 @@
 // this file also builds alone (the sanitizer driver, smq_host_check.cpp).
 #include "smq_chunks.h"
 #include "smq_crc.h"
+#include "smq_encode.h"
 #include "smq_format.h"
 
 namespace smq {
@@ -120,6 +121,97 @@ sm_status smq_chunks_plan(const uint8_t* in, const uint64_t* in_off, const uint6
   for (uint32_t r = 0; r < nchunks; ++r) {
     if (status) status[r] = SM_ERR_ARGUMENT;
     if (out_len) out_len[r] = 0;
+  }
+  return SM_BUFFER_TOO_SMALL;
+}
+
+// ---- the page encoder (include/snappy_mi355x_parquet_write.h) ------------------------------------------
+
+uint64_t smqe_max_chunk_length(uint64_t n, uint64_t pages) { return n + n / 6 + 40 * pages; }
+
+uint64_t smqe_stage_bound(uint64_t total_in_bytes, uint64_t pages) {
+  return smq::kStageDump + total_in_bytes + total_in_bytes / 6 + 48 * pages;
+}
+
+sm_status smqe_rewrite_header(const uint8_t* hdr, size_t n, uint64_t new_body_len, uint32_t crc, uint8_t* out, size_t cap,
+                              size_t* out_len) {
+  if (!out_len || (!hdr && n) || (!out && cap)) return SM_ERR_ARGUMENT;
+  smq::Frame stack[SMQ_MAX_DEPTH];
+  smq::ByteFetch fetch{hdr};
+  smq::Reader<smq::ByteFetch> r(fetch, n, stack);
+  smq::HeaderFields h;
+  smq::read_page_header<smq::EncodeWalk>(r, h);
+  if (!r.ok()) return r.status;
+  if (!smq::header_fields_ok<smq::EncodeWalk>(h)) return SMQ_ERR_HEADER;
+  if (r.pos > 0xffffffffull) return SMQ_ERR_HEADER;
+  if (new_body_len > smq::kMaxBody) return SM_ERR_INPUT_TOO_LARGE;
+  const smq::Rewrite w = smq::make_rewrite((uint32_t)r.pos, smq::header_sites(h, 0), (uint32_t)new_body_len, crc);
+  *out_len = w.new_len;
+  if (w.new_len > cap) return SM_BUFFER_TOO_SMALL;
+  for (uint32_t i = 0; i < w.new_len; ++i) out[i] = smq::rewritten_byte(w, fetch, i);
+  return SM_OK;
+}
+
+sm_status smqe_index(const uint8_t* buf, size_t n, const smq_pages* pages, uint32_t* sites, uint32_t max_pages,
+                     smq_summary* summary) {
+  if (!summary || (!buf && n)) return SM_ERR_ARGUMENT;
+  if (pages && max_pages && !smq::valid_pages(*pages)) return SM_ERR_ARGUMENT;
+  smq::Frame stack[SMQ_MAX_DEPTH];
+  smq::ByteFetch fetch{buf};
+  const smq::Walk w = smq::walk_pages<smq::EncodeWalk>(n, fetch, stack, [&](uint32_t k, uint64_t at, const smq::Page& p) {
+    if (!pages || k >= max_pages) return;
+    smq::store_page(*pages, k, at, p);
+    if (sites) {
+      const uint32_t v[SMQE_SITES] = {p.sites.f3_at, p.sites.f3_len, p.sites.f4_at, p.sites.f4_len, p.sites.f7_at};
+      for (uint32_t i = 0; i < SMQE_SITES; ++i) sites[(size_t)k * SMQE_SITES + i] = v[i];
+    }
+  });
+  summary->total_length = w.total;
+  summary->npages = w.npages;
+  summary->status = smq::walk_status(w, pages != nullptr, max_pages);
+  return summary->status;
+}
+
+size_t smqe_scratch_bytes(uint32_t nchunks, uint32_t max_pages, uint64_t stage_bytes) {
+  return smq::encode_chunks_bytes(nchunks, max_pages, (size_t)stage_bytes);
+}
+
+// the device's encode plan, chunk by chunk (smq_encode.h)
+sm_status smqe_chunks_plan(const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len, uint32_t nchunks,
+                           uint32_t max_pages, uint32_t* first, int32_t* status, uint64_t* out_bound, uint64_t* total_pages,
+                           uint64_t* stage_bytes, uint64_t* total_fragments) {
+  if (nchunks > smq::kMaxChunks || max_pages > smq::kMaxChunks) return SM_ERR_ARGUMENT;
+  if (nchunks && (!in_off || !in_len)) return SM_ERR_ARGUMENT;
+  for (uint32_t r = 0; r < nchunks; ++r)
+    if (in_len[r] && !in) return SM_ERR_ARGUMENT;
+  uint64_t sum = 0, stage = smq::kStageDump, fragments = 0;
+  smq::Frame stack[SMQ_MAX_DEPTH];
+  for (uint32_t r = 0; r < nchunks; ++r) {
+    smq::ByteFetch fetch{in_len[r] ? in + in_off[r] : nullptr};
+    uint64_t slots = 0, frags = 0, bound = 0;  // of this chunk, should it be compressed
+    const smq::Walk w = smq::walk_pages<smq::EncodeWalk>(in_len[r], fetch, stack, [&](uint32_t, uint64_t, const smq::Page& p) {
+      slots += smq::stage_slot(p);
+      frags += smq::encode_fragments(p);
+      bound += smq::page_bound(p);
+    });
+    const bool ok = w.status == SM_OK;
+    if (first) first[r] = sum > 0xffffffffull ? 0xffffffffu : (uint32_t)sum;
+    if (status) status[r] = w.status;
+    if (out_bound) out_bound[r] = ok ? bound : 0;
+    if (ok) {
+      sum += w.npages;
+      stage += slots;
+      fragments += frags;
+    }
+  }
+  if (first) first[nchunks] = sum > 0xffffffffull ? 0xffffffffu : (uint32_t)sum;
+  if (total_pages) *total_pages = sum;
+  if (stage_bytes) *stage_bytes = stage;
+  if (total_fragments) *total_fragments = fragments;
+  if (sum <= max_pages) return SM_OK;
+  for (uint32_t r = 0; r < nchunks; ++r) {
+    if (status) status[r] = SM_ERR_ARGUMENT;
+    if (out_bound) out_bound[r] = 0;
   }
   return SM_BUFFER_TOO_SMALL;
 }

@@ -3,7 +3,9 @@
 // the chunk's size, so a walk that reads past a cut chunk trips the sanitizer; the batched decode's
 // plan (smq_chunks_plan) runs over the same cases laid directly behind one another; the CRC
 // kernel's arithmetic runs lane by lane (crc32_model) over heap blocks of exactly the range's size
-// at every alignment.  The expected values are written out here; none comes from the code under test.
+// at every alignment; the page encoder's rewrite rule, its walk and its plan (smqe_*) run case by case
+// over exact-size heap blocks too.  The expected values are written out here; none comes from the code
+// under test.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -12,6 +14,7 @@
 
 #include "smq_chunks.h"
 #include "smq_crc.h"
+#include "smq_encode.h"
 #include "smq_format.h"
 
 namespace {
@@ -209,6 +212,198 @@ void crc_cases() {
   std::free(T);
 }
 
+// ---- the page encoder (include/snappy_mi355x_parquet_write.h) ------------------------------------------
+// smqe_rewrite_header over a heap block of exactly the header's size, into one of exactly `cap` bytes
+struct Rewritten {
+  sm_status status;
+  size_t len;
+  S bytes;
+};
+Rewritten rewrite(const S& hdr, uint64_t body, uint32_t crc, size_t cap) {
+  uint8_t* in = (uint8_t*)std::malloc(hdr.size() ? hdr.size() : 1);
+  std::memcpy(in, hdr.data(), hdr.size());
+  uint8_t* out = (uint8_t*)std::malloc(cap ? cap : 1);
+  std::memset(out, 0xee, cap ? cap : 1);
+  Rewritten r{SM_OK, 0, S()};
+  r.status = smqe_rewrite_header(in, hdr.size(), body, crc, cap ? out : nullptr, cap, &r.len);
+  r.bytes = S((const char*)out, cap);
+  std::free(in);
+  std::free(out);
+  return r;
+}
+
+void rewrite_case(const char* name, const S& hdr, uint64_t body, uint32_t crc, const S& want) {
+  const Rewritten exact = rewrite(hdr, body, crc, want.size());
+  const Rewritten roomy = rewrite(hdr + "behind", body, crc, want.size() + 3);
+  const Rewritten tight = rewrite(hdr, body, crc, want.size() - 1);
+  const Rewritten measure = rewrite(hdr, body, crc, 0);
+  if (exact.status != SM_OK || exact.len != want.size() || exact.bytes != want || roomy.status != SM_OK ||
+      roomy.bytes != want + S(3, '\xee') || tight.status != SM_BUFFER_TOO_SMALL || tight.len != want.size() ||
+      tight.bytes != S(want.size() - 1, '\xee') || measure.status != SM_BUFFER_TOO_SMALL || measure.len != want.size()) {
+    std::printf("FAIL rewrite: %s (status %d, length %zu, want %zu)\n", name, exact.status, exact.len, want.size());
+    ++failures;
+  }
+}
+
+struct EncodeResult {
+  smq_summary sum;
+  std::vector<uint32_t> sites, hdr_len, body_len, flags;
+};
+EncodeResult encode_walk(const S& chunk, uint32_t max_pages = 8) {
+  EncodeResult r;
+  std::vector<uint64_t> hdr_off(max_pages), out_off(max_pages);
+  std::vector<uint32_t> usize(max_pages), levels(max_pages), crc(max_pages);
+  std::vector<int32_t> nv(max_pages), type(max_pages), enc(max_pages);
+  r.sites.assign((size_t)max_pages * SMQE_SITES, 0xeeeeeeeeu);
+  r.hdr_len.resize(max_pages);
+  r.body_len.resize(max_pages);
+  r.flags.resize(max_pages);
+  uint8_t* heap = (uint8_t*)std::malloc(chunk.size() ? chunk.size() : 1);
+  std::memcpy(heap, chunk.data(), chunk.size());
+  const smq_pages pg{hdr_off.data(), r.hdr_len.data(), r.body_len.data(), usize.data(), levels.data(), out_off.data(),
+                     nv.data(),      type.data(),      enc.data(),        r.flags.data(), crc.data()};
+  r.sum = smq_summary{0, 0, 0};
+  smqe_index(heap, chunk.size(), &pg, r.sites.data(), max_pages, &r.sum);
+  smq_summary count{0, 0, 0};
+  smqe_index(heap, chunk.size(), nullptr, nullptr, 0, &count);
+  expect(count.npages == r.sum.npages && count.total_length == r.sum.total_length, "encode walk: the count-only walk agrees");
+  std::free(heap);
+  return r;
+}
+
+void encode_status(const char* name, const S& chunk, int32_t status, uint32_t npages) {
+  const EncodeResult r = encode_walk(chunk);
+  if (r.sum.status != status || r.sum.npages != npages) {
+    std::printf("FAIL encode walk: %s: status %d (want %d), pages %u (want %u)\n", name, r.sum.status, status, r.sum.npages, npages);
+    ++failures;
+  }
+}
+
+void encode_cases() {
+  const int64_t crc = -2, imin = INT32_MIN;
+  // both varints grow; the rest of the header stays
+  const S v1 = head(0, 3, 3, &crc) + data_header(4, 3, 0) + kStopByte;
+  rewrite_case("both varints grow", v1, 64, 0x80000000u, head(0, 3, 64, &imin) + data_header(4, 3, 0) + kStopByte);
+  const int64_t big_crc = 0x12345678;
+  const S wide = head(0, 0x7fffffff, 0x7fffffff, &big_crc) + data_header(4, 3, 0) + kStopByte;
+  const int64_t zero = 0;
+  rewrite_case("both varints shrink", wide, 0, 0, head(0, 0x7fffffff, 0, &zero) + data_header(4, 3, 0) + kStopByte);
+  rewrite_case("the longest body", v1, 0x7fffffffu, 0xfffffffeu, head(0, 3, 0x7fffffff, &crc) + data_header(4, 3, 0) + kStopByte);
+  // no crc: none is added, and the crc argument is not looked at
+  rewrite_case("no crc", head(0, 3, 3) + data_header(3, 3, 0) + kStopByte, 8192, 0xdeadbeefu,
+               head(0, 3, 8192) + data_header(3, 3, 0) + kStopByte);
+  // v2: is_compressed false becomes true, true stays, absent stays absent
+  const S v2_false = head(3, 6, 6) + v2_header(3, 9, 8, 2, 1, 0) + kStopByte;
+  rewrite_case("v2 false", v2_false, 5, 0, head(3, 6, 5) + v2_header(3, 9, 8, 2, 1, 1) + kStopByte);
+  rewrite_case("v2 true", head(3, 6, 6) + v2_header(3, 9, 8, 2, 1, 1) + kStopByte, 5, 0,
+               head(3, 6, 5) + v2_header(3, 9, 8, 2, 1, 1) + kStopByte);
+  rewrite_case("v2 absent", head(3, 6, 6) + v2_header(3, 9, 8, 2, 1, -1) + kStopByte, 5, 0,
+               head(3, 6, 5) + v2_header(3, 9, 8, 2, 1, -1) + kStopByte);
+  // the crc before the size, both in the long form, an unknown field between them
+  const S lf3 = S("\x05", 1) + zz(3), lf4 = S("\x05", 1) + zz(4), unknown = S("\x08", 1) + zz(90) + S("\x03" "abc", 4);
+  rewrite_case("crc before the size", i32f(1, 0) + i32f(1, 3) + lf4 + zz(-2) + unknown + lf3 + zz(3) + data_header(3, 3, 0) + kStopByte,
+               8192, 1, i32f(1, 0) + i32f(1, 3) + lf4 + zz(1) + unknown + lf3 + zz(8192) + data_header(3, 3, 0) + kStopByte);
+  // a page type the walk steps over: the rule is the same
+  rewrite_case("an index page", head(1, 99, 4, &crc) + kStopByte, 4, 0xfffffffeu, head(1, 99, 4, &crc) + kStopByte);
+  // rejections
+  expect(rewrite(v1, 0x80000000ull, 0, 64).status == SM_ERR_INPUT_TOO_LARGE, "rewrite: a body above 2 GiB - 1");
+  for (size_t cut = 0; cut < v1.size(); ++cut)
+    expect(rewrite(v1.substr(0, cut), 5, 5, 64).status == SMQ_ERR_TRUNCATED, "rewrite: a cut header");
+  const S twice3 = i32f(1, 1) + i32f(1, 0) + i32f(1, 0) + lf3 + zz(0) + kStopByte;
+  const S twice4 = head(1, 0, 0, &crc) + lf4 + zz(0) + kStopByte;
+  const S twice7 = head(3, 6, 6) + v2_header(3, 9, 8, 2, 1, 0).substr(0, 14) + S("\x01", 1) + zz(7) + kStopByte + kStopByte;
+  expect(rewrite(twice3, 5, 5, 64).status == SMQ_ERR_HEADER, "rewrite: field 3 twice");
+  expect(rewrite(twice4, 5, 5, 64).status == SMQ_ERR_HEADER, "rewrite: field 4 twice");
+  expect(rewrite(twice7, 5, 5, 64).status == SMQ_ERR_HEADER, "rewrite: field 8.7 twice");
+  expect(rewrite(i32f(1, 1) + i32f(1, 0) + kStopByte, 5, 5, 64).status == SMQ_ERR_HEADER, "rewrite: field 3 missing");
+  size_t len = 0;
+  expect(smqe_rewrite_header((const uint8_t*)v1.data(), v1.size(), 5, 5, nullptr, 0, nullptr) == SM_ERR_ARGUMENT &&
+             smqe_rewrite_header(nullptr, 4, 5, 5, nullptr, 0, &len) == SM_ERR_ARGUMENT &&
+             smqe_rewrite_header((const uint8_t*)v1.data(), v1.size(), 5, 5, nullptr, 4, &len) == SM_ERR_ARGUMENT,
+         "rewrite: arguments");
+
+  // the encode walk: plain pages, their sites
+  const S abc = head(0, 3, 3) + data_header(3, 3, 0) + kStopByte + "abc";
+  const S v2 = head(3, 6, 6, &crc) + v2_header(4, 9, 8, 2, 1, 0) + kStopByte + "LLLabc";
+  const S index_page = head(1, 99, 4) + kStopByte + "skip";
+  {
+    const EncodeResult r = encode_walk(abc + index_page + v2);
+    expect(r.sum.status == SM_OK && r.sum.npages == 3 && r.sum.total_length == 9, "encode walk: summary");
+    const uint32_t want[3][SMQE_SITES] = {{5, 1, 0, 0, 0}, {6, 1, 0, 0, 0}, {5, 1, 7, 1, 21}};
+    for (uint32_t k = 0; k < 3; ++k)
+      for (uint32_t i = 0; i < SMQE_SITES; ++i) expect(r.sites[k * SMQE_SITES + i] == want[k][i], "encode walk: sites");
+    expect(r.sites[3 * SMQE_SITES] == 0xeeeeeeeeu, "encode walk: no site behind the last page");
+    expect(r.body_len[0] == 3 && r.body_len[1] == 4 && r.body_len[2] == 6 && r.flags[0] == 0 && r.flags[1] == 0 &&
+               r.flags[2] == SMQ_PAGE_HAS_CRC && r.hdr_len[2] == v2.size() - 6,
+           "encode walk: entries");
+    const EncodeResult small = encode_walk(abc + index_page + v2, 2);
+    expect(small.sum.status == SM_BUFFER_TOO_SMALL && small.sum.npages == 3, "encode walk: capacity too small");
+  }
+  encode_status("empty chunk", "", SM_OK, 0);
+  encode_status("a section that is Snappy already", abc + head(0, 3, 5) + data_header(3, 3, 0) + kStopByte + kAbc, SMQ_ERR_SIZE_MISMATCH, 1);
+  encode_status("a v2 page whose sizes differ", head(3, 6, 8) + v2_header(3, 9, 8, 2, 1, 0) + kStopByte + "LLL" + kAbc, SMQ_ERR_SIZE_MISMATCH, 0);
+  encode_status("an index page whose sizes differ", index_page, SM_OK, 1);
+  encode_status("field 3 twice", abc + twice3, SMQ_ERR_HEADER, 1);
+  encode_status("field 4 twice", abc + twice4, SMQ_ERR_HEADER, 1);
+  encode_status("field 8.7 twice", abc + twice7 + "LLLabc", SMQ_ERR_HEADER, 1);
+  encode_status("field 3 missing", i32f(1, 1) + i32f(1, 0) + kStopByte, SMQ_ERR_HEADER, 0);
+  encode_status("levels above the size", head(3, 2, 2) + v2_header(3, 9, 8, 2, 1, -1) + kStopByte + "LL", SMQ_ERR_HEADER, 0);
+  encode_status("nothing of a section is looked at", head(0, 3, 3) + data_header(3, 3, 0) + kStopByte + S("\x80\x80\x80", 3), SM_OK, 1);
+  for (size_t cut = 1; cut < v2.size(); ++cut) encode_status("v2 cut", v2.substr(0, cut), SMQ_ERR_TRUNCATED, 0);
+  for (size_t cut = 1; cut < v2.size(); ++cut) encode_status("second page cut", abc + v2.substr(0, cut), SMQ_ERR_TRUNCATED, 1);
+
+  // the plan: chunks directly behind one another in a heap block of exactly their size
+  {
+    const S big = head(0, 200000, 200000) + data_header(3, 1, 0) + kStopByte + S(200000, 'x');
+    const S bad = head(0, 3, 5) + data_header(3, 3, 0) + kStopByte + kAbc;
+    const S parts[5] = {abc, v2 + index_page, bad, big, ""};
+    uint64_t off[5], len[5], n = 0;
+    for (int i = 0; i < 5; ++i) {
+      off[i] = n;
+      len[i] = parts[i].size();
+      n += len[i];
+    }
+    uint8_t* heap = (uint8_t*)std::malloc(n);
+    for (int i = 0; i < 5; ++i) std::memcpy(heap + off[i], parts[i].data(), len[i]);
+    uint32_t first[6];
+    int32_t st[5];
+    uint64_t bound[5], pages = 0, stage = 0, frags = 0;
+    expect(smqe_chunks_plan(heap, off, len, 5, 4, first, st, bound, &pages, &stage, &frags) == SM_OK, "encode plan: status");
+    expect(pages == 4 && frags == 4 && stage == 32 + 48 + 48 + 233376, "encode plan: the three bounds");
+    expect(first[0] == 0 && first[1] == 1 && first[2] == 3 && first[3] == 3 && first[4] == 4 && first[5] == 4, "encode plan: the scan");
+    expect(st[0] == SM_OK && st[1] == SM_OK && st[2] == SMQ_ERR_SIZE_MISMATCH && st[3] == SM_OK && st[4] == SM_OK, "encode plan: statuses");
+    expect(bound[0] == abc.size() - 3 + 8 + 35 && bound[1] == (v2.size() - 6) + 8 + 3 + 35 + index_page.size() && bound[2] == 0 &&
+               bound[3] == (big.size() - 200000) + 8 + 32 + 200000 + 33333 && bound[4] == 0,
+           "encode plan: the output bounds");
+    expect(smqe_chunks_plan(heap, off, len, 5, 3, first, st, bound, &pages, &stage, &frags) == SM_BUFFER_TOO_SMALL && pages == 4,
+           "encode plan: one slot short");
+    for (int i = 0; i < 5; ++i) expect(st[i] == SM_ERR_ARGUMENT && bound[i] == 0, "encode plan: one slot short: the statuses");
+    expect(smqe_chunks_plan(heap, off, len, 5, 4, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == SM_OK &&
+               smqe_chunks_plan(nullptr, off, len, 5, 4, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == SM_ERR_ARGUMENT &&
+               smqe_chunks_plan(nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, &pages, &stage, &frags) == SM_OK &&
+               pages == 0 && stage == 32 && frags == 0,
+           "encode plan: arguments");
+    std::free(heap);
+  }
+  expect(smqe_max_chunk_length(600, 2) == 600 + 100 + 80 && smqe_stage_bound(600, 2) == 32 + 600 + 100 + 96, "encoder bounds");
+  expect(smqe_scratch_bytes(3, 7, 1000) > smqe_scratch_bytes(3, 6, 1000) && smqe_scratch_bytes(3, 7, 5000) >= smqe_scratch_bytes(3, 7, 1000) + 3984 &&
+             smqe_scratch_bytes(0, 0, 0) > 0,
+         "encoder scratch bytes");
+  // the verdicts
+  expect(smq::page_verdict(false, 0, 0, 5) == SM_OK && smq::page_verdict(true, 3, 10, SM_OK) == SM_OK &&
+             smq::page_verdict(true, 3, 0, SM_OK) == SM_ERR_DEVICE && smq::page_verdict(true, 3, 10, SM_ERR_DEVICE) == SM_ERR_DEVICE &&
+             smq::page_verdict(true, 0x7ffffff0u, 16, SM_OK) == SM_ERR_INPUT_TOO_LARGE && smq::page_verdict(true, 0x7ffffff0u, 15, SM_OK) == SM_OK,
+         "page verdict");
+  {
+    const smq::EncodeVerdict over = smq::encode_verdict(true, SM_OK, false, 0, 10, 10), pre = smq::encode_verdict(false, SMQ_ERR_HEADER, true, 32, 10, 10),
+                             fail = smq::encode_verdict(false, SM_OK, true, 32, 10, 10), tight = smq::encode_verdict(false, SM_OK, false, 0, 11, 10),
+                             fits = smq::encode_verdict(false, SM_OK, false, 0, 10, 10);
+    expect(over.status == SM_ERR_ARGUMENT && over.length == 0 && pre.status == SMQ_ERR_HEADER && pre.length == 0 && fail.status == 32 &&
+               fail.length == 0 && tight.status == SM_BUFFER_TOO_SMALL && tight.length == 11 && fits.status == SM_OK && fits.length == 10,
+           "encode verdict");
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -380,6 +575,7 @@ int main() {
     expect(smq::copy_len(p) == 0, "a page that is stepped over copies nothing");
   }
   crc_cases();
+  encode_cases();
 
   if (failures) {
     std::printf("%d failure(s)\n", failures);

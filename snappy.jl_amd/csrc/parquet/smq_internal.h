@@ -33,6 +33,30 @@ hipError_t launch_decode_plan(const DecodeChunksArgs& a, hipStream_t s);
 // chunks' results
 hipError_t launch_decode_result(const DecodeChunksArgs& a, const CrcLut* T, hipStream_t s);
 
+// ---- the encoder (smq_encode.hip) ----------------------------------------------------------------------
+struct EncodeChunksArgs {
+  const uint8_t* in;
+  const uint64_t *in_off, *in_len;
+  uint32_t nchunks, m;   // m = max_pages: the slots
+  uint64_t stage_bytes;  // the caller's bound on the stage
+  uint32_t max_fragments;
+  uint8_t* out;
+  const uint64_t *out_off, *out_cap;
+  uint64_t* out_len;
+  int32_t* status;
+  uint32_t* page_first;  // optional
+  int32_t* page_status;  // optional
+  bool table;            // pages is given
+  smq_pages pages;
+  EncodeChunks s;
+};
+// the counting walk, the scan of the slots against m, the storing walk with the slots no page took,
+// the scan of the stage slots and the fragments against their bounds
+hipError_t launch_encode_plan(const EncodeChunksArgs& a, hipStream_t s);
+// behind smm_compress_device: the level bytes to their slots' fronts, the new bodies' lengths and the
+// pages' statuses, the CRC segments, the sizes with the chunks' results, the pack
+hipError_t launch_encode_result(const EncodeChunksArgs& a, const CrcLut* T, hipStream_t s);
+
 // CRC-32 of jobs (ranges or slots): job j is in[off[j] .. +len[j]) with its segments numbered from
 // seg_first[j]; hdr->segments = seg_first[njobs].  Adds every segment's share to acc[j] (zero before).
 struct CrcJobs {

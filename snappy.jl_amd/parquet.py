@@ -14,6 +14,18 @@ promises that its codec is SNAPPY -- no footer, schema or encoding is parsed her
 and, on torch tensors resident in HBM: uncompress_column_chunks_device, crc32_device (no host
 synchronisation), last_indexed.
 
+The page encoder (include/snappy_mi355x_parquet_write.h, the same library) goes the other way: a
+chunk in its plain form -- pages with compressed_page_size == uncompressed_page_size, what a writer
+holds before compression and what parquet-cpp writes with compression=NONE -- becomes the
+compression=SNAPPY chunk the calls above read, its page headers rewritten around the new bodies:
+
+    compress_column_chunk(x, mode)             -> bytes                 one chunk (a batch of one)
+    compress_column_chunks(xs, mode)           -> list of bytes         one batched call
+    index_plain_column_chunk(x)                -> (summary, arrays, sites)   the encode walk on the host
+    rewrite_page_header(h, new_body_len, crc), compress_chunks_plan(xs), max_compressed_chunk_length(n, pages)
+
+and compress_column_chunks_device on tensors.
+
 A chunk's output is its pages' uncompressed bytes back to back, what a CPU reader holds after
 decompression; the page table says where each page's bytes lie and what its header declares.
 
@@ -25,8 +37,9 @@ import os
 
 import numpy as np
 
-from . import HERE, SnappyError, _in_arg
-from ._binding import PAGE_KEYS, PARQUET, Pages, Summary, check, collect, context_cache, device_caller, exclusive_scan, lay_out, load
+from . import HERE, SnappyError, _in_arg, _mode
+from ._binding import (PAGE_KEYS, PARQUET, PARQUET_WRITE, Pages, Summary, check, collect, context_cache, device_caller,
+                       exclusive_scan, lay_out, load)
 
 LIB_PATH = os.path.join(HERE, "libsnappy_mi355x_parquet.so")
 
@@ -42,6 +55,8 @@ PAGE_DTYPES = {"hdr_off": np.uint64, "hdr_len": np.uint32, "body_len": np.uint32
                "crc": np.uint32}
 
 PARQUET_ABI_SYMBOLS = tuple(PARQUET)  # exported symbols of include/snappy_mi355x_parquet.h (tests/test_parquet_host.py)
+PARQUET_WRITE_ABI_SYMBOLS = tuple(PARQUET_WRITE)  # and of include/snappy_mi355x_parquet_write.h (tests/test_parquet_write_host.py)
+SITE_KEYS = ("f3_at", "f3_len", "f4_at", "f4_len", "f7_at")  # a page's patch sites, SMQE_SITES words
 
 _lib = None
 
@@ -54,7 +69,7 @@ def lib():
     """Load libsnappy_mi355x_parquet.so (raises OSError if it was not built)."""
     global _lib
     if _lib is None:
-        _lib = load(LIB_PATH, PARQUET, "libsnappy_mi355x_parquet.so not built (run __graft_entry__.build())")
+        _lib = load(LIB_PATH, {**PARQUET, **PARQUET_WRITE}, "libsnappy_mi355x_parquet.so not built (run __graft_entry__.build())")
     return _lib
 
 
@@ -125,6 +140,56 @@ def chunks_plan(chunks, out_cap=None, max_pages=0x7FFFFFFF):
     return int(rc), first, out_len, status, pages.value, fragments.value
 
 
+# ---- the page encoder's host helpers (no device) ----------------------------------------------------
+
+def max_compressed_chunk_length(n, pages):
+    """smqe_max_chunk_length: an upper bound on the SNAPPY form of an n-byte plain chunk of `pages` pages."""
+    return lib().smqe_max_chunk_length(int(n), int(pages))
+
+
+def rewrite_page_header(header, new_body_len, crc=0):
+    """smqe_rewrite_header, the rewrite rule alone: the bytes of the PageHeader at the start of
+    `header` with compressed_page_size = new_body_len, its crc field (if it has one) = crc, and a v2
+    is_compressed (if it has one) true.  Raises ParquetError for a header the encode walk refuses."""
+    src, n, keep = _in_arg(header)
+    out = np.empty(n + 8, np.uint8)  # (each of the two varints grows by 4 bytes at the most)
+    got = ctypes.c_size_t(0)
+    check(lib().smqe_rewrite_header(src, n, int(new_body_len), int(crc) & 0xFFFFFFFF, out.ctypes.data, out.size,
+                                    ctypes.byref(got)), ParquetError)
+    return out[:got.value].tobytes()
+
+
+def index_plain_column_chunk(data, max_pages=None):
+    """The encode walk on the host (smqe_index) over a chunk in its plain form: (Summary, dict of numpy
+    arrays keyed as INDEX_KEYS -- the input's pages --, uint32 array [pages, 5] of the headers' patch
+    sites, columns as SITE_KEYS).  max_pages=None sizes the arrays by a counting walk first."""
+    src, n, keep = _in_arg(data)
+    s = Summary()
+    if max_pages is None:
+        s.status = lib().smqe_index(src, n, None, None, 0, ctypes.byref(s))
+        max_pages = s.nchunks
+    arrays = {k: np.zeros(max_pages, PAGE_DTYPES[k]) for k in INDEX_KEYS}
+    sites = np.zeros((max_pages, len(SITE_KEYS)), np.uint32)
+    pages = Pages(*(arrays[k].ctypes.data for k in INDEX_KEYS))
+    s.status = lib().smqe_index(src, n, ctypes.byref(pages), sites.ctypes.data, max_pages, ctypes.byref(s))
+    return s, arrays, sites
+
+
+def compress_chunks_plan(chunks, max_pages=0x7FFFFFFF):
+    """smqe_chunks_plan, the device's encode plan on the host, for a list of plain chunks: (rc, first,
+    status, out_bound, total_pages, stage_bytes, total_fragments) -- per chunk the walk's error or 0,
+    the exclusive scan of the slots (len(chunks) + 1 entries), an output capacity that always
+    suffices, and the device call's three bounds."""
+    buf, offs, lens = lay_out(chunks)
+    k = len(chunks)
+    first, status, bound = np.zeros(k + 1, np.uint32), np.zeros(k, np.int32), np.zeros(k, np.uint64)
+    pages, stage, fragments = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = lib().smqe_chunks_plan(buf.ctypes.data, offs.ctypes.data, lens.ctypes.data, k, int(max_pages), first.ctypes.data,
+                                status.ctypes.data, bound.ctypes.data, ctypes.byref(pages), ctypes.byref(stage),
+                                ctypes.byref(fragments))
+    return int(rc), first, status, bound, pages.value, stage.value, fragments.value
+
+
 # ---- host buffers -----------------------------------------------------------------------
 
 def uncompress_column_chunks(chunks, verify_crc=True, device=0, statuses=False):
@@ -164,6 +229,40 @@ def uncompress_column_chunk(data, verify_crc=True, device=0):
         raise ParquetError(e.code) from None  # (a chunk alone has no number)
 
 
+def compress_column_chunks(chunks, mode="fast", device=0, statuses=False):
+    """Compress a list of plain column chunks in one batched call (smqe_compress_chunks): a list of
+    bytes, each the compression=SNAPPY form of its chunk.  A failing chunk raises ParquetError (its
+    status, its number as `.chunk`); with statuses=True nothing is raised and the result is (that
+    list, with None for a failing chunk; list of statuses)."""
+    chunks = list(chunks)
+    if not chunks:
+        return ([], []) if statuses else []
+    buf, offs, lens = lay_out(chunks)
+    k = len(chunks)
+    cap = compress_chunks_plan(chunks)[3]
+    out_off = exclusive_scan(cap, total=True)
+    out = np.empty(max(int(out_off[-1]), 1), np.uint8)
+    out_len, status = np.zeros(k, np.uint64), np.zeros(k, np.int32)
+    check(lib().smqe_compress_chunks(context(device), buf.ctypes.data, offs.ctypes.data, lens.ctypes.data, k, out.ctypes.data,
+                                     out_off.ctypes.data, cap.ctypes.data, out_len.ctypes.data, status.ctypes.data,
+                                     _mode(mode)), ParquetError)
+    codes = status.tolist()
+    if not statuses:
+        for c, code in enumerate(codes):
+            if code:
+                raise ParquetError(code, c)
+    res = collect(out, out_off, out_len, codes)
+    return (res, codes) if statuses else res
+
+
+def compress_column_chunk(data, mode="fast", device=0):
+    """One plain column chunk: its compression=SNAPPY form."""
+    try:
+        return compress_column_chunks([data], mode=mode, device=device)[0]
+    except ParquetError as e:
+        raise ParquetError(e.code) from None  # (a chunk alone has no number)
+
+
 # ---- device API (torch tensors resident in HBM; asynchronous on `stream`) ---------------------
 
 _device = device_caller(lib, context, ParquetError)
@@ -187,6 +286,23 @@ def uncompress_column_chunks_device(d_in, d_in_off, d_in_len, max_pages, max_fra
             d_page_status)
 
 
+def compress_column_chunks_device(d_in, d_in_off, d_in_len, max_pages, stage_bytes, max_fragments, d_out, d_out_off, d_out_cap,
+                                  d_out_len, d_status, mode="fast", d_page_first=None, d_page_status=None, d_pages=None,
+                                  stream=None, device=None):
+    """smqe_compress_chunks_device: the plain chunk c = d_in[d_in_off[c] : d_in_off[c] + d_in_len[c]]
+    becomes a compression=SNAPPY chunk in d_out[d_out_off[c] : d_out_off[c] + d_out_cap[c]]; per chunk
+    d_out_len (int64) and d_status (int32).  max_pages, stage_bytes and max_fragments are
+    compress_chunks_plan's three totals (or bounds on them).  Optional, both or neither: d_page_first
+    int32[nchunks + 1], d_page_status int32[max_pages].  Optional: d_pages, a dict of tensors of
+    max_pages entries keyed as INDEX_KEYS, the OUTPUT chunks' page table.  Nothing is synchronised."""
+    pages = None
+    if d_pages is not None:
+        pages = ctypes.byref(Pages(*(d_pages[k].data_ptr() for k in INDEX_KEYS)))
+    _device("smqe_compress_chunks_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), int(max_pages),
+            int(stage_bytes), int(max_fragments), d_out, d_out_off, d_out_cap, d_out_len, d_status, d_page_first, pages,
+            d_page_status, _mode(mode))
+
+
 def crc32_device(d_in, d_off, d_len, d_crc, stream=None, device=None):
     """smq_crc32_device: d_crc[i] (int32, the CRC's 32 bits) = the CRC-32 (zlib.crc32) of
     d_in[d_off[i] : d_off[i] + d_len[i]]; d_off and d_len int64.  Nothing is synchronised."""
@@ -199,6 +315,8 @@ def last_indexed(device=0):
     return int(lib().smq_ctx_last_indexed(context(device)))
 
 
-__all__ = ["PARQUET_ABI_SYMBOLS", "INDEX_KEYS", "ParquetError", "uncompress_column_chunk", "uncompress_column_chunks",
-           "index_column_chunk", "length_uncompressed", "chunks_plan", "max_pages", "uncompress_column_chunks_device",
-           "crc32_device", "last_indexed", "status_message", "version"]
+__all__ = ["PARQUET_ABI_SYMBOLS", "PARQUET_WRITE_ABI_SYMBOLS", "INDEX_KEYS", "SITE_KEYS", "ParquetError",
+           "uncompress_column_chunk", "uncompress_column_chunks", "index_column_chunk", "length_uncompressed", "chunks_plan",
+           "max_pages", "uncompress_column_chunks_device", "crc32_device", "last_indexed", "status_message", "version",
+           "compress_column_chunk", "compress_column_chunks", "compress_chunks_plan", "index_plain_column_chunk",
+           "rewrite_page_header", "max_compressed_chunk_length", "compress_column_chunks_device"]
