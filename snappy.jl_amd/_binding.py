@@ -1,5 +1,5 @@
-"""What the six ctypes bindings of this package share (__init__.py, framing.py, multi.py, blocks.py, orc.py,
-parquet.py): the
+"""What the seven ctypes bindings of this package share (__init__.py, framing.py, multi.py, blocks.py, orc.py,
+parquet.py, avro.py): the
 prototype table of each library, the loader and the per-device context cache, the status, stream
 and device rules of the device wrappers, and the layout of a batch in one host buffer.
 
@@ -10,11 +10,12 @@ A prototype is "<return> <arguments>", one letter per C type:
     Z size_t*     U uint32_t*    Q uint64_t*          (results the wrappers pass by reference)
     C smf_chunks*                S smf_summary* / smb_summary* / smo_summary* / smq_summary* (one layout)
     B smb_chunks*                O smo_chunks*                G smq_pages*
+    A sma_blocks*                Y sma_summary*
 
 tests/test_bindings.py holds every entry against the declaration in include/*.h
 (tests/test_blocks_host.py: the BLOCKS table; tests/test_orc_host.py: ORC;
 tests/test_multi_range_host.py: MULTI_RANGE; tests/test_parquet_host.py: PARQUET;
-tests/test_parquet_write_host.py: PARQUET_WRITE).
+tests/test_parquet_write_host.py: PARQUET_WRITE; tests/test_avro_host.py: AVRO).
 """
 import ctypes
 import os
@@ -48,6 +49,20 @@ class Pages(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in PAGE_KEYS]
 
 
+AVRO_BLOCK_KEYS = ("pay_off", "pay_len", "ulen", "count", "crc", "out_off")  # sma_blocks' arrays, in its order
+
+
+class AvroBlocks(ctypes.Structure):
+    """sma_blocks: six parallel arrays, one entry per block."""
+    _fields_ = [(k, ctypes.c_void_p) for k in AVRO_BLOCK_KEYS]
+
+
+class AvroSummary(ctypes.Structure):
+    """sma_summary: Summary's three fields (nblocks for nchunks), then the objects, the header's length and the marker."""
+    _fields_ = [("total_length", ctypes.c_uint64), ("nblocks", ctypes.c_uint32), ("status", ctypes.c_int32),
+                ("objects", ctypes.c_uint64), ("header_length", ctypes.c_uint64), ("sync", ctypes.c_uint8 * 16)]
+
+
 class Summary(ctypes.Structure):
     """smf_summary, and smb_summary, smo_summary and smq_summary (npages for nchunks) with the same fields."""
     _fields_ = [("total_length", ctypes.c_uint64), ("nchunks", ctypes.c_uint32), ("status", ctypes.c_int32)]
@@ -58,7 +73,7 @@ CTYPES = {
     "u": ctypes.c_uint32, "q": ctypes.c_uint64, "z": ctypes.c_size_t, "Z": ctypes.POINTER(ctypes.c_size_t),
     "U": ctypes.POINTER(ctypes.c_uint32), "Q": ctypes.POINTER(ctypes.c_uint64), "C": ctypes.POINTER(Chunks),
     "S": ctypes.POINTER(Summary), "B": ctypes.POINTER(BlockChunks), "O": ctypes.POINTER(OrcChunks),
-    "G": ctypes.POINTER(Pages),
+    "G": ctypes.POINTER(Pages), "A": ctypes.POINTER(AvroBlocks), "Y": ctypes.POINTER(AvroSummary),
 }
 
 RAW = {  # include/snappy_mi355x.h
@@ -229,6 +244,28 @@ PARQUET_WRITE = {  # include/snappy_mi355x_parquet_write.h: the page encoder, ex
     "smqe_scratch_bytes": "z uuq",
     "smqe_compress_chunks_device": "s ppppuuquppppppGpip",
     "smqe_compress_chunks": "s ppppupppppi",
+}
+
+AVRO = {  # include/snappy_mi355x_avro.h
+    "sma_status_message": "c s",
+    "sma_version": "c",
+    "sma_max_blocks": "q q",
+    "sma_max_block_length": "q q",
+    "sma_stage_length": "q q",
+    "sma_index": "s pzipAuY",
+    "sma_uncompressed_length": "s pzipZ",
+    "sma_streams_plan": "s pppuippuppppQQ",
+    "sma_streams_scratch_bytes": "z uuuq",
+    "sma_find_sync": "s ppppuppup",
+    "sma_write_header": "s pzppuppzZ",
+    "sma_ctx_create": "p i",
+    "sma_ctx_destroy": "v p",
+    "sma_ctx_last_indexed": "i p",
+    "sma_uncompress_streams_device": "s pippppuuuipppppppApp",
+    "sma_find_sync_device": "s pppppuppupp",
+    "sma_compress_streams_device": "s pppppppppuuquppppip",
+    "sma_uncompress_streams": "s pippppuipppppp",
+    "sma_compress_streams": "s pppppppppuppppi",
 }
 
 
