@@ -1,5 +1,5 @@
-"""What the seven ctypes bindings of this package share (__init__.py, framing.py, multi.py, blocks.py, orc.py,
-parquet.py, avro.py): the
+"""What the eight ctypes bindings of this package share (__init__.py, framing.py, multi.py, blocks.py, orc.py,
+parquet.py, avro.py, table.py): the
 prototype table of each library, the loader and the per-device context cache, the status, stream
 and device rules of the device wrappers, and the layout of a batch in one host buffer.
 
@@ -8,14 +8,15 @@ A prototype is "<return> <arguments>", one letter per C type:
     v void        c const char* (a returned text)     p any other pointer, as an address
     i int         s sm_status / int32_t               u uint32_t     q uint64_t     z size_t
     Z size_t*     U uint32_t*    Q uint64_t*          (results the wrappers pass by reference)
-    C smf_chunks*                S smf_summary* / smb_summary* / smo_summary* / smq_summary* (one layout)
+    C smf_chunks*                S smf_summary* / smb_summary* / smo_summary* / smq_summary* / smt_summary* (one layout)
     B smb_chunks*                O smo_chunks*                G smq_pages*
     A sma_blocks*                Y sma_summary*
 
 tests/test_bindings.py holds every entry against the declaration in include/*.h
 (tests/test_blocks_host.py: the BLOCKS table; tests/test_orc_host.py: ORC;
 tests/test_multi_range_host.py: MULTI_RANGE; tests/test_parquet_host.py: PARQUET;
-tests/test_parquet_write_host.py: PARQUET_WRITE; tests/test_avro_host.py: AVRO).
+tests/test_parquet_write_host.py: PARQUET_WRITE; tests/test_avro_host.py: AVRO;
+tests/test_table_host.py: TABLE).
 """
 import ctypes
 import os
@@ -266,6 +267,30 @@ AVRO = {  # include/snappy_mi355x_avro.h
     "sma_compress_streams_device": "s pppppppppuuquppppip",
     "sma_uncompress_streams": "s pippppuipppppp",
     "sma_compress_streams": "s pppppppppuppppi",
+}
+
+TABLE = {  # include/snappy_mi355x_table.h (smt_summary has Summary's layout)
+    "smt_status_message": "c s",
+    "smt_version": "c",
+    "smt_footer": "s pzQQQQ",
+    "smt_index_bound": "s pzQ",
+    "smt_max_blocks": "q q",
+    "smt_walk_index": "s pzqppuS",
+    "smt_block_head": "s pzqqUQ",
+    "smt_max_block_length": "q q",
+    "smt_stage_length": "q q",
+    "smt_tables_scratch_bytes": "z uuquq",
+    "smt_write_tail": "s ppuppqpzZ",
+    "smt_ctx_create": "p i",
+    "smt_ctx_destroy": "v p",
+    "smt_ctx_last_indexed": "i p",
+    "smt_index_tables_device": "s ppppuuqippppp",
+    "smt_uncompress_blocks_device": "s ppppuuipppppp",
+    "smt_uncompress_tables_device": "s ppppuuquipppppppppppp",
+    "smt_compress_blocks_device": "s pppppuuquppppppip",
+    "smt_uncompress_tables": "s ppppuippppppupppp",
+    "smt_uncompress_blocks": "s ppzppuippppp",
+    "smt_compress_blocks": "s pppppuppppppi",
 }
 
 

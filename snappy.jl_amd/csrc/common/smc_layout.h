@@ -75,6 +75,32 @@ SMC_HD inline int32_t parse_varint32(At at, uint32_t n, uint32_t& value, uint32_
   return st;
 }
 
+// A varint64 (LevelDB's GetVarint64Ptr: a block handle's offset and size) over a byte accessor: up
+// to 10 bytes of 7-bit groups, of which n exist.  Returns 0 with the value and its length (1..10),
+// or kErrVarint when it runs past n or its 10th byte is above 1 (bits past the 64th, or an 11th
+// byte).  Reads at(i) for i < min(n, 10) only, in order, and stops at the last byte.
+template <typename At>
+SMC_HD inline int32_t parse_varint64(At at, uint32_t n, uint64_t& value, uint32_t& len) {
+  value = 0;
+  len = 0;
+  for (uint32_t i = 0; i < 10; ++i) {
+    if (i >= n) break;
+    const uint64_t b = at(i);
+    if (i == 9) {
+      if (b > 1) break;
+      value |= b << 63;
+      len = 10;
+      return 0;
+    }
+    value |= (b & 0x7f) << (7 * i);
+    if (b < 0x80) {
+      len = i + 1;
+      return 0;
+    }
+  }
+  return kErrVarint;
+}
+
 // A 64 KiB block's output slot.  Two pitches, and they stay two (allocation sizes and the slots'
 // alignment are behaviour): framing rounds the bound up to 16 bytes, multi takes the raw fragment
 // compressor's slot (the bound + 8, rounded up to 256).
