@@ -7,7 +7,6 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <algorithm>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -16,6 +15,7 @@
 #include "../../../include/snappy_mi355x_parquet.h"
 #include "../common/smc_hip_host.h"
 #include "../common/smc_layout.h"
+#include "../common/smc_staging.h"
 #include "sma_format.h"
 #include "sma_internal.h"
 
@@ -167,30 +167,14 @@ sm_status sma_compress_streams_device(sma_ctx* ctx, const uint8_t* d_in, const u
 
 }  // extern "C"
 
-// ---- host buffers --------------------------------------------------------------------------------
-namespace {
-
-constexpr uint64_t round16(uint64_t n) { return (n + 15) / 16 * 16; }
-
-// uploads n elements of a host array behind one another in the ctx's argument scratch
-struct ArgUpload {
-  smc::Carve c;
-  hipStream_t s;
-  template <typename T>
-  T* put(const T* host, size_t n, hipError_t& e) {
-    T* const d = c.take<T>(n);
-    if (e == hipSuccess && host && n) e = hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, s);
-    return d;
-  }
-};
-
-}  // namespace
+// ---- host buffers (../common/smc_staging.h) ------------------------------------------------------
+using smc::round16;
 
 extern "C" {
 
 // The streams' bytes packed behind one another in one staging block (one upload), and room for
 // every stream's output at a 16-byte boundary of the device buffer (one download; each stream's
-// own bytes then go to the caller's place), as the blocks library's host-buffer calls.
+// own bytes then go to the caller's place); the objects come back beside the lengths.
 sm_status sma_uncompress_streams(sma_ctx* ctx, int kind, const uint8_t* in, const uint64_t* in_off,
                                  const uint64_t* in_len, const uint8_t* sync, uint32_t nstreams, int verify_crc,
                                  uint8_t* out, const uint64_t* out_off, const uint64_t* out_cap, uint64_t* out_len,
@@ -205,34 +189,24 @@ sm_status sma_uncompress_streams(sma_ctx* ctx, int kind, const uint8_t* in, cons
   const sm_status planned = sma_streams_plan(in, in_off, in_len, nstreams, kind, sync, out_cap, sma::kMaxStreams, nullptr,
                                              room.data(), status, nullptr, &blocks, &fragments);
   if (planned != SM_OK) return planned == SM_BUFFER_TOO_SMALL ? (sm_status)SM_ERR_INPUT_TOO_LARGE : planned;
-  std::vector<uint64_t> h_in_off(nstreams), h_out_off(nstreams);
-  uint64_t in_total = 0, out_total = 0;
   for (uint32_t r = 0; r < nstreams; ++r) {
     if (status[r] != SM_OK) room[r] = 0;  // (not decoded)
     if (room[r] && !out) return SM_ERR_ARGUMENT;
-    h_in_off[r] = in_total;
-    in_total += in_len[r];
-    h_out_off[r] = out_total;
-    out_total += round16(room[r]);
   }
   if (fragments > sma::kMaxStreams) fragments = 0;  // (a hint: such a batch decodes in stream order)
-  std::vector<uint8_t> bytes((size_t)in_total);
-  for (uint32_t r = 0; r < nstreams; ++r)
-    if (in_len[r]) memcpy(bytes.data() + h_in_off[r], in + in_off[r], (size_t)in_len[r]);
+  const StreamStaging h(in, in_off, in_len, nstreams, room.data());
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
+  const StagingBufs b{ctx->io_in, ctx->io_out, ctx->sarg, ctx->stream};
   hipStream_t s = ctx->stream;
-  // (a byte of each at the least: the device call wants both pointers)
-  SM_CHECK(ctx->io_in.ensure(std::max<size_t>(bytes.size(), 1)));
-  SM_CHECK(ctx->io_out.ensure(std::max<size_t>((size_t)out_total, 1)));
   const size_t n = nstreams;
-  SM_CHECK(ctx->sarg.ensure(6 * round16(8 * n) + round16(4 * n) + round16(16 * n)));
+  SM_PASS(ensure_staging(b, h.bytes.size(), (size_t)h.out_total, 6 * round16(8 * n) + round16(4 * n) + round16(16 * n)));
   ArgUpload up{smc::Carve{(uintptr_t)ctx->sarg.p}, s};
   hipError_t e = hipSuccess;
-  if (!bytes.empty()) e = hipMemcpyAsync(ctx->io_in.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s);
-  const uint64_t* const d_in_off = up.put(h_in_off.data(), n, e);
+  if (!h.bytes.empty()) e = hipMemcpyAsync(ctx->io_in.p, h.bytes.data(), h.bytes.size(), hipMemcpyHostToDevice, s);
+  const uint64_t* const d_in_off = up.put(h.in_off.data(), n, e);
   const uint64_t* const d_in_len = up.put(in_len, n, e);
-  const uint64_t* const d_out_off = up.put(h_out_off.data(), n, e);
+  const uint64_t* const d_out_off = up.put(h.out_off.data(), n, e);
   const uint64_t* const d_out_cap = up.put(out_cap, n, e);
   uint64_t* const d_out_len = up.put((const uint64_t*)nullptr, n, e);
   uint64_t* const d_objects = up.put((const uint64_t*)nullptr, n, e);
@@ -242,14 +216,12 @@ sm_status sma_uncompress_streams(sma_ctx* ctx, int kind, const uint8_t* in, cons
   SM_PASS(sma_uncompress_streams_device(ctx, kind, (const uint8_t*)ctx->io_in.p, d_in_off, d_in_len, d_sync, nstreams,
                                         (uint32_t)blocks, (uint32_t)fragments, verify_crc, (uint8_t*)ctx->io_out.p, d_out_off,
                                         d_out_cap, d_out_len, d_status, d_objects, nullptr, nullptr, nullptr, s));
-  std::vector<uint8_t> decoded((size_t)out_total);
-  SM_CHECK(hipMemcpyAsync(out_len, d_out_len, 8 * n, hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipMemcpyAsync(status, d_status, 4 * n, hipMemcpyDeviceToHost, s));
+  std::vector<uint8_t> decoded;
+  SM_PASS(download_results(b, d_out_len, d_status, n, out_len, status));
   if (objects) SM_CHECK(hipMemcpyAsync(objects, d_objects, 8 * n, hipMemcpyDeviceToHost, s));
-  if (!decoded.empty()) SM_CHECK(hipMemcpyAsync(decoded.data(), ctx->io_out.p, decoded.size(), hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipStreamSynchronize(s));
+  SM_PASS(download_output(b, h.out_total, decoded));
   for (uint32_t r = 0; r < nstreams; ++r)
-    if (room[r]) memcpy(out + out_off[r], decoded.data() + h_out_off[r], (size_t)room[r]);
+    if (room[r]) memcpy(out + out_off[r], decoded.data() + h.out_off[r], (size_t)room[r]);
   return SM_OK;
 }
 
@@ -294,12 +266,12 @@ sm_status sma_compress_streams(sma_ctx* ctx, const uint8_t* in, const uint32_t* 
   }
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
+  const StagingBufs b{ctx->io_in, ctx->io_out, ctx->sarg, ctx->stream};
   hipStream_t s = ctx->stream;
-  SM_CHECK(ctx->io_in.ensure(std::max<size_t>(bytes.size(), 1)));
-  SM_CHECK(ctx->io_out.ensure(std::max<size_t>((size_t)out_total, 1)));
   const size_t n = nstreams;
-  SM_CHECK(ctx->sarg.ensure(4 * round16(8 * n) + 2 * round16(4 * (n + 1)) + round16(16 * n) + 2 * round16(8 * (size_t)m) +
-                            round16(4 * (size_t)m)));
+  SM_PASS(ensure_staging(b, bytes.size(), (size_t)out_total,
+                         4 * round16(8 * n) + 2 * round16(4 * (n + 1)) + round16(16 * n) + 2 * round16(8 * (size_t)m) +
+                             round16(4 * (size_t)m)));
   ArgUpload up{smc::Carve{(uintptr_t)ctx->sarg.p}, s};
   hipError_t e = hipSuccess;
   if (!bytes.empty()) e = hipMemcpyAsync(ctx->io_in.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s);
@@ -317,11 +289,9 @@ sm_status sma_compress_streams(sma_ctx* ctx, const uint8_t* in, const uint32_t* 
   SM_PASS(sma_compress_streams_device(ctx, (const uint8_t*)ctx->io_in.p, d_first, d_block_off, d_block_len, d_block_count, d_sync,
                                       head_len ? d_head_off : nullptr, head_len ? d_head_len : nullptr, nstreams, m, stage,
                                       (uint32_t)fragments, (uint8_t*)ctx->io_out.p, d_out_off, d_out_len, d_status, mode, s));
-  std::vector<uint8_t> packed((size_t)out_total);
-  SM_CHECK(hipMemcpyAsync(out_len, d_out_len, 8 * n, hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipMemcpyAsync(status, d_status, 4 * n, hipMemcpyDeviceToHost, s));
-  if (!packed.empty()) SM_CHECK(hipMemcpyAsync(packed.data(), ctx->io_out.p, packed.size(), hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipStreamSynchronize(s));
+  std::vector<uint8_t> packed;
+  SM_PASS(download_results(b, d_out_len, d_status, n, out_len, status));
+  SM_PASS(download_output(b, out_total, packed));
   for (uint32_t r = 0; r < nstreams; ++r) {
     if (out_len[r] > room[r]) return SM_ERR_DEVICE;
     if (status[r] == SM_OK && out_len[r]) memcpy(out + out_off[r], packed.data() + h_out_off[r], (size_t)out_len[r]);

@@ -16,55 +16,6 @@ namespace sma {
 
 namespace {
 
-constexpr uint32_t kWalkWaves = 4;  // streams a workgroup of the walkers takes: one per wave
-constexpr uint32_t kWindow = 64;    // bytes of a stream a wave holds: one per lane
-
-// The walker's fetch (walk_stream), by one wave.  The header's map and a block's two longs are runs
-// of variable-length fields of no fixed place, so the wave keeps a window of kWindow bytes of its
-// stream, a byte a lane, read by one load; fetch(pos) reads the byte out of its lane into a scalar
-// register, so the parse -- its arithmetic and its branches -- is the wave's, not a lane's.  When
-// the cursor leaves the window the window is read again from the cursor on: a block costs one load
-// at its payload's end (the checksum, the marker and the next block's longs share it) unless its
-// longs straddle a window.  Bytes at or behind the stream's end are not read.
-struct WaveFetch {
-  const uint8_t* in;
-  uint64_t n;
-  uint32_t lane;
-  uint64_t base = 0;
-  uint32_t mine = 0;
-  bool valid = false;
-  __device__ uint32_t operator()(uint64_t pos) {
-    if (!valid || pos < base || pos - base >= kWindow) {
-      base = pos;
-      mine = base + lane < n ? in[base + lane] : 0u;
-      valid = true;
-    }
-    const uint32_t at = __builtin_amdgcn_readfirstlane((uint32_t)(pos - base));
-    return (uint32_t)__builtin_amdgcn_readlane((int)mine, (int)at) & 0xffu;
-  }
-};
-
-// the stream of this wave of walkers, as the wave's own value
-__device__ inline uint32_t walker_stream() {
-  return __builtin_amdgcn_readfirstlane(blockIdx.x * kWalkWaves + (threadIdx.x >> 6));
-}
-
-// The exclusive scan of value(i), i < n, by one workgroup (block_scan's contract: 256 threads, sh
-// its 4 u64 of LDS), tile by tile: each(i, value(i), the sum before i).  Returns the total to every thread.
-template <typename Value, typename Each>
-__device__ inline uint64_t tile_scan(uint32_t n, uint64_t* sh, Value value, Each each) {
-  uint64_t carry = 0;
-  for (uint32_t b0 = 0; b0 < n; b0 += 256) {  // (uniform: every thread takes every tile)
-    const uint32_t i = b0 + threadIdx.x;
-    const uint64_t v = i < n ? value(i) : 0u;
-    uint64_t total;
-    const uint64_t ex = smc::block_scan(v, sh, total);
-    if (i < n) each(i, v, carry + ex);
-    carry += total;
-  }
-  return carry;
-}
-
 __device__ inline void store_block(const sma_blocks& t, uint32_t j, uint64_t at, const Block& b) {
   t.pay_off[j] = b.pay_off;
   t.pay_len[j] = b.pay_len;
@@ -80,9 +31,9 @@ __device__ inline void store_block(const sma_blocks& t, uint32_t j, uint64_t at,
 // The counting walk, one wave per stream: what the stream gets (stream_plan) before any byte of it
 // is decoded.  The walks of a workgroup's waves are independent: no barrier in here.
 __global__ __launch_bounds__(256) void k_avro_count(DecodeStreamsArgs a) {
-  const uint32_t r = walker_stream();
+  const uint32_t r = smc::walker_index();
   if (r >= a.nstreams) return;
-  WaveFetch fetch{a.in + a.in_off[r], a.in_len[r], threadIdx.x & 63};
+  smc::WindowFetch fetch{a.in + a.in_off[r], a.in_len[r], threadIdx.x & 63};
   const uint8_t* const marker = a.kind == SMA_INPUT_BLOCKS ? a.sync + (uint64_t)kSync * r : nullptr;
   const Walk w = walk_stream(a.kind, a.in_len[r], fetch, marker, [](uint32_t, uint64_t, const Block&) {});
   if (fetch.lane == 0) {
@@ -95,24 +46,10 @@ __global__ __launch_bounds__(256) void k_avro_count(DecodeStreamsArgs a) {
   }
 }
 
-// The exclusive scan of the streams' slots against the bound m, by one workgroup: first[0,
-// nstreams] (and the caller's copy) and the header.  Over the bound the scan is not used (it
-// saturates).
+// the exclusive scan of the streams' slots against the bound m, by one workgroup
 __global__ __launch_bounds__(256) void k_avro_scan(DecodeStreamsArgs a) {
   __shared__ uint64_t sh[4];
-  const uint64_t sum = tile_scan(
-      a.nstreams, sh, [&](uint32_t r) { return a.s.count[r]; },
-      [&](uint32_t r, uint64_t, uint64_t at) {
-        a.s.first[r] = smc::sat32(at);
-        if (a.block_first) a.block_first[r] = smc::sat32(at);
-      });
-  if (threadIdx.x == 0) {
-    const bool over = sum > a.m;
-    a.s.first[a.nstreams] = smc::sat32(sum);
-    if (a.block_first) a.block_first[a.nstreams] = smc::sat32(sum);
-    a.s.hdr->over = over ? 1u : 0u;
-    a.s.hdr->total = over ? 0u : (uint32_t)sum;
-  }
+  smc::count_scan(a.nstreams, a.m, [&](uint32_t r) { return a.s.count[r]; }, a.s.first, a.block_first, a.s.hdr, sh);
 }
 
 // The slots no block took (all of them over the bound) become empty streams with no room, which
@@ -132,12 +69,12 @@ __global__ __launch_bounds__(256) void k_avro_fill(DecodeStreamsArgs a) {
     a.s.stream[j] = kNoSlot;
     if (a.table) store_block(a.blocks, (uint32_t)j, 0, Block{0, 0, 0, 0, 0});
   }
-  const uint32_t r = walker_stream();
+  const uint32_t r = smc::walker_index();
   if (r >= a.nstreams || a.s.hdr->over) return;
   const uint32_t cnt = a.s.count[r], base = a.s.first[r];
   if (cnt == 0) return;
   const uint64_t in_off = a.in_off[r], out_off = a.out_off[r];
-  WaveFetch fetch{a.in + in_off, a.in_len[r], threadIdx.x & 63};
+  smc::WindowFetch fetch{a.in + in_off, a.in_len[r], threadIdx.x & 63};
   const uint32_t lane = fetch.lane;
   const uint8_t* const marker = a.kind == SMA_INPUT_BLOCKS ? a.sync + (uint64_t)kSync * r : nullptr;
   walk_stream(a.kind, a.in_len[r], fetch, marker, [&](uint32_t k, uint64_t at, const Block& b) {
@@ -155,7 +92,7 @@ __global__ __launch_bounds__(256) void k_avro_fill(DecodeStreamsArgs a) {
 }
 
 hipError_t launch_decode_plan(const DecodeStreamsArgs& a, hipStream_t s) {
-  const uint32_t walkers = (a.nstreams + kWalkWaves - 1) / kWalkWaves;
+  const uint32_t walkers = (a.nstreams + smc::kWalkWaves - 1) / smc::kWalkWaves;
   hipLaunchKernelGGL(k_avro_count, dim3(walkers), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_avro_scan, dim3(1), dim3(256), 0, s, a);
   if (a.m) hipLaunchKernelGGL(k_avro_fill, dim3(walkers), dim3(256), 0, s, a);
@@ -181,7 +118,7 @@ __global__ __launch_bounds__(256) void k_avro_result(DecodeStreamsArgs a) {
   if (r >= a.nstreams) return;
   const bool over = a.s.hdr->over != 0;
   const uint32_t fail = over ? kNoSlot : a.s.fail[r];
-  a.status[r] = stream_verdict(over, a.s.pre[r], fail, fail != kNoSlot ? a.s.slot_status[fail] : (int32_t)SM_OK);
+  a.status[r] = smc::plan_verdict(over, a.s.pre[r], fail, fail != kNoSlot ? a.s.slot_status[fail] : (int32_t)SM_OK);
   a.out_len[r] = over ? 0 : a.s.length[r];
   if (a.objects) a.objects[r] = over ? 0 : a.s.objects[r];
 }
@@ -283,7 +220,7 @@ __global__ __launch_bounds__(256) void k_cavro_plan(CompressStreamsArgs a) {
   const uint32_t total = a.block_first[a.nstreams];
   const uint32_t used = total > a.m ? 0u : total;
   uint64_t mine = 0;  // the fragments of this thread's blocks: a sum, not a scan
-  const uint64_t stage = tile_scan(
+  const uint64_t stage = smc::tile_scan(
       used, sh,
       [&](uint32_t j) {
         const uint32_t len = a.block_len[j];
@@ -312,7 +249,7 @@ __global__ __launch_bounds__(256) void k_cavro_slots(CompressStreamsArgs a) {
   a.s.in_len[j] = len;
   a.s.crc_len[j] = len;
   a.s.count[j] = used ? a.block_count[j] : 0u;
-  a.s.stream[j] = used ? slot_stream(a.block_first, a.nstreams, j) : kNoSlot;
+  a.s.stream[j] = used ? smc::slot_owner(a.block_first, a.nstreams, j) : kNoSlot;
   if (!used) a.s.slot_off[j] = a.stage_bytes;  // (the spare bytes behind the stage: an empty raw stream harms nothing there)
 }
 
@@ -329,7 +266,7 @@ hipError_t launch_compress_plan(const CompressStreamsArgs& a, hipStream_t s) {
 __global__ __launch_bounds__(256) void k_cavro_sizes(CompressStreamsArgs a) {
   __shared__ uint64_t sh[4];
   const uint32_t used = a.s.hdr->total;
-  const uint64_t sum = tile_scan(
+  const uint64_t sum = smc::tile_scan(
       used, sh,
       [&](uint32_t j) -> uint64_t {
         if (block_ok(a.s.comp_status[j], a.s.comp_len[j], a.s.in_len[j])) return block_bytes(a.s.count[j], a.s.comp_len[j]);

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "../common/smc_staging.h"
 #include "smb_format.h"
 #include "smb_streams.h"
 
@@ -263,21 +264,52 @@ int main() {
              smb_streams_scratch_bytes(4, 7, 9) >= smb_streams_scratch_bytes(3, 7, 9) && smb_streams_scratch_bytes(0, 0, 0) > 0,
          "streams scratch bytes");
   // the verdict and the slot search
-  expect(smb::stream_verdict(true, SM_OK, smb::kNoSlot, 0) == SM_ERR_ARGUMENT &&
-             smb::stream_verdict(true, SMB_ERR_TRUNCATED, 3, 19) == SM_ERR_ARGUMENT &&
-             smb::stream_verdict(false, SMB_ERR_TRUNCATED, 3, 19) == SMB_ERR_TRUNCATED &&
-             smb::stream_verdict(false, SM_OK, 3, 19) == 19 && smb::stream_verdict(false, SM_OK, 0, 19) == 19 &&
-             smb::stream_verdict(false, SM_OK, smb::kNoSlot, 19) == SM_OK,
+  expect(smc::plan_verdict(true, SM_OK, smb::kNoSlot, 0) == SM_ERR_ARGUMENT &&
+             smc::plan_verdict(true, SMB_ERR_TRUNCATED, 3, 19) == SM_ERR_ARGUMENT &&
+             smc::plan_verdict(false, SMB_ERR_TRUNCATED, 3, 19) == SMB_ERR_TRUNCATED &&
+             smc::plan_verdict(false, SM_OK, 3, 19) == 19 && smc::plan_verdict(false, SM_OK, 0, 19) == 19 &&
+             smc::plan_verdict(false, SM_OK, smb::kNoSlot, 19) == SM_OK,
          "stream verdict");
   {
     uint32_t* first = (uint32_t*)std::malloc(6 * sizeof(uint32_t));
     const uint32_t f[6] = {0, 0, 2, 2, 2, 5};  // streams 1 and 4 have slots
     std::memcpy(first, f, sizeof(f));
     const uint32_t want[5] = {1, 1, 4, 4, 4};
-    for (uint32_t j = 0; j < 5; ++j) expect(smb::slot_stream(first, 5, j) == want[j], "slot stream");
+    for (uint32_t j = 0; j < 5; ++j) expect(smc::slot_owner(first, 5, j) == want[j], "slot stream");
     first[1] = 1;
-    expect(smb::slot_stream(first, 1, 0) == 0, "slot stream: one stream");
+    expect(smc::slot_owner(first, 1, 0) == 0, "slot stream: one stream");
     std::free(first);
+  }
+  // the host-buffer calls' staging (../common/smc_staging.h): the inputs behind one another in the
+  // order of the streams, wherever they stand in the caller's buffer (a heap block of exactly the
+  // bytes in use), each output from a 16-byte boundary, an empty stream in between, and no stream
+  {
+    const S text = "....abcdefg.xy";  // stream 0: "xy" at 12, stream 1: empty (its offset past the end), stream 2: "abcdefg" at 4
+    uint8_t* in = (uint8_t*)std::malloc(text.size());
+    std::memcpy(in, text.data(), text.size());
+    const uint64_t off[3] = {12, 1000, 4}, len[3] = {2, 0, 7}, room[3] = {17, 0, 16};
+    const StreamStaging h(in, off, len, 3, room);
+    expect(h.bytes.size() == 9 && std::memcmp(h.bytes.data(), "xyabcdefg", 9) == 0, "staging: the packed bytes");
+    expect(h.in_off[0] == 0 && h.in_off[1] == 2 && h.in_off[2] == 2, "staging: input offsets");
+    expect(h.out_off[0] == 0 && h.out_off[1] == 32 && h.out_off[2] == 32 && h.out_total == 48, "staging: output offsets");
+    std::free(in);
+    const uint64_t none = 0;
+    const StreamStaging e(nullptr, &none, &none, 1, &none);  // one empty stream of a null buffer
+    expect(e.bytes.empty() && e.in_off[0] == 0 && e.out_off[0] == 0 && e.out_total == 0, "staging: an empty stream");
+    const StreamStaging z(nullptr, nullptr, nullptr, 0, nullptr);
+    expect(z.bytes.empty() && z.in_off.empty() && z.out_off.empty() && z.out_total == 0, "staging: no stream");
+    expect(smc::round16(0) == 0 && smc::round16(1) == 16 && smc::round16(16) == 16 && smc::round16(17) == 32 &&
+               smc::round16(0xfffffffffffffff0ull) == 0xfffffffffffffff0ull,
+           "round16");
+    // the call's arrays: six of them, each from a 16-byte boundary, none for no stream
+    const StreamCallArrays a = carve_stream_call(4096, 3);
+    expect((uintptr_t)a.in_off == 4096 && (uintptr_t)a.in_len == 4096 + 32 && (uintptr_t)a.out_off == 4096 + 64 &&
+               (uintptr_t)a.out_cap == 4096 + 96 && (uintptr_t)a.out_len == 4096 + 128 && (uintptr_t)a.status == 4096 + 160 &&
+               a.end == 4096 + 176,
+           "stream call arrays");
+    expect(stream_call_bytes(0) == 0 && stream_call_bytes(1) == 96 && stream_call_bytes(3) == 176 &&
+               stream_call_bytes(4) == 5 * 32 + 16,
+           "stream call bytes");
   }
   // the prefix bytes the pack kernel writes
   {

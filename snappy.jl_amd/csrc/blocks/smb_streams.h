@@ -1,24 +1,21 @@
 // smb_streams.h -- the rules of the batched calls (smb_uncompress_streams_device,
 // smb_compress_streams_device), shared by their kernels (smb_kernels.hip) and the host
 // (smb_streams_plan in smb_host.cpp, which the sanitizer driver runs): what a walked stream of a
-// batch gets, a slot's and a stream's verdict, and the scratch layouts.  The walk itself is
+// batch gets and the scratch layouts (the slot rules are ../common/smc_slots.h's).  The walk itself is
 // walk_blocks (smb_format.h).  Plain functions, compiled for the host and the device alike, so the
 // host checker tests the code the kernels run.  Not part of the public ABI.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../common/smc_slots.h"
 #include "smb_format.h"
 
 namespace smb {
 
 constexpr uint32_t kMaxStreams = 0x7fffffffu;  // more streams, chunks or blocks: SM_ERR_ARGUMENT
-constexpr uint32_t kNoSlot = 0xffffffffu;      // a slot of no stream; a stream without a failing slot
-
-struct Header {    // a plan's words for the kernels behind it
-  uint32_t total;  // slots in use (0 over the bound: nothing is decoded or packed)
-  uint32_t over;   // the streams need more slots than the caller's bound
-};
+using smc::kNoSlot;                            // a slot of no stream; a stream without a failing slot
+using Header = smc::PlanHeader;
 
 struct StreamPlan {
   int32_t status;  // the walk's error, SM_BUFFER_TOO_SMALL, or SM_OK: what is known before any decode
@@ -34,25 +31,8 @@ SMC_HD inline StreamPlan stream_plan(const Walk& w, uint64_t cap) {
   return p;
 }
 
-// A stream's status: SM_ERR_ARGUMENT over the caller's bound, else the plan's, else its first
-// failing slot's raw decoder status (fail == kNoSlot: none failed).
-SMC_HD inline int32_t stream_verdict(bool over, int32_t pre, uint32_t fail, int32_t fail_status) {
-  if (over) return SM_ERR_ARGUMENT;
-  if (pre != SM_OK) return pre;
-  return fail != kNoSlot ? fail_status : (int32_t)SM_OK;
-}
-
-// The stream of slot j: first[r] <= j < first[r + 1] in the scan first[0, nstreams] (of equal
-// entries the last one, so streams without slots are passed over).  j < first[nstreams].
-SMC_HD inline uint32_t slot_stream(const uint32_t* first, uint32_t nstreams, uint32_t j) {
-  uint32_t lo = 0, hi = nstreams;  // first[lo] <= j < first[hi]
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (first[mid] <= j) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
+// (A stream's status is smc::plan_verdict over its first failing slot's raw decoder status; the
+// stream of a slot is its smc::slot_owner in the scan first[0, nstreams].)
 
 // ---- scratch (smc::Carve: a null base measures) ------------------------------------------------
 struct DecodeStreams {

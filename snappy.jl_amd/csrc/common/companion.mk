@@ -6,7 +6,8 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 MK = ../common/companion.mk
-HDRS += ../common/smc_layout.h ../common/smc_device.h ../common/smc_hip_host.h ../../../include/snappy_mi355x.h
+HDRS += ../common/smc_layout.h ../common/smc_slots.h ../common/smc_device.h ../common/smc_hip_host.h ../common/smc_staging.h \
+        ../../../include/snappy_mi355x.h
 # the version: a hash of the sources, headers, Makefiles, target and compiler (as ../Makefile)
 VERSION ?= src-$(shell (cat $(SRCS) $(HOSTSRCS) $(HDRS) Makefile $(MK); echo '$(EXTRA) $(ARCH)'; $(HIPCC) --version) 2>/dev/null | sha1sum | cut -c1-10)
 EXTRA ?=

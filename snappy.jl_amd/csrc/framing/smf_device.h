@@ -1,7 +1,6 @@
 // smf_device.h -- the device helpers the framing kernels share (smf_kernels.hip, smf_range.hip,
-// smf_streams.hip): the one-wave fetch of the chunk walk, the tiled scan of one workgroup and the
-// scan of the groups' slot counts over it, and the packing of one chunk.  All inline: they vanish
-// into their callers.  Not part of the public ABI.
+// smf_streams.hip): the one-wave fetch of the chunk walk and the packing of one chunk (the scans are
+// ../common/smc_device.h's).  All inline: they vanish into their callers.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,39 +28,12 @@ struct WaveFetch {
   }
 };
 
-// The exclusive scan of value(i), i < n, by one workgroup (block_scan's contract: 256 threads, sh
-// its 4 u64 of LDS), tile by tile: each(i, value(i), the sum before i).  Returns the total to every thread.
-template <typename Value, typename Each>
-__device__ inline uint64_t tile_scan(uint32_t n, uint64_t* sh, Value value, Each each) {
-  uint64_t carry = 0;
-  for (uint32_t b0 = 0; b0 < n; b0 += 256) {  // (uniform: every thread takes every tile)
-    const uint32_t i = b0 + threadIdx.x;
-    const uint64_t v = i < n ? value(i) : 0u;
-    uint64_t total;
-    const uint64_t ex = smc::block_scan(v, sh, total);
-    if (i < n) each(i, v, carry + ex);
-    carry += total;
-  }
-  return carry;
-}
-
-// The exclusive scan of cnt(r) over the groups against the bound m, by one workgroup: first[0,
-// ngroups] (and first_out, if given) and the header.  Over the bound the scan is not used (it
-// saturates).
+// The exclusive scan of cnt(r) over the groups against the bound m, by one workgroup: the shared
+// count scan, under the name the framing kernels know it by.
 template <typename Count>
 __device__ inline void scan_counts(uint32_t ngroups, uint32_t m, Count cnt, uint32_t* first, uint32_t* first_out,
                                    GroupHeader* hdr, uint64_t* sh) {
-  const uint64_t sum = tile_scan(ngroups, sh, cnt, [&](uint32_t r, uint64_t, uint64_t at) {
-    first[r] = smc::sat32(at);
-    if (first_out) first_out[r] = smc::sat32(at);
-  });
-  if (threadIdx.x == 0) {
-    const bool over = sum > m;
-    first[ngroups] = smc::sat32(sum);
-    if (first_out) first_out[ngroups] = smc::sat32(sum);
-    hdr->over = over ? 1u : 0u;
-    hdr->total = over ? 0u : (uint32_t)sum;
-  }
+  smc::count_scan(ngroups, m, cnt, first, first_out, hdr, sh);
 }
 
 // One chunk at d, by the workgroups (blockIdx.x, *) of k_frame_pack and k_streams_pack: the header

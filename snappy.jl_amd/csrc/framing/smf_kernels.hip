@@ -236,7 +236,7 @@ hipError_t launch_frame_result(uint64_t* d_len, uint64_t len, const smf_summary*
 __global__ __launch_bounds__(256) void k_frame_plan(smf_chunks ch, uint32_t nchunks, uint64_t out_capacity, Slots s,
                                                     uint64_t* out_len) {
   __shared__ uint64_t sh[4];
-  const uint64_t total = tile_scan(nchunks, sh, [&](uint32_t c) { return ch.ulen[c]; }, [&](uint32_t c, uint64_t ulen, uint64_t o) {
+  const uint64_t total = smc::tile_scan(nchunks, sh, [&](uint32_t c) { return ch.ulen[c]; }, [&](uint32_t c, uint64_t ulen, uint64_t o) {
     const uint32_t ty = ch.type[c], pl = ch.pay_len[c], u = (uint32_t)ulen;
     int32_t st = SM_OK;
     if (ty > SMF_CHUNK_UNCOMPRESSED) st = SM_ERR_ARGUMENT;

@@ -25,7 +25,7 @@ using smc::copy_bytes;
 __global__ __launch_bounds__(256) void k_chunk_offsets(const uint32_t* __restrict__ ulen, uint32_t nchunks,
                                                        uint64_t* __restrict__ chunk_off) {
   __shared__ uint64_t sh[4];
-  const uint64_t total = tile_scan(nchunks, sh, [&](uint32_t c) { return ulen[c]; },
+  const uint64_t total = smc::tile_scan(nchunks, sh, [&](uint32_t c) { return ulen[c]; },
                                    [&](uint32_t c, uint64_t, uint64_t o) { chunk_off[c] = o; });
   if (threadIdx.x == 0) chunk_off[nchunks] = total;
 }

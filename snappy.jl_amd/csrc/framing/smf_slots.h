@@ -10,16 +10,13 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../common/smc_slots.h"
 #include "smf_format.h"
 
 namespace smf {
 
-constexpr uint32_t kNoSlot = 0xffffffffu;  // a slot of no group; a group without a failing slot
-
-struct GroupHeader {  // a plan's words for the kernels behind it
-  uint32_t total;     // slots in use (0 over the bound: nothing is decoded or packed)
-  uint32_t over;      // the groups need more slots than the caller's bound
-};
+using smc::kNoSlot;  // a slot of no group; a group without a failing slot
+using GroupHeader = smc::PlanHeader;
 
 // A slot's status: why it was not decoded, else the raw decoder's status (a 0x00 chunk), else the
 // CRC's verdict.
@@ -29,12 +26,9 @@ SMC_HD inline int32_t slot_verdict(int32_t pre, uint32_t type, int32_t dec_statu
   return crc_out != crc_want ? (int32_t)SMF_ERR_CRC : (int32_t)SM_OK;
 }
 
-// A group's status: SM_ERR_ARGUMENT over the caller's bound, else the plan's, else its first
-// failing slot's (fail == kNoSlot: none failed).
+// A group's status: the shared rule, under the name the slot stage and its checker know it by.
 SMC_HD inline int32_t group_verdict(bool over, int32_t pre, uint32_t fail, int32_t fail_status) {
-  if (over) return SM_ERR_ARGUMENT;
-  if (pre != SM_OK) return pre;
-  return fail != kNoSlot ? fail_status : (int32_t)SM_OK;
+  return smc::plan_verdict(over, pre, fail, fail_status);
 }
 
 struct Slots {

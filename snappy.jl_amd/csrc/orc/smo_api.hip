@@ -6,7 +6,6 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <algorithm>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -14,35 +13,13 @@
 #include "../../../include/snappy_mi355x_multi.h"
 #include "../common/smc_hip_host.h"
 #include "../common/smc_layout.h"
+#include "../common/smc_staging.h"
 #include "smo_format.h"
 #include "smo_internal.h"
 
 #ifndef SMO_VERSION_STR
 #define SMO_VERSION_STR "dev"
 #endif
-
-namespace {
-
-struct StreamCallArrays {  // per stream, what a host-buffer call hands the device call (ctx->sarg)
-  uint64_t *in_off, *in_len, *out_off, *out_cap, *out_len;
-  int32_t* status;
-  uintptr_t end;
-};
-constexpr StreamCallArrays carve_stream_call(uintptr_t base, size_t n) {
-  smc::Carve c{base};
-  StreamCallArrays m{};
-  m.in_off = c.take<uint64_t>(n);
-  m.in_len = c.take<uint64_t>(n);
-  m.out_off = c.take<uint64_t>(n);
-  m.out_cap = c.take<uint64_t>(n);
-  m.out_len = c.take<uint64_t>(n);
-  m.status = c.take<int32_t>(n);
-  m.end = c.p;
-  return m;
-}
-constexpr size_t stream_call_bytes(size_t n) { return carve_stream_call(0, n).end; }
-
-}  // namespace
 
 struct smo_ctx {
   smm_ctx* smm = nullptr;
@@ -166,66 +143,7 @@ sm_status smo_compress_streams_device(smo_ctx* ctx, uint32_t block_size, const u
   return SM_OK;
 }
 
-}  // extern "C"
-
-// ---- host buffers --------------------------------------------------------------------------------
-namespace {
-
-// The host side of a host-buffer call, as the blocks library's: the streams' bytes packed behind
-// one another in one staging block (one upload), and room for every stream's output at a 16-byte
-// boundary of the device buffer (one download; each stream's own bytes then go to the caller's place).
-struct StreamStaging {
-  std::vector<uint8_t> bytes;
-  std::vector<uint64_t> in_off, out_off;
-  uint64_t out_total = 0;
-  StreamStaging(const uint8_t* in, const uint64_t* off, const uint64_t* len, uint32_t n, const std::vector<uint64_t>& room)
-      : in_off(n), out_off(n) {
-    uint64_t total = 0;
-    for (uint32_t r = 0; r < n; ++r) {
-      in_off[r] = total;
-      total += len[r];
-      out_off[r] = out_total;
-      out_total += (room[r] + 15) / 16 * 16;
-    }
-    bytes.resize((size_t)total);
-    for (uint32_t r = 0; r < n; ++r)
-      if (len[r]) memcpy(bytes.data() + in_off[r], in + off[r], (size_t)len[r]);
-  }
-};
-
-// uploads the staging and the arrays; out_cap may be null (compress)
-sm_status upload_stream_call(smo_ctx* ctx, const StreamStaging& h, const uint64_t* in_len, const uint64_t* out_cap,
-                             uint32_t n, StreamCallArrays& d) {
-  hipStream_t s = ctx->stream;
-  // (a byte of each at the least: the device calls want both pointers)
-  SM_CHECK(ctx->io_in.ensure(std::max<size_t>(h.bytes.size(), 1)));
-  SM_CHECK(ctx->io_out.ensure(std::max<size_t>((size_t)h.out_total, 1)));
-  SM_CHECK(ctx->sarg.ensure(stream_call_bytes(n)));
-  d = carve_stream_call((uintptr_t)ctx->sarg.p, n);
-  if (!h.bytes.empty()) SM_CHECK(hipMemcpyAsync(ctx->io_in.p, h.bytes.data(), h.bytes.size(), hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d.in_off, h.in_off.data(), 8 * (size_t)n, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d.in_len, in_len, 8 * (size_t)n, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d.out_off, h.out_off.data(), 8 * (size_t)n, hipMemcpyHostToDevice, s));
-  if (out_cap) SM_CHECK(hipMemcpyAsync(d.out_cap, out_cap, 8 * (size_t)n, hipMemcpyHostToDevice, s));
-  return SM_OK;
-}
-
-// the lengths, the statuses and the device output buffer, back on the host (synchronises)
-sm_status download_stream_call(smo_ctx* ctx, const StreamStaging& h, const StreamCallArrays& d, uint32_t n,
-                               uint64_t* out_len, int32_t* status, std::vector<uint8_t>& out) {
-  hipStream_t s = ctx->stream;
-  out.resize((size_t)h.out_total);
-  SM_CHECK(hipMemcpyAsync(out_len, d.out_len, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipMemcpyAsync(status, d.status, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
-  if (!out.empty()) SM_CHECK(hipMemcpyAsync(out.data(), ctx->io_out.p, out.size(), hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipStreamSynchronize(s));
-  return SM_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
+// ---- host buffers (../common/smc_staging.h) ------------------------------------------------------
 sm_status smo_compress_streams(smo_ctx* ctx, uint32_t block_size, const uint8_t* in, const uint64_t* in_off,
                                const uint64_t* in_len, uint32_t nstreams, uint8_t* out, const uint64_t* out_off,
                                uint64_t* out_len, int32_t* status, int mode) {
@@ -241,16 +159,17 @@ sm_status smo_compress_streams(smo_ctx* ctx, uint32_t block_size, const uint8_t*
       return SM_ERR_INPUT_TOO_LARGE;
     room[r] = smo::max_length(in_len[r], block_size);
   }
-  const StreamStaging h(in, in_off, in_len, nstreams, room);
+  const StreamStaging h(in, in_off, in_len, nstreams, room.data());
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
+  const StagingBufs b{ctx->io_in, ctx->io_out, ctx->sarg, ctx->stream};
   StreamCallArrays d;
-  SM_PASS(upload_stream_call(ctx, h, in_len, nullptr, nstreams, d));
+  SM_PASS(upload_stream_call(b, h, in_len, nullptr, nstreams, d));
   SM_PASS(smo_compress_streams_device(ctx, block_size, (const uint8_t*)ctx->io_in.p, d.in_off, d.in_len, nstreams,
                                       (uint32_t)pieces, (uint8_t*)ctx->io_out.p, d.out_off, d.out_len, d.status, mode,
                                       ctx->stream));
   std::vector<uint8_t> packed;
-  SM_PASS(download_stream_call(ctx, h, d, nstreams, out_len, status, packed));
+  SM_PASS(download_stream_call(b, h, d, nstreams, out_len, status, packed));
   for (uint32_t r = 0; r < nstreams; ++r) {
     if (out_len[r] > room[r]) return SM_ERR_DEVICE;
     if (out_len[r]) memcpy(out + out_off[r], packed.data() + h.out_off[r], (size_t)out_len[r]);
@@ -275,16 +194,17 @@ sm_status smo_uncompress_streams(smo_ctx* ctx, uint32_t block_size, const uint8_
     if (room[r] && !out) return SM_ERR_ARGUMENT;
   }
   if (fragments > smo::kMaxStreams) fragments = 0;  // (a hint: such a batch decodes in stream order)
-  const StreamStaging h(in, in_off, in_len, nstreams, room);
+  const StreamStaging h(in, in_off, in_len, nstreams, room.data());
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
+  const StagingBufs b{ctx->io_in, ctx->io_out, ctx->sarg, ctx->stream};
   StreamCallArrays d;
-  SM_PASS(upload_stream_call(ctx, h, in_len, out_cap, nstreams, d));
+  SM_PASS(upload_stream_call(b, h, in_len, out_cap, nstreams, d));
   SM_PASS(smo_uncompress_streams_device(ctx, block_size, (const uint8_t*)ctx->io_in.p, d.in_off, d.in_len, nstreams,
                                         (uint32_t)chunks, (uint32_t)fragments, (uint8_t*)ctx->io_out.p, d.out_off,
                                         d.out_cap, d.out_len, d.status, nullptr, nullptr, ctx->stream));
   std::vector<uint8_t> decoded;
-  SM_PASS(download_stream_call(ctx, h, d, nstreams, out_len, status, decoded));
+  SM_PASS(download_stream_call(b, h, d, nstreams, out_len, status, decoded));
   for (uint32_t r = 0; r < nstreams; ++r)
     if (room[r]) memcpy(out + out_off[r], decoded.data() + h.out_off[r], (size_t)room[r]);
   return SM_OK;

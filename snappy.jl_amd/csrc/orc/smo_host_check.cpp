@@ -252,11 +252,11 @@ int main() {
              smo_streams_scratch_bytes(0, 0, 0, 1000) > 0 && smo_streams_scratch_bytes(1, 10, 0, 262144) >= 10 * 305920u,
          "streams scratch bytes");
   // the verdicts, the slot search and the copies' rows
-  expect(smo::stream_verdict(true, SM_OK, smo::kNoSlot, 0) == SM_ERR_ARGUMENT &&
-             smo::stream_verdict(true, SMO_ERR_TRUNCATED, 3, 19) == SM_ERR_ARGUMENT &&
-             smo::stream_verdict(false, SMO_ERR_TRUNCATED, 3, 19) == SMO_ERR_TRUNCATED &&
-             smo::stream_verdict(false, SM_OK, 3, 19) == 19 && smo::stream_verdict(false, SM_OK, 0, 19) == 19 &&
-             smo::stream_verdict(false, SM_OK, smo::kNoSlot, 19) == SM_OK,
+  expect(smc::plan_verdict(true, SM_OK, smo::kNoSlot, 0) == SM_ERR_ARGUMENT &&
+             smc::plan_verdict(true, SMO_ERR_TRUNCATED, 3, 19) == SM_ERR_ARGUMENT &&
+             smc::plan_verdict(false, SMO_ERR_TRUNCATED, 3, 19) == SMO_ERR_TRUNCATED &&
+             smc::plan_verdict(false, SM_OK, 3, 19) == 19 && smc::plan_verdict(false, SM_OK, 0, 19) == 19 &&
+             smc::plan_verdict(false, SM_OK, smo::kNoSlot, 19) == SM_OK,
          "stream verdict");
   expect(smo::slot_verdict(smo::kNoSlot, smo::kNoCopy, 19) == SM_OK && smo::slot_verdict(2, 0, 19) == SM_OK &&
              smo::slot_verdict(2, 70000, 18) == SM_OK && smo::slot_verdict(2, smo::kNoCopy, 19) == 19 &&
@@ -267,14 +267,14 @@ int main() {
     const uint32_t f[6] = {0, 0, 2, 2, 2, 5};  // streams 1 and 4 have slots
     std::memcpy(first, f, sizeof(f));
     const uint32_t want[5] = {1, 1, 4, 4, 4};
-    for (uint32_t j = 0; j < 5; ++j) expect(smo::slot_stream(first, 5, j) == want[j], "slot stream");
+    for (uint32_t j = 0; j < 5; ++j) expect(smc::slot_owner(first, 5, j) == want[j], "slot stream");
     first[1] = 1;
-    expect(smo::slot_stream(first, 1, 0) == 0, "slot stream: one stream");
+    expect(smc::slot_owner(first, 1, 0) == 0, "slot stream: one stream");
     std::free(first);
   }
-  expect(smo::copy_rows(1, 1) == 1 && smo::copy_rows(1, 16384) == 1 && smo::copy_rows(1, 16385) == 2 &&
-             smo::copy_rows(1, 0x7fffff) == 512 && smo::copy_rows(100, 0x7fffff) == 20 && smo::copy_rows(2500, 262144) == 1 &&
-             smo::copy_rows(0, 262144) == 16 && smo::copy_rows(0x7fffffff, 0x7fffff) == 1,
+  expect(smc::copy_rows(1, 1) == 1 && smc::copy_rows(1, 16384) == 1 && smc::copy_rows(1, 16385) == 2 &&
+             smc::copy_rows(1, 0x7fffff) == 512 && smc::copy_rows(100, 0x7fffff) == 20 && smc::copy_rows(2500, 262144) == 1 &&
+             smc::copy_rows(0, 262144) == 16 && smc::copy_rows(0x7fffffff, 0x7fffff) == 1,
          "copy rows");
 
   if (failures) {

@@ -16,80 +16,8 @@ namespace smo {
 
 namespace {
 
-constexpr uint32_t kWalkWaves = 4;  // streams a workgroup of the walkers takes: one per wave
-
-// The walker's fetch (walk_chunks), by one wave, as the blocks library's: a step's bytes
-// (kHeadBytes) come in by one load, a byte a lane, and every lane then takes the same step, so a
-// chunk costs one dependent load.  The bytes are read out of their lanes into scalar registers, so
-// the step's arithmetic and its branches are the wave's, not a lane's.  The little-endian header is
-// put together from these bytes: a stream sits at any alignment.
-struct WaveFetch {
-  const uint8_t* in;
-  uint32_t lane;
-  __device__ void operator()(uint64_t pos, uint32_t have, uint8_t* h) const {
-    const uint32_t mine = lane < have ? in[pos + lane] : 0u;
-#pragma unroll
-    for (uint32_t i = 0; i < kHeadBytes; ++i) h[i] = (uint8_t)__builtin_amdgcn_readlane((int)mine, (int)i);
-  }
-};
-
-// the stream of this wave of walkers, as the wave's own value (its loads of the stream's arguments
-// are then the wave's too)
-__device__ inline uint32_t walker_stream() {
-  return __builtin_amdgcn_readfirstlane(blockIdx.x * kWalkWaves + (threadIdx.x >> 6));
-}
-
-// The exclusive scan of value(i), i < n, by one workgroup (block_scan's contract: 256 threads, sh
-// its 4 u64 of LDS), tile by tile: each(i, value(i), the sum before i).  Returns the total to every thread.
-template <typename Value, typename Each>
-__device__ inline uint64_t tile_scan(uint32_t n, uint64_t* sh, Value value, Each each) {
-  uint64_t carry = 0;
-  for (uint32_t b0 = 0; b0 < n; b0 += 256) {  // (uniform: every thread takes every tile)
-    const uint32_t i = b0 + threadIdx.x;
-    const uint64_t v = i < n ? value(i) : 0u;
-    uint64_t total;
-    const uint64_t ex = smc::block_scan(v, sh, total);
-    if (i < n) each(i, v, carry + ex);
-    carry += total;
-  }
-  return carry;
-}
-
-// The exclusive scan of cnt(r) over the streams against the bound m, by one workgroup: first[0,
-// nstreams] (and first_out, if given) and the header.  Over the bound the scan is not used (it
-// saturates).
-template <typename Count>
-__device__ inline void scan_slots(uint32_t nstreams, uint32_t m, Count cnt, uint32_t* first, uint32_t* first_out,
-                                  Header* hdr, uint64_t* sh) {
-  const uint64_t sum = tile_scan(nstreams, sh, cnt, [&](uint32_t r, uint64_t, uint64_t at) {
-    first[r] = smc::sat32(at);
-    if (first_out) first_out[r] = smc::sat32(at);
-  });
-  if (threadIdx.x == 0) {
-    const bool over = sum > m;
-    first[nstreams] = smc::sat32(sum);
-    if (first_out) first_out[nstreams] = smc::sat32(sum);
-    hdr->over = over ? 1u : 0u;
-    hdr->total = over ? 0u : (uint32_t)sum;
-  }
-}
-
-// n bytes from src to dst by this workgroup's row of the grid (copy_rows): tile t goes to row
-// t mod gridDim.y.  A tile is a multiple of 16 bytes, so every tile of a slot meets the source at
-// the same alignment; copy_bytes reads nothing outside [src, src + n) and writes nothing outside
-// [dst, dst + n).
-__device__ inline void copy_tiled(const uint8_t* src, uint32_t n, uint8_t* dst) {
-  for (uint32_t o = blockIdx.y * kCopyTile; o < n; o += gridDim.y * kCopyTile) {
-    const uint32_t len = n - o < kCopyTile ? n - o : kCopyTile;
-    smc::copy_bytes(src + o, len, dst + o, threadIdx.x, blockDim.x);
-  }
-}
-
-// the copies' grid: a workgroup a used slot (striding, where the bound is far above what a device
-// holds at once) in x, the rows of a slot's tiles in y
-inline dim3 copy_grid(uint32_t m, uint32_t block_size) {
-  return dim3(m < 8 * kCopyGroups ? m : 8 * kCopyGroups, copy_rows(m, block_size));
-}
+// the walkers' fetch (walk_chunks): a step's kHeadBytes, the little-endian header put together from them
+using WaveFetch = smc::HeadFetch<kHeadBytes>;
 
 }  // namespace
 
@@ -97,7 +25,7 @@ inline dim3 copy_grid(uint32_t m, uint32_t block_size) {
 // The counting walk, one wave per stream: what the stream gets (stream_plan) before any byte of it
 // is decoded.  The walks of a workgroup's waves are independent: no barrier in here.
 __global__ __launch_bounds__(256) void k_orc_count(DecodeStreamsArgs a) {
-  const uint32_t r = walker_stream();
+  const uint32_t r = smc::walker_index();
   if (r >= a.nstreams) return;
   const WaveFetch fetch{a.in + a.in_off[r], threadIdx.x & 63};
   const Walk w = walk_chunks(a.block_size, a.in_len[r], fetch, [](uint32_t, uint64_t, const Chunk&) {});
@@ -112,7 +40,7 @@ __global__ __launch_bounds__(256) void k_orc_count(DecodeStreamsArgs a) {
 
 __global__ __launch_bounds__(256) void k_orc_scan(DecodeStreamsArgs a) {
   __shared__ uint64_t sh[4];
-  scan_slots(a.nstreams, a.m, [&](uint32_t r) { return a.s.count[r]; }, a.s.first, a.chunk_first, a.s.hdr, sh);
+  smc::count_scan(a.nstreams, a.m, [&](uint32_t r) { return a.s.count[r]; }, a.s.first, a.chunk_first, a.s.hdr, sh);
 }
 
 // The slots no chunk took (all of them over the bound) become empty streams with no room, which
@@ -131,7 +59,7 @@ __global__ __launch_bounds__(256) void k_orc_fill(DecodeStreamsArgs a) {
     a.s.copy_len[j] = kNoCopy;
     a.s.stream[j] = kNoSlot;
   }
-  const uint32_t r = walker_stream();
+  const uint32_t r = smc::walker_index();
   if (r >= a.nstreams || a.s.hdr->over) return;
   const uint32_t cnt = a.s.count[r], base = a.s.first[r];
   if (cnt == 0) return;
@@ -151,7 +79,7 @@ __global__ __launch_bounds__(256) void k_orc_fill(DecodeStreamsArgs a) {
 }
 
 hipError_t launch_decode_plan(const DecodeStreamsArgs& a, hipStream_t s) {
-  const uint32_t walkers = (a.nstreams + kWalkWaves - 1) / kWalkWaves;
+  const uint32_t walkers = (a.nstreams + smc::kWalkWaves - 1) / smc::kWalkWaves;
   hipLaunchKernelGGL(k_orc_count, dim3(walkers), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_orc_scan, dim3(1), dim3(256), 0, s, a);
   if (a.m) hipLaunchKernelGGL(k_orc_fill, dim3(walkers), dim3(256), 0, s, a);
@@ -167,7 +95,7 @@ __global__ __launch_bounds__(256) void k_orc_copy(DecodeStreamsArgs a) {
   for (uint32_t j = blockIdx.x; j < total; j += gridDim.x) {
     const uint32_t n = a.s.copy_len[j];
     if (a.s.stream[j] == kNoSlot || n == kNoCopy) continue;
-    copy_tiled(a.in + a.s.in_off[j], n, a.out + a.s.out_off[j]);
+    smc::copy_tiled(a.in + a.s.in_off[j], n, a.out + a.s.out_off[j]);
   }
 }
 
@@ -187,13 +115,13 @@ __global__ __launch_bounds__(256) void k_orc_result(DecodeStreamsArgs a) {
   if (r >= a.nstreams) return;
   const bool over = a.s.hdr->over != 0;
   const uint32_t fail = over ? kNoSlot : a.s.fail[r];
-  a.status[r] = stream_verdict(over, a.s.pre[r], fail, fail != kNoSlot ? a.s.dec_status[fail] : (int32_t)SM_OK);
+  a.status[r] = smc::plan_verdict(over, a.s.pre[r], fail, fail != kNoSlot ? a.s.dec_status[fail] : (int32_t)SM_OK);
   a.out_len[r] = over ? 0 : a.s.length[r];
 }
 
 hipError_t launch_decode_result(const DecodeStreamsArgs& a, hipStream_t s) {
   if (a.m) {
-    hipLaunchKernelGGL(k_orc_copy, copy_grid(a.m, a.block_size), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_orc_copy, smc::copy_grid(a.m, a.block_size), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_orc_verdict, dim3((a.m + 255) / 256), dim3(256), 0, s, a);
   }
   hipLaunchKernelGGL(k_orc_result, dim3((a.nstreams + 255) / 256), dim3(256), 0, s, a);
@@ -203,7 +131,7 @@ hipError_t launch_decode_result(const DecodeStreamsArgs& a, hipStream_t s) {
 // ---- compress: the plan --------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_corc_scan(CompressStreamsArgs a) {
   __shared__ uint64_t sh[4];
-  scan_slots(a.nstreams, a.m, [&](uint32_t r) { return stream_pieces(a.in_len[r], a.block_size); }, a.s.first, nullptr,
+  smc::count_scan(a.nstreams, a.m, [&](uint32_t r) { return stream_pieces(a.in_len[r], a.block_size); }, a.s.first, nullptr,
              a.s.hdr, sh);
   for (uint32_t r = threadIdx.x; r < a.nstreams; r += 256) a.s.bad[r] = 0;
 }
@@ -216,7 +144,7 @@ __global__ __launch_bounds__(256) void k_corc_pieces(CompressStreamsArgs a) {
   uint64_t in_off = 0;
   uint32_t in_len = 0, stream = kNoSlot;
   if (j < a.s.hdr->total) {
-    const uint32_t r = slot_stream(a.s.first, a.nstreams, j);
+    const uint32_t r = smc::slot_owner(a.s.first, a.nstreams, j);
     const uint64_t o = (uint64_t)(j - a.s.first[r]) * a.block_size, n = a.in_len[r];
     if (o < n) {  // (always, for the scan of these lengths)
       stream = r;
@@ -247,7 +175,7 @@ __device__ inline bool piece_ok(const CompressStreamsArgs& a, uint32_t j) {
 __global__ __launch_bounds__(256) void k_corc_sizes(CompressStreamsArgs a) {
   __shared__ uint64_t sh[4];
   const uint32_t used = a.s.hdr->total;
-  const uint64_t sum = tile_scan(
+  const uint64_t sum = smc::tile_scan(
       used, sh,
       [&](uint32_t j) -> uint64_t {
         if (a.s.stream[j] == kNoSlot) return 0;
@@ -274,7 +202,7 @@ __global__ __launch_bounds__(256) void k_corc_pack(CompressStreamsArgs a) {
     const uint32_t L = stored ? a.s.in_len[j] : a.s.comp_len[j];
     uint8_t* const d = a.out + a.out_off[r] + (a.s.size_scan[j] - a.s.size_scan[a.s.first[r]]);
     if (blockIdx.y == 0 && threadIdx.x < SMO_HEADER_LENGTH) d[threadIdx.x] = chunk_header_byte(threadIdx.x, L, stored);
-    copy_tiled(stored ? a.in + a.s.in_off[j] : a.slots + a.s.slot_off[j], L, d + SMO_HEADER_LENGTH);
+    smc::copy_tiled(stored ? a.in + a.s.in_off[j] : a.slots + a.s.slot_off[j], L, d + SMO_HEADER_LENGTH);
   }
 }
 
@@ -293,7 +221,7 @@ __global__ __launch_bounds__(256) void k_corc_result(CompressStreamsArgs a) {
 
 hipError_t launch_compress_pack(const CompressStreamsArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_corc_sizes, dim3(1), dim3(256), 0, s, a);
-  if (a.m) hipLaunchKernelGGL(k_corc_pack, copy_grid(a.m, a.block_size), dim3(256), 0, s, a);
+  if (a.m) hipLaunchKernelGGL(k_corc_pack, smc::copy_grid(a.m, a.block_size), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_corc_result, dim3((a.nstreams + 255) / 256), dim3(256), 0, s, a);
   return hipGetLastError();
 }

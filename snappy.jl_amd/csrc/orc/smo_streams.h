@@ -1,25 +1,23 @@
 // smo_streams.h -- the rules of the batched calls (smo_uncompress_streams_device,
 // smo_compress_streams_device), shared by their kernels (smo_kernels.hip) and the host
 // (smo_streams_plan in smo_host.cpp, which the sanitizer driver runs): what a walked stream of a
-// batch gets, a slot's and a stream's verdict, the tiling of the copies and the scratch layouts.
+// batch gets, a slot's verdict and the scratch layouts (the shared slot rules are ../common/smc_slots.h's).
 // The walk itself is walk_chunks (smo_format.h).  Plain functions, compiled for the host and the
 // device alike, so the host checker tests the code the kernels run.  Not part of the public ABI.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../common/smc_slots.h"
 #include "smo_format.h"
 
 namespace smo {
 
 constexpr uint32_t kMaxStreams = 0x7fffffffu;  // more streams, chunks or pieces: SM_ERR_ARGUMENT
-constexpr uint32_t kNoSlot = 0xffffffffu;      // a slot of no stream; a stream without a failing slot
+using smc::kNoSlot;                            // a slot of no stream; a stream without a failing slot
 constexpr uint32_t kNoCopy = 0xffffffffu;      // a slot's copy length when its chunk is not a stored one
 
-struct Header {    // a plan's words for the kernels behind it
-  uint32_t total;  // slots in use (0 over the bound: nothing is decoded or packed)
-  uint32_t over;   // the streams need more slots than the caller's bound
-};
+using Header = smc::PlanHeader;
 
 struct StreamPlan {
   int32_t status;  // the walk's error, SM_BUFFER_TOO_SMALL, or SM_OK: what is known before any decode
@@ -41,40 +39,9 @@ SMC_HD inline int32_t slot_verdict(uint32_t stream, uint32_t copy_len, int32_t d
   return stream == kNoSlot || copy_len != kNoCopy ? (int32_t)SM_OK : dec_status;
 }
 
-// A stream's status: SM_ERR_ARGUMENT over the caller's bound, else the plan's, else its first
-// failing slot's raw decoder status (fail == kNoSlot: none failed).
-SMC_HD inline int32_t stream_verdict(bool over, int32_t pre, uint32_t fail, int32_t fail_status) {
-  if (over) return SM_ERR_ARGUMENT;
-  if (pre != SM_OK) return pre;
-  return fail != kNoSlot ? fail_status : (int32_t)SM_OK;
-}
-
-// The stream of slot j: first[r] <= j < first[r + 1] in the scan first[0, nstreams] (of equal
-// entries the last one, so streams without slots are passed over).  j < first[nstreams].
-SMC_HD inline uint32_t slot_stream(const uint32_t* first, uint32_t nstreams, uint32_t j) {
-  uint32_t lo = 0, hi = nstreams;  // first[lo] <= j < first[hi]
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (first[mid] <= j) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// ---- the copies' grid -----------------------------------------------------------------------------
-// A slot's bytes (a stored chunk on decode, a chunk's payload on compress) are copied in tiles of
-// kCopyTile bytes, tile t by the workgroups of row t mod rows.  With many slots one row does (a
-// workgroup a slot); with few, a long slot is spread over as many rows as fill the device
-// (kCopyGroups workgroups), at most one per tile of the longest slot there can be.
-constexpr uint32_t kCopyTile = 16384;
-constexpr uint32_t kCopyGroups = 2048;  // 256 CUs x 8 workgroups
-
-SMC_HD inline uint32_t copy_rows(uint32_t slots, uint32_t longest) {
-  const uint32_t tiles = longest / kCopyTile + (longest % kCopyTile ? 1 : 0);
-  const uint32_t want = slots ? kCopyGroups / slots : kCopyGroups;
-  const uint32_t rows = tiles < want ? tiles : want;
-  return rows ? rows : 1;
-}
+// (A stream's status is smc::plan_verdict over its first failing slot's raw decoder status; the
+// stream of a slot is its smc::slot_owner in the scan first[0, nstreams]; the copies of the stored
+// chunks and of the packed payloads are tiled by smc::copy_rows for slots of block_size bytes.)
 
 // ---- scratch (smc::Carve: a null base measures) ------------------------------------------------
 struct DecodeStreams {

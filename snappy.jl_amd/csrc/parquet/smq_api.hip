@@ -15,6 +15,7 @@
 #include "../../../include/snappy_mi355x_multi.h"
 #include "../common/smc_hip_host.h"
 #include "../common/smc_layout.h"
+#include "../common/smc_staging.h"
 #include "smq_chunks.h"
 #include "smq_crc.h"
 #include "smq_encode.h"
@@ -24,29 +25,6 @@
 #ifndef SMQ_VERSION_STR
 #define SMQ_VERSION_STR "dev"
 #endif
-
-namespace {
-
-struct ChunkCallArrays {  // per chunk, what a host-buffer call hands the device call (ctx->sarg)
-  uint64_t *in_off, *in_len, *out_off, *out_cap, *out_len;
-  int32_t* status;
-  uintptr_t end;
-};
-constexpr ChunkCallArrays carve_chunk_call(uintptr_t base, size_t n) {
-  smc::Carve c{base};
-  ChunkCallArrays m{};
-  m.in_off = c.take<uint64_t>(n);
-  m.in_len = c.take<uint64_t>(n);
-  m.out_off = c.take<uint64_t>(n);
-  m.out_cap = c.take<uint64_t>(n);
-  m.out_len = c.take<uint64_t>(n);
-  m.status = c.take<int32_t>(n);
-  m.end = c.p;
-  return m;
-}
-constexpr size_t chunk_call_bytes(size_t n) { return carve_chunk_call(0, n).end; }
-
-}  // namespace
 
 struct smq_ctx {
   smm_ctx* smm = nullptr;
@@ -197,7 +175,7 @@ sm_status smqe_compress_chunks_device(smq_ctx* ctx, const uint8_t* d_in, const u
 // ---- host buffers --------------------------------------------------------------------------------
 // The chunks' bytes packed behind one another in one staging block (one upload), and room for every
 // chunk's output at a 16-byte boundary of the device buffer (one download; each chunk's own bytes
-// then go to the caller's place), as the ORC library's host-buffer calls.
+// then go to the caller's place): ../common/smc_staging.h.
 sm_status smq_uncompress_chunks(smq_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint64_t* in_len,
                                 uint32_t nchunks, int verify_crc, uint8_t* out, const uint64_t* out_off,
                                 const uint64_t* out_cap, uint64_t* out_len, int32_t* status) {
@@ -210,44 +188,24 @@ sm_status smq_uncompress_chunks(smq_ctx* ctx, const uint8_t* in, const uint64_t*
   const sm_status planned =
       smq_chunks_plan(in, in_off, in_len, nchunks, out_cap, smq::kMaxChunks, nullptr, room.data(), status, &pages, &fragments);
   if (planned != SM_OK) return planned == SM_BUFFER_TOO_SMALL ? (sm_status)SM_ERR_INPUT_TOO_LARGE : planned;
-  std::vector<uint64_t> h_in_off(nchunks), h_out_off(nchunks);
-  uint64_t in_total = 0, out_total = 0;
   for (uint32_t r = 0; r < nchunks; ++r) {
     if (status[r] != SM_OK) room[r] = 0;  // (not decoded)
     if (room[r] && !out) return SM_ERR_ARGUMENT;
-    h_in_off[r] = in_total;
-    in_total += in_len[r];
-    h_out_off[r] = out_total;
-    out_total += (room[r] + 15) / 16 * 16;
   }
   if (fragments > smq::kMaxChunks) fragments = 0;  // (a hint: such a batch decodes in stream order)
-  std::vector<uint8_t> bytes((size_t)in_total);
-  for (uint32_t r = 0; r < nchunks; ++r)
-    if (in_len[r]) memcpy(bytes.data() + h_in_off[r], in + in_off[r], (size_t)in_len[r]);
+  const StreamStaging h(in, in_off, in_len, nchunks, room.data());
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
-  hipStream_t s = ctx->stream;
-  // (a byte of each at the least: the device call wants both pointers)
-  SM_CHECK(ctx->io_in.ensure(std::max<size_t>(bytes.size(), 1)));
-  SM_CHECK(ctx->io_out.ensure(std::max<size_t>((size_t)out_total, 1)));
-  SM_CHECK(ctx->sarg.ensure(chunk_call_bytes(nchunks)));
-  const ChunkCallArrays d = carve_chunk_call((uintptr_t)ctx->sarg.p, nchunks);
-  const size_t n8 = 8 * (size_t)nchunks;
-  if (!bytes.empty()) SM_CHECK(hipMemcpyAsync(ctx->io_in.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d.in_off, h_in_off.data(), n8, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d.in_len, in_len, n8, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d.out_off, h_out_off.data(), n8, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d.out_cap, out_cap, n8, hipMemcpyHostToDevice, s));
+  const StagingBufs b{ctx->io_in, ctx->io_out, ctx->sarg, ctx->stream};
+  StreamCallArrays d;
+  SM_PASS(upload_stream_call(b, h, in_len, out_cap, nchunks, d));
   SM_PASS(smq_uncompress_chunks_device(ctx, (const uint8_t*)ctx->io_in.p, d.in_off, d.in_len, nchunks, (uint32_t)pages,
                                        (uint32_t)fragments, verify_crc, (uint8_t*)ctx->io_out.p, d.out_off, d.out_cap, d.out_len,
-                                       d.status, nullptr, nullptr, nullptr, s));
-  std::vector<uint8_t> decoded((size_t)out_total);
-  SM_CHECK(hipMemcpyAsync(out_len, d.out_len, n8, hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipMemcpyAsync(status, d.status, 4 * (size_t)nchunks, hipMemcpyDeviceToHost, s));
-  if (!decoded.empty()) SM_CHECK(hipMemcpyAsync(decoded.data(), ctx->io_out.p, decoded.size(), hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipStreamSynchronize(s));
+                                       d.status, nullptr, nullptr, nullptr, ctx->stream));
+  std::vector<uint8_t> decoded;
+  SM_PASS(download_stream_call(b, h, d, nchunks, out_len, status, decoded));
   for (uint32_t r = 0; r < nchunks; ++r)
-    if (room[r]) memcpy(out + out_off[r], decoded.data() + h_out_off[r], (size_t)room[r]);
+    if (room[r]) memcpy(out + out_off[r], decoded.data() + h.out_off[r], (size_t)room[r]);
   return SM_OK;
 }
 
@@ -265,42 +223,23 @@ sm_status smqe_compress_chunks(smq_ctx* ctx, const uint8_t* in, const uint64_t* 
       smqe_chunks_plan(in, in_off, in_len, nchunks, smq::kMaxChunks, nullptr, status, room.data(), &pages, &stage, &fragments);
   if (planned != SM_OK) return planned == SM_BUFFER_TOO_SMALL ? (sm_status)SM_ERR_INPUT_TOO_LARGE : planned;
   if (fragments > smq::kMaxChunks) return SM_ERR_INPUT_TOO_LARGE;
-  std::vector<uint64_t> h_in_off(nchunks), h_out_off(nchunks);
-  uint64_t in_total = 0, out_total = 0;
   for (uint32_t r = 0; r < nchunks; ++r) {
     room[r] = std::min(room[r], out_cap[r]);
     if (room[r] && !out) return SM_ERR_ARGUMENT;
-    h_in_off[r] = in_total;
-    in_total += in_len[r];
-    h_out_off[r] = out_total;
-    out_total += (room[r] + 15) / 16 * 16;
   }
-  std::vector<uint8_t> bytes((size_t)in_total);
-  for (uint32_t r = 0; r < nchunks; ++r)
-    if (in_len[r]) memcpy(bytes.data() + h_in_off[r], in + in_off[r], (size_t)in_len[r]);
+  const StreamStaging h(in, in_off, in_len, nchunks, room.data());
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
-  hipStream_t s = ctx->stream;
-  SM_CHECK(ctx->io_in.ensure(std::max<size_t>(bytes.size(), 1)));
-  SM_CHECK(ctx->io_out.ensure(std::max<size_t>((size_t)out_total, 1)));
-  SM_CHECK(ctx->sarg.ensure(chunk_call_bytes(nchunks)));
-  const ChunkCallArrays d = carve_chunk_call((uintptr_t)ctx->sarg.p, nchunks);
-  const size_t n8 = 8 * (size_t)nchunks;
-  if (!bytes.empty()) SM_CHECK(hipMemcpyAsync(ctx->io_in.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d.in_off, h_in_off.data(), n8, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d.in_len, in_len, n8, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d.out_off, h_out_off.data(), n8, hipMemcpyHostToDevice, s));
-  SM_CHECK(hipMemcpyAsync(d.out_cap, out_cap, n8, hipMemcpyHostToDevice, s));
+  const StagingBufs b{ctx->io_in, ctx->io_out, ctx->sarg, ctx->stream};
+  StreamCallArrays d;
+  SM_PASS(upload_stream_call(b, h, in_len, out_cap, nchunks, d));
   SM_PASS(smqe_compress_chunks_device(ctx, (const uint8_t*)ctx->io_in.p, d.in_off, d.in_len, nchunks, (uint32_t)pages, stage,
                                       (uint32_t)fragments, (uint8_t*)ctx->io_out.p, d.out_off, d.out_cap, d.out_len, d.status,
-                                      nullptr, nullptr, nullptr, mode, s));
-  std::vector<uint8_t> packed((size_t)out_total);
-  SM_CHECK(hipMemcpyAsync(out_len, d.out_len, n8, hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipMemcpyAsync(status, d.status, 4 * (size_t)nchunks, hipMemcpyDeviceToHost, s));
-  if (!packed.empty()) SM_CHECK(hipMemcpyAsync(packed.data(), ctx->io_out.p, packed.size(), hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipStreamSynchronize(s));
+                                      nullptr, nullptr, nullptr, mode, ctx->stream));
+  std::vector<uint8_t> packed;
+  SM_PASS(download_stream_call(b, h, d, nchunks, out_len, status, packed));
   for (uint32_t r = 0; r < nchunks; ++r)
-    if (status[r] == SM_OK && out_len[r]) memcpy(out + out_off[r], packed.data() + h_out_off[r], (size_t)out_len[r]);
+    if (status[r] == SM_OK && out_len[r]) memcpy(out + out_off[r], packed.data() + h.out_off[r], (size_t)out_len[r]);
   return SM_OK;
 }
 

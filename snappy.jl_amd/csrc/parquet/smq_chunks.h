@@ -1,6 +1,6 @@
 // smq_chunks.h -- the rules of the batched call (smq_uncompress_chunks_device), shared by its kernels
 // (smq_kernels.hip) and the host (smq_chunks_plan in smq_host.cpp, which the sanitizer driver runs):
-// what a walked chunk of a batch gets, a slot's and a chunk's verdict, the tiling of the copies and
+// what a walked chunk of a batch gets, a slot's verdict (a chunk's is smc::plan_verdict) and
 // the scratch layout -- and the encoder's slots and their carve (smqe_compress_chunks_device; its
 // rules are smq_encode.h's).  The walk itself is walk_pages (smq_format.h).  Plain functions, compiled for
 // the host and the device alike, so the host checker tests the code the kernels run.  Not part of
@@ -12,14 +12,15 @@
 #include <initializer_list>
 
 #include "../../../include/snappy_mi355x_parquet_write.h"
+#include "../common/smc_slots.h"
 #include "smq_format.h"
 
 namespace smq {
 
 constexpr uint32_t kMaxChunks = 0x7fffffffu;  // more chunks or pages: SM_ERR_ARGUMENT
-constexpr uint32_t kNoSlot = 0xffffffffu;     // a slot of no chunk; a chunk without a failing slot
+using smc::kNoSlot;                           // a slot of no chunk; a chunk without a failing slot
 
-struct Header {    // a plan's words for the kernels behind it
+struct Header {    // a plan's words for the kernels behind it: smc::PlanHeader's two and the CRC pass's
   uint32_t total;  // slots in use (0 over the bound: nothing is decoded)
   uint32_t over;   // the chunks need more slots than the caller's bound
   uint32_t segments;  // CRC segments of all slots (0 without verification)
@@ -49,42 +50,10 @@ SMC_HD inline int32_t slot_verdict(uint32_t chunk, bool checked, uint32_t crc_go
   return compressed ? dec_status : (int32_t)SM_OK;
 }
 
-// A chunk's status: SM_ERR_ARGUMENT over the caller's bound, else the plan's, else its first
-// failing slot's status (fail == kNoSlot: none failed).
-SMC_HD inline int32_t chunk_verdict(bool over, int32_t pre, uint32_t fail, int32_t fail_status) {
-  if (over) return SM_ERR_ARGUMENT;
-  if (pre != SM_OK) return pre;
-  return fail != kNoSlot ? fail_status : (int32_t)SM_OK;
-}
-
-// The owner of item j in the exclusive scan first[0, n]: first[r] <= j < first[r + 1] (of equal
-// entries the last one, so owners without items are passed over).  j < first[n].
-SMC_HD inline uint32_t scan_owner(const uint32_t* first, uint32_t n, uint32_t j) {
-  uint32_t lo = 0, hi = n;  // first[lo] <= j < first[hi]
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (first[mid] <= j) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// ---- the copies' grid -----------------------------------------------------------------------------
-// A slot's stored bytes (level bytes, a section that is not compressed) are copied in tiles of
-// kCopyTile bytes, tile t by the workgroups of row t mod rows, as the ORC library's stored chunks:
-// with many slots one row does, with few a long slot is spread over the rows.  A page has no bound
-// short of 2 GiB, so the rows are sized for pages of kCopyTypical bytes (the writers' default page
-// size); a longer one is strided.
-constexpr uint32_t kCopyTile = 16384;
-constexpr uint32_t kCopyGroups = 2048;  // 256 CUs x 8 workgroups
+// A slot's stored bytes (level bytes, a section that is not compressed) are copied in tiles
+// (smc::copy_tiled).  A page has no bound short of 2 GiB, so the rows (smc::copy_rows) are sized for
+// pages of kCopyTypical bytes (the writers' default page size); a longer one is strided.
 constexpr uint32_t kCopyTypical = 1u << 20;
-
-SMC_HD inline uint32_t copy_rows(uint32_t slots) {
-  const uint32_t tiles = kCopyTypical / kCopyTile;
-  const uint32_t want = slots ? kCopyGroups / slots : kCopyGroups;
-  const uint32_t rows = tiles < want ? tiles : want;
-  return rows ? rows : 1;
-}
 
 // ---- scratch (smc::Carve: a null base measures) ------------------------------------------------
 struct DecodeChunks {

@@ -27,7 +27,7 @@ __device__ inline uint32_t job_len(const CrcJobs& j, uint32_t i) {
 }  // namespace
 
 // Segment g of the call (grid-strided, so the tables are staged in LDS once per workgroup) belongs
-// to job i = scan_owner(seg_first, g) and is its segment g - seg_first[i].  Within the segment, as
+// to job i = smc::slot_owner(seg_first, g) and is its segment g - seg_first[i].  Within the segment, as
 // in the framing library's CRC-32C: lane t takes the 16-byte granules at distance t, t + 256, ...
 // from the last one as coalesced 16-byte loads -- a lane's register, 256 granules old, is advanced
 // by four lookups and the new granule enters by sixteen, all independent -- and moves its register
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(kCrcThreads) void k_crc32_segments(CrcJobs j, const
   for (uint32_t i = t; i < kCrcTabs * 256; i += kCrcThreads) tab[i] = (&T->tab[0][0])[i];
   __syncthreads();
   for (uint32_t g = blockIdx.x; g < nseg_all; g += gridDim.x) {
-    const uint32_t i = scan_owner(j.seg_first, njobs, g), k = g - j.seg_first[i];
+    const uint32_t i = smc::slot_owner(j.seg_first, njobs, g), k = g - j.seg_first[i];
     const uint32_t n = job_len(j, i), nseg = crc_segments(n);
     const uint32_t len = crc_segment_len(n, k);
     const uint8_t* p = j.in + j.off[i] + crc_segment_start(n, k);

@@ -11,7 +11,6 @@
 
 #include "../common/smc_device.h"
 #include "smq_chunks.h"
-#include "smq_device.h"
 #include "smq_encode.h"
 #include "smq_format.h"
 #include "smq_internal.h"
@@ -58,11 +57,11 @@ __device__ inline Rewrite slot_rewrite(const EncodeChunksArgs& a, uint32_t j) {
 // ---- the plan ------------------------------------------------------------------------------------
 // The counting walk, one wave per chunk: a chunk without a walk error takes a slot per page.
 __global__ __launch_bounds__(256) void k_pqe_count(EncodeChunksArgs a) {
-  __shared__ Frame frames[kWalkWaves][SMQ_MAX_DEPTH];
-  const uint32_t r = walker_chunk();
+  __shared__ Frame frames[smc::kWalkWaves][SMQ_MAX_DEPTH];
+  const uint32_t r = smc::walker_index();
   if (r >= a.nchunks) return;
   const uint64_t n = a.in_len[r];
-  WaveFetch fetch{a.in + a.in_off[r], n, threadIdx.x & 63};
+  smc::WindowFetch fetch{a.in + a.in_off[r], n, threadIdx.x & 63};
   const Walk w = walk_pages<EncodeWalk>(n, fetch, frames[threadIdx.x >> 6], [](uint32_t, uint64_t, const Page&) {});
   if (fetch.lane == 0) {
     a.s.count[r] = w.status == SM_OK ? w.npages : 0u;
@@ -75,18 +74,8 @@ __global__ __launch_bounds__(256) void k_pqe_count(EncodeChunksArgs a) {
 // the exclusive scan of the chunks' slots against the bound m, by one workgroup
 __global__ __launch_bounds__(256) void k_pqe_scan(EncodeChunksArgs a) {
   __shared__ uint64_t sh[4];
-  const uint64_t sum = tile_scan(a.nchunks, sh, [&](uint32_t r) { return a.s.count[r]; }, [&](uint32_t r, uint64_t, uint64_t at) {
-    a.s.first[r] = smc::sat32(at);
-    if (a.page_first) a.page_first[r] = smc::sat32(at);
-  });
-  if (threadIdx.x == 0) {
-    const bool over = sum > a.m;
-    a.s.first[a.nchunks] = smc::sat32(sum);
-    if (a.page_first) a.page_first[a.nchunks] = smc::sat32(sum);
-    a.s.hdr->over = over ? 1u : 0u;
-    a.s.hdr->total = over ? 0u : (uint32_t)sum;
-    a.s.hdr->segments = 0;
-  }
+  smc::count_scan(a.nchunks, a.m, [&](uint32_t r) { return a.s.count[r]; }, a.s.first, a.page_first, a.s.hdr, sh);
+  if (threadIdx.x == 0) a.s.hdr->segments = 0;
 }
 
 // The slots no page took (all of them over the bound) become empty.  Then the storing walk: page k
@@ -94,17 +83,17 @@ __global__ __launch_bounds__(256) void k_pqe_scan(EncodeChunksArgs a) {
 // compressor's input (offsets relative to d_in) and the size of its stage slot.  The walk is the
 // counting walk's over the same bytes; a slot past the chunk's count is never stored.
 __global__ __launch_bounds__(256) void k_pqe_fill(EncodeChunksArgs a) {
-  __shared__ Frame frames[kWalkWaves][SMQ_MAX_DEPTH];
+  __shared__ Frame frames[smc::kWalkWaves][SMQ_MAX_DEPTH];
   for (uint64_t j = (uint64_t)a.s.hdr->total + (uint64_t)blockIdx.x * 256u + threadIdx.x; j < a.m; j += (uint64_t)gridDim.x * 256u) {
     clear_slot(a, j);
     if (a.table) store_page(a.pages, j, 0, Page{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, false});
   }
-  const uint32_t r = walker_chunk();
+  const uint32_t r = smc::walker_index();
   if (r >= a.nchunks || a.s.hdr->over) return;
   const uint32_t cnt = a.s.count[r], base = a.s.first[r];
   if (cnt == 0) return;
   const uint64_t in_off = a.in_off[r], n = a.in_len[r];
-  WaveFetch fetch{a.in + in_off, n, threadIdx.x & 63};
+  smc::WindowFetch fetch{a.in + in_off, n, threadIdx.x & 63};
   const uint32_t lane = fetch.lane;
   walk_pages<EncodeWalk>(n, fetch, frames[threadIdx.x >> 6], [&](uint32_t k, uint64_t at, const Page& p) {
     if (lane != 0 || k >= cnt) return;
@@ -140,7 +129,7 @@ __global__ __launch_bounds__(256) void k_pqe_stage(EncodeChunksArgs a) {
   __shared__ uint64_t sh[4];
   const uint32_t used = a.s.hdr->total;
   uint64_t mine = 0;  // the fragments of this thread's slots: a sum, not a scan
-  const uint64_t stage = tile_scan(
+  const uint64_t stage = smc::tile_scan(
       used, sh,
       [&](uint32_t j) {
         const uint32_t n = a.s.in_len[j];
@@ -166,7 +155,7 @@ __global__ __launch_bounds__(256) void k_pqe_stage(EncodeChunksArgs a) {
 }
 
 hipError_t launch_encode_plan(const EncodeChunksArgs& a, hipStream_t s) {
-  const uint32_t walkers = (a.nchunks + kWalkWaves - 1) / kWalkWaves;
+  const uint32_t walkers = (a.nchunks + smc::kWalkWaves - 1) / smc::kWalkWaves;
   hipLaunchKernelGGL(k_pqe_count, dim3(walkers), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_pqe_scan, dim3(1), dim3(256), 0, s, a);
   if (a.m) hipLaunchKernelGGL(k_pqe_fill, dim3(walkers), dim3(256), 0, s, a);
@@ -182,7 +171,7 @@ __global__ __launch_bounds__(256) void k_pqe_levels(EncodeChunksArgs a) {
   for (uint32_t j = blockIdx.x; j < total; j += gridDim.x) {
     const uint32_t n = a.s.levels[j];
     if (n == 0) continue;
-    copy_tiled(a.in + a.s.hdr_in[j] + a.s.hdr_len[j], n, a.s.stage + a.s.body_off[j]);
+    smc::copy_tiled(a.in + a.s.hdr_in[j] + a.s.hdr_len[j], n, a.s.stage + a.s.body_off[j]);
   }
 }
 
@@ -192,7 +181,7 @@ __global__ __launch_bounds__(256) void k_pqe_levels(EncodeChunksArgs a) {
 __global__ __launch_bounds__(256) void k_pqe_bodies(EncodeChunksArgs a) {
   __shared__ uint64_t sh[4];
   const uint32_t used = a.s.hdr->total;
-  const uint64_t sum = tile_scan(
+  const uint64_t sum = smc::tile_scan(
       used, sh,
       [&](uint32_t j) -> uint64_t {
         const uint32_t flags = a.s.flags[j];
@@ -221,7 +210,7 @@ __global__ __launch_bounds__(256) void k_pqe_size(EncodeChunksArgs a) {
   const bool over = a.s.hdr->over != 0;
   for (uint32_t r = blockIdx.x; r < a.nchunks; r += gridDim.x) {  // (uniform: the workgroup's chunk)
     const uint32_t base = a.s.first[r], cnt = over ? 0u : a.s.count[r];
-    const uint64_t need = tile_scan(
+    const uint64_t need = smc::tile_scan(
         cnt, sh,
         [&](uint32_t k) -> uint64_t {
           const uint32_t j = base + k;
@@ -274,24 +263,24 @@ __global__ __launch_bounds__(256) void k_pqe_pack(EncodeChunksArgs a) {
       if (blockIdx.y == 0)
         for (uint32_t i = threadIdx.x; i < w.new_len; i += blockDim.x)
           dst[i] = rewritten_byte(w, [&](uint32_t k) { return hdr[k]; }, i);
-      copy_tiled(a.s.stage + a.s.body_off[j], a.s.new_body[j], dst + w.new_len);
+      smc::copy_tiled(a.s.stage + a.s.body_off[j], a.s.new_body[j], dst + w.new_len);
     } else {
-      copy_tiled(hdr, hdr_len, dst);
-      copy_tiled(hdr + hdr_len, a.s.old_body[j], dst + hdr_len);
+      smc::copy_tiled(hdr, hdr_len, dst);
+      smc::copy_tiled(hdr + hdr_len, a.s.old_body[j], dst + hdr_len);
     }
   }
 }
 
 hipError_t launch_encode_result(const EncodeChunksArgs& a, const CrcLut* T, hipStream_t s) {
-  const uint32_t groups = a.m < 8 * kCopyGroups ? a.m : 8 * kCopyGroups;
+  const dim3 copies = smc::copy_grid(a.m, kCopyTypical);
   if (a.m) {
-    hipLaunchKernelGGL(k_pqe_levels, dim3(groups, copy_rows(a.m)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_pqe_levels, copies, dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_pqe_bodies, dim3(1), dim3(256), 0, s, a);
     const hipError_t e = launch_crc_segments(CrcJobs{a.s.stage, a.s.body_off, a.s.new_body, nullptr, a.s.seg_first, a.m, a.s.hdr, a.s.crc_acc}, T, s);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(k_pqe_size, dim3(a.nchunks < kCopyGroups ? a.nchunks : kCopyGroups), dim3(256), 0, s, a);
-  if (a.m) hipLaunchKernelGGL(k_pqe_pack, dim3(groups, copy_rows(a.m)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_pqe_size, dim3(a.nchunks < smc::kCopyGroups ? a.nchunks : smc::kCopyGroups), dim3(256), 0, s, a);
+  if (a.m) hipLaunchKernelGGL(k_pqe_pack, copies, dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -547,9 +547,9 @@ int main() {
              smq_chunks_scratch_bytes(3, 0, 1000) > smq_chunks_scratch_bytes(3, 0, 1),
          "chunks scratch bytes");
   // the verdicts, the owner search and the copies' rows
-  expect(smq::chunk_verdict(true, SM_OK, smq::kNoSlot, 0) == SM_ERR_ARGUMENT &&
-             smq::chunk_verdict(false, SMQ_ERR_TRUNCATED, 3, 19) == SMQ_ERR_TRUNCATED && smq::chunk_verdict(false, SM_OK, 3, 19) == 19 &&
-             smq::chunk_verdict(false, SM_OK, smq::kNoSlot, 19) == SM_OK,
+  expect(smc::plan_verdict(true, SM_OK, smq::kNoSlot, 0) == SM_ERR_ARGUMENT &&
+             smc::plan_verdict(false, SMQ_ERR_TRUNCATED, 3, 19) == SMQ_ERR_TRUNCATED && smc::plan_verdict(false, SM_OK, 3, 19) == 19 &&
+             smc::plan_verdict(false, SM_OK, smq::kNoSlot, 19) == SM_OK,
          "chunk verdict");
   expect(smq::slot_verdict(smq::kNoSlot, true, 1, 2, true, 19) == SM_OK && smq::slot_verdict(2, true, 1, 2, true, 19) == SMQ_ERR_CRC &&
              smq::slot_verdict(2, true, 2, 2, true, 19) == 19 && smq::slot_verdict(2, false, 1, 2, true, 19) == 19 &&
@@ -560,11 +560,11 @@ int main() {
     const uint32_t f[6] = {0, 0, 2, 2, 2, 5};  // owners 1 and 4 have items
     std::memcpy(first, f, sizeof(f));
     const uint32_t want[5] = {1, 1, 4, 4, 4};
-    for (uint32_t j = 0; j < 5; ++j) expect(smq::scan_owner(first, 5, j) == want[j], "scan owner");
+    for (uint32_t j = 0; j < 5; ++j) expect(smc::slot_owner(first, 5, j) == want[j], "scan owner");
     std::free(first);
   }
-  expect(smq::copy_rows(1) == 64 && smq::copy_rows(100) == 20 && smq::copy_rows(2500) == 1 && smq::copy_rows(0) == 64 &&
-             smq::copy_rows(0x7fffffff) == 1,
+  expect(smc::copy_rows(1, smq::kCopyTypical) == 64 && smc::copy_rows(100, smq::kCopyTypical) == 20 && smc::copy_rows(2500, smq::kCopyTypical) == 1 && smc::copy_rows(0, smq::kCopyTypical) == 64 &&
+             smc::copy_rows(0x7fffffff, smq::kCopyTypical) == 1,
          "copy rows");
   {
     smq::Page p{0, 10, 8, 6, 3, 9, 3, 8, SMQ_PAGE_COMPRESSED, 0, true};

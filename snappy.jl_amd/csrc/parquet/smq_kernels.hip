@@ -9,7 +9,6 @@
 
 #include "../common/smc_device.h"
 #include "smq_chunks.h"
-#include "smq_device.h"
 #include "smq_format.h"
 #include "smq_internal.h"
 
@@ -20,11 +19,11 @@ namespace smq {
 // decoded.  The walks of a workgroup's waves are independent: no barrier in here.  The Thrift
 // reader's frames are the wave's own piece of LDS (every lane writes the same value).
 __global__ __launch_bounds__(256) void k_pq_count(DecodeChunksArgs a) {
-  __shared__ Frame frames[kWalkWaves][SMQ_MAX_DEPTH];
-  const uint32_t r = walker_chunk();
+  __shared__ Frame frames[smc::kWalkWaves][SMQ_MAX_DEPTH];
+  const uint32_t r = smc::walker_index();
   if (r >= a.nchunks) return;
   const uint64_t n = a.in_len[r];
-  WaveFetch fetch{a.in + a.in_off[r], n, threadIdx.x & 63};
+  smc::WindowFetch fetch{a.in + a.in_off[r], n, threadIdx.x & 63};
   const Walk w = walk_pages(n, fetch, frames[threadIdx.x >> 6], [](uint32_t, uint64_t, const Page&) {});
   if (fetch.lane == 0) {
     const ChunkPlan p = chunk_plan(w, a.out_cap[r]);
@@ -38,18 +37,8 @@ __global__ __launch_bounds__(256) void k_pq_count(DecodeChunksArgs a) {
 // the exclusive scan of the chunks' slots against the bound m, by one workgroup
 __global__ __launch_bounds__(256) void k_pq_scan(DecodeChunksArgs a) {
   __shared__ uint64_t sh[4];
-  const uint64_t sum = tile_scan(a.nchunks, sh, [&](uint32_t r) { return a.s.count[r]; }, [&](uint32_t r, uint64_t, uint64_t at) {
-    a.s.first[r] = smc::sat32(at);
-    if (a.page_first) a.page_first[r] = smc::sat32(at);
-  });
-  if (threadIdx.x == 0) {
-    const bool over = sum > a.m;
-    a.s.first[a.nchunks] = smc::sat32(sum);
-    if (a.page_first) a.page_first[a.nchunks] = smc::sat32(sum);
-    a.s.hdr->over = over ? 1u : 0u;
-    a.s.hdr->total = over ? 0u : (uint32_t)sum;
-    a.s.hdr->segments = 0;
-  }
+  smc::count_scan(a.nchunks, a.m, [&](uint32_t r) { return a.s.count[r]; }, a.s.first, a.page_first, a.s.hdr, sh);
+  if (threadIdx.x == 0) a.s.hdr->segments = 0;
 }
 
 // The slots no page took (all of them over the bound) become empty: nothing to copy, to check or to
@@ -60,7 +49,7 @@ __global__ __launch_bounds__(256) void k_pq_scan(DecodeChunksArgs a) {
 // no room.  The walk is the counting walk's over the same bytes; a slot past the chunk's count is
 // never stored.
 __global__ __launch_bounds__(256) void k_pq_fill(DecodeChunksArgs a) {
-  __shared__ Frame frames[kWalkWaves][SMQ_MAX_DEPTH];
+  __shared__ Frame frames[smc::kWalkWaves][SMQ_MAX_DEPTH];
   for (uint64_t j = (uint64_t)a.s.hdr->total + (uint64_t)blockIdx.x * 256u + threadIdx.x; j < a.m; j += (uint64_t)gridDim.x * 256u) {
     a.s.body_off[j] = 0;
     a.s.page_out[j] = 0;
@@ -76,12 +65,12 @@ __global__ __launch_bounds__(256) void k_pq_fill(DecodeChunksArgs a) {
     a.s.crc_got[j] = 0;
     if (a.table) store_page(a.pages, j, 0, Page{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, false});
   }
-  const uint32_t r = walker_chunk();
+  const uint32_t r = smc::walker_index();
   if (r >= a.nchunks || a.s.hdr->over) return;
   const uint32_t cnt = a.s.count[r], base = a.s.first[r];
   if (cnt == 0) return;
   const uint64_t in_off = a.in_off[r], out_off = a.out_off[r], n = a.in_len[r];
-  WaveFetch fetch{a.in + in_off, n, threadIdx.x & 63};
+  smc::WindowFetch fetch{a.in + in_off, n, threadIdx.x & 63};
   const uint32_t lane = fetch.lane;
   walk_pages(n, fetch, frames[threadIdx.x >> 6], [&](uint32_t k, uint64_t at, const Page& p) {
     if (lane != 0 || k >= cnt) return;
@@ -109,7 +98,7 @@ __global__ __launch_bounds__(256) void k_pq_fill(DecodeChunksArgs a) {
 __global__ __launch_bounds__(256) void k_pq_segments(DecodeChunksArgs a) {
   __shared__ uint64_t sh[4];
   const uint32_t used = a.s.hdr->total;
-  const uint64_t sum = tile_scan(
+  const uint64_t sum = smc::tile_scan(
       used, sh, [&](uint32_t j) -> uint64_t { return (a.s.flags[j] & SMQ_PAGE_HAS_CRC) ? crc_segments(a.s.body_len[j]) : 0u; },
       [&](uint32_t j, uint64_t, uint64_t at) { a.s.seg_first[j] = smc::sat32(at); });
   if (threadIdx.x == 0) {
@@ -119,7 +108,7 @@ __global__ __launch_bounds__(256) void k_pq_segments(DecodeChunksArgs a) {
 }
 
 hipError_t launch_decode_plan(const DecodeChunksArgs& a, hipStream_t s) {
-  const uint32_t walkers = (a.nchunks + kWalkWaves - 1) / kWalkWaves;
+  const uint32_t walkers = (a.nchunks + smc::kWalkWaves - 1) / smc::kWalkWaves;
   hipLaunchKernelGGL(k_pq_count, dim3(walkers), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_pq_scan, dim3(1), dim3(256), 0, s, a);
   if (a.m) {
@@ -138,7 +127,7 @@ __global__ __launch_bounds__(256) void k_pq_copy(DecodeChunksArgs a) {
   for (uint32_t j = blockIdx.x; j < total; j += gridDim.x) {
     const uint32_t n = a.s.copy_len[j];
     if (a.s.chunk[j] == kNoSlot || n == 0) continue;
-    copy_tiled(a.in + a.s.body_off[j], n, a.out + a.s.page_out[j]);
+    smc::copy_tiled(a.in + a.s.body_off[j], n, a.out + a.s.page_out[j]);
   }
 }
 
@@ -162,14 +151,13 @@ __global__ __launch_bounds__(256) void k_pq_result(DecodeChunksArgs a) {
   if (r >= a.nchunks) return;
   const bool over = a.s.hdr->over != 0;
   const uint32_t fail = over ? kNoSlot : a.s.fail[r];
-  a.status[r] = chunk_verdict(over, a.s.pre[r], fail, fail != kNoSlot ? a.s.dec_status[fail] : (int32_t)SM_OK);
+  a.status[r] = smc::plan_verdict(over, a.s.pre[r], fail, fail != kNoSlot ? a.s.dec_status[fail] : (int32_t)SM_OK);
   a.out_len[r] = over ? 0 : a.s.length[r];
 }
 
 hipError_t launch_decode_result(const DecodeChunksArgs& a, const CrcLut* T, hipStream_t s) {
   if (a.m) {
-    const uint32_t groups = a.m < 8 * kCopyGroups ? a.m : 8 * kCopyGroups;
-    hipLaunchKernelGGL(k_pq_copy, dim3(groups, copy_rows(a.m)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_pq_copy, smc::copy_grid(a.m, kCopyTypical), dim3(256), 0, s, a);
     if (a.verify_crc) {
       const hipError_t e = launch_crc_segments(CrcJobs{a.in, a.s.body_off, a.s.body_len, nullptr, a.s.seg_first, a.m, a.s.hdr, a.s.crc_got}, T, s);
       if (e != hipSuccess) return e;

@@ -7,7 +7,6 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <algorithm>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -16,6 +15,7 @@
 #include "../../../include/snappy_mi355x_multi.h"
 #include "../common/smc_hip_host.h"
 #include "../common/smc_layout.h"
+#include "../common/smc_staging.h"
 #include "smt_format.h"
 #include "smt_internal.h"
 
@@ -243,24 +243,8 @@ sm_status smt_compress_blocks_device(smt_ctx* ctx, const uint8_t* d_in, const ui
 
 }  // extern "C"
 
-// ---- host buffers --------------------------------------------------------------------------------
-namespace {
-
-using smt::round16;
-
-// uploads n elements of a host array behind one another in the ctx's argument scratch
-struct ArgUpload {
-  smc::Carve c;
-  hipStream_t s;
-  template <typename T>
-  T* put(const T* host, size_t n, hipError_t& e) {
-    T* const d = c.take<T>(n);
-    if (e == hipSuccess && host && n) e = hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, s);
-    return d;
-  }
-};
-
-}  // namespace
+// ---- host buffers (../common/smc_staging.h) ------------------------------------------------------
+using smc::round16;
 
 extern "C" {
 
@@ -280,8 +264,7 @@ sm_status smt_uncompress_tables(smt_ctx* ctx, const uint8_t* in, const uint64_t*
       entries != (block_status != nullptr))
     return SM_ERR_ARGUMENT;
   // the bounds on the host: each table's decoded index length, and the entries that many bytes hold
-  std::vector<uint64_t> h_in_off(ntables), h_out_off(ntables);
-  uint64_t in_total = 0, out_total = 0, index_bytes = 0, blocks = 0;
+  uint64_t index_bytes = 0, blocks = 0;
   for (uint32_t t = 0; t < ntables; ++t) {
     if (in_len[t] && !in) return SM_ERR_ARGUMENT;
     if (out_cap[t] && !out) return SM_ERR_ARGUMENT;
@@ -290,31 +273,24 @@ sm_status smt_uncompress_tables(smt_ctx* ctx, const uint8_t* in, const uint64_t*
       index_bytes += round16(ib);
       blocks += smt_max_blocks(ib);
     }
-    h_in_off[t] = in_total;
-    in_total += in_len[t];
-    h_out_off[t] = out_total;
-    out_total += round16(out_cap[t]);
   }
   if (blocks > smt::kMaxCount) return SM_ERR_INPUT_TOO_LARGE;
-  uint64_t fragments = blocks + out_total / 65536;  // (a hint: what the decoded tables' blocks can hold)
+  const StreamStaging h(in, in_off, in_len, ntables, out_cap);
+  uint64_t fragments = blocks + h.out_total / 65536;  // (a hint: what the decoded tables' blocks can hold)
   if (fragments > smt::kMaxCount) fragments = 0;
   const uint32_t m = (uint32_t)blocks;
-  std::vector<uint8_t> bytes((size_t)in_total);
-  for (uint32_t t = 0; t < ntables; ++t)
-    if (in_len[t]) memcpy(bytes.data() + h_in_off[t], in + in_off[t], (size_t)in_len[t]);
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
+  const StagingBufs b{ctx->io_in, ctx->io_out, ctx->sarg, ctx->stream};
   hipStream_t s = ctx->stream;
-  SM_CHECK(ctx->io_in.ensure(std::max<size_t>(bytes.size(), 1)));
-  SM_CHECK(ctx->io_out.ensure(std::max<size_t>((size_t)out_total, 1)));
   const size_t n = ntables, e8 = round16(8 * (size_t)m + 8), e4 = round16(4 * (size_t)m + 4);
-  SM_CHECK(ctx->sarg.ensure(5 * round16(8 * n) + 2 * round16(4 * (n + 1)) + 3 * e8 + e4));
+  SM_PASS(ensure_staging(b, h.bytes.size(), (size_t)h.out_total, 5 * round16(8 * n) + 2 * round16(4 * (n + 1)) + 3 * e8 + e4));
   ArgUpload up{smc::Carve{(uintptr_t)ctx->sarg.p}, s};
   hipError_t e = hipSuccess;
-  if (!bytes.empty()) e = hipMemcpyAsync(ctx->io_in.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s);
-  const uint64_t* const d_in_off = up.put(h_in_off.data(), n, e);
+  if (!h.bytes.empty()) e = hipMemcpyAsync(ctx->io_in.p, h.bytes.data(), h.bytes.size(), hipMemcpyHostToDevice, s);
+  const uint64_t* const d_in_off = up.put(h.in_off.data(), n, e);
   const uint64_t* const d_in_len = up.put(in_len, n, e);
-  const uint64_t* const d_out_off = up.put(h_out_off.data(), n, e);
+  const uint64_t* const d_out_off = up.put(h.out_off.data(), n, e);
   const uint64_t* const d_out_cap = up.put(out_cap, n, e);
   uint64_t* const d_out_len = up.put((const uint64_t*)nullptr, n, e);
   int32_t* const d_status = up.put((const int32_t*)nullptr, n, e);
@@ -328,16 +304,14 @@ sm_status smt_uncompress_tables(smt_ctx* ctx, const uint8_t* in, const uint64_t*
   SM_PASS(smt_uncompress_tables_device(ctx, (const uint8_t*)ctx->io_in.p, d_in_off, d_in_len, ntables, m, index_bytes,
                                        (uint32_t)fragments, verify_crc, (uint8_t*)ctx->io_out.p, d_out_off, d_out_cap, d_out_len,
                                        d_status, d_first, d_hoff, d_hsize, nullptr, d_blen, d_bstatus, s));
-  std::vector<uint8_t> decoded((size_t)out_total);
+  std::vector<uint8_t> decoded;
   std::vector<uint32_t> first(n + 1);
-  SM_CHECK(hipMemcpyAsync(out_len, d_out_len, 8 * n, hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipMemcpyAsync(status, d_status, 4 * n, hipMemcpyDeviceToHost, s));
+  SM_PASS(download_results(b, d_out_len, d_status, n, out_len, status));
   SM_CHECK(hipMemcpyAsync(first.data(), d_first, 4 * (n + 1), hipMemcpyDeviceToHost, s));
-  if (!decoded.empty()) SM_CHECK(hipMemcpyAsync(decoded.data(), ctx->io_out.p, decoded.size(), hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipStreamSynchronize(s));
+  SM_PASS(download_output(b, h.out_total, decoded));
   for (uint32_t t = 0; t < ntables; ++t)
     if (status[t] != SM_ERR_ARGUMENT && out_len[t] && out_len[t] <= out_cap[t])
-      memcpy(out + out_off[t], decoded.data() + h_out_off[t], (size_t)out_len[t]);
+      memcpy(out + out_off[t], decoded.data() + h.out_off[t], (size_t)out_len[t]);
   if (!entries) return SM_OK;
   const uint32_t total = first[n];
   if (total > m) return SM_ERR_DEVICE;
@@ -372,11 +346,10 @@ sm_status smt_uncompress_blocks(smt_ctx* ctx, const uint8_t* in, size_t n, const
   if (fragments > smt::kMaxCount) fragments = 0;
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
+  const StagingBufs b{ctx->io_in, ctx->io_out, ctx->sarg, ctx->stream};
   hipStream_t s = ctx->stream;
-  SM_CHECK(ctx->io_in.ensure(std::max<size_t>(n, 1)));
-  SM_CHECK(ctx->io_out.ensure(std::max<size_t>((size_t)out_total, 1)));
   const size_t k = nblocks;
-  SM_CHECK(ctx->sarg.ensure(5 * round16(8 * k) + round16(4 * k)));
+  SM_PASS(ensure_staging(b, n, (size_t)out_total, 5 * round16(8 * k) + round16(4 * k)));
   ArgUpload up{smc::Carve{(uintptr_t)ctx->sarg.p}, s};
   hipError_t e = hipMemcpyAsync(ctx->io_in.p, in, n, hipMemcpyHostToDevice, s);
   const uint64_t* const d_off = up.put(blk_off, k, e);
@@ -388,11 +361,9 @@ sm_status smt_uncompress_blocks(smt_ctx* ctx, const uint8_t* in, size_t n, const
   SM_CHECK(e);
   SM_PASS(smt_uncompress_blocks_device(ctx, (const uint8_t*)ctx->io_in.p, d_off, d_size, nblocks, (uint32_t)fragments, verify_crc,
                                        (uint8_t*)ctx->io_out.p, d_out_off, d_out_cap, d_out_len, d_status, s));
-  std::vector<uint8_t> decoded((size_t)out_total);
-  SM_CHECK(hipMemcpyAsync(out_len, d_out_len, 8 * k, hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipMemcpyAsync(status, d_status, 4 * k, hipMemcpyDeviceToHost, s));
-  if (!decoded.empty()) SM_CHECK(hipMemcpyAsync(decoded.data(), ctx->io_out.p, decoded.size(), hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipStreamSynchronize(s));
+  std::vector<uint8_t> decoded;
+  SM_PASS(download_results(b, d_out_len, d_status, k, out_len, status));
+  SM_PASS(download_output(b, out_total, decoded));
   for (uint32_t j = 0; j < nblocks; ++j)
     if (out_len[j] && out_len[j] <= out_cap[j]) memcpy(out + out_off[j], decoded.data() + h_out_off[j], (size_t)out_len[j]);
   return SM_OK;
@@ -432,11 +403,11 @@ sm_status smt_compress_blocks(smt_ctx* ctx, const uint8_t* in, const uint32_t* b
     if (block_len[j]) memcpy(bytes.data() + h_block_off[j], in + block_off[j], block_len[j]);
   std::lock_guard<std::mutex> lock(ctx->mu);
   DeviceGuard g(ctx->device);
+  const StagingBufs b{ctx->io_in, ctx->io_out, ctx->sarg, ctx->stream};
   hipStream_t s = ctx->stream;
-  SM_CHECK(ctx->io_in.ensure(std::max<size_t>(bytes.size(), 1)));
-  SM_CHECK(ctx->io_out.ensure(std::max<size_t>((size_t)out_total, 1)));
   const size_t n = ntables;
-  SM_CHECK(ctx->sarg.ensure(2 * round16(8 * n) + 2 * round16(4 * (n + 1)) + 3 * round16(8 * (size_t)m + 8) + round16(4 * (size_t)m + 4)));
+  SM_PASS(ensure_staging(b, bytes.size(), (size_t)out_total,
+                         2 * round16(8 * n) + 2 * round16(4 * (n + 1)) + 3 * round16(8 * (size_t)m + 8) + round16(4 * (size_t)m + 4)));
   ArgUpload up{smc::Carve{(uintptr_t)ctx->sarg.p}, s};
   hipError_t e = hipSuccess;
   if (!bytes.empty()) e = hipMemcpyAsync(ctx->io_in.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, s);
@@ -452,15 +423,13 @@ sm_status smt_compress_blocks(smt_ctx* ctx, const uint8_t* in, const uint32_t* b
   SM_PASS(smt_compress_blocks_device(ctx, (const uint8_t*)ctx->io_in.p, d_first, d_block_off, d_block_len, ntables, m, stage,
                                      (uint32_t)fragments, (uint8_t*)ctx->io_out.p, d_out_off, d_hoff, d_hsize, d_out_len, d_status,
                                      mode, s));
-  std::vector<uint8_t> packed((size_t)out_total);
-  SM_CHECK(hipMemcpyAsync(out_len, d_out_len, 8 * n, hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipMemcpyAsync(status, d_status, 4 * n, hipMemcpyDeviceToHost, s));
+  std::vector<uint8_t> packed;
+  SM_PASS(download_results(b, d_out_len, d_status, n, out_len, status));
   if (m) {
     SM_CHECK(hipMemcpyAsync(handle_off, d_hoff, 8 * (size_t)m, hipMemcpyDeviceToHost, s));
     SM_CHECK(hipMemcpyAsync(handle_size, d_hsize, 8 * (size_t)m, hipMemcpyDeviceToHost, s));
   }
-  if (!packed.empty()) SM_CHECK(hipMemcpyAsync(packed.data(), ctx->io_out.p, packed.size(), hipMemcpyDeviceToHost, s));
-  SM_CHECK(hipStreamSynchronize(s));
+  SM_PASS(download_output(b, out_total, packed));
   for (uint32_t t = 0; t < ntables; ++t) {
     if (out_len[t] > room[t]) return SM_ERR_DEVICE;
     if (status[t] == SM_OK && out_len[t]) memcpy(out + out_off[t], packed.data() + h_out_off[t], (size_t)out_len[t]);

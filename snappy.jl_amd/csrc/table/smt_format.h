@@ -11,6 +11,7 @@
 
 #include "../../../include/snappy_mi355x_table.h"
 #include "../common/smc_layout.h"
+#include "../common/smc_slots.h"
 
 namespace smt {
 
@@ -168,18 +169,6 @@ SMC_HD inline int32_t table_plan(int32_t index_status, int32_t head_status, uint
   return total > cap ? (int32_t)SM_BUFFER_TOO_SMALL : (int32_t)SM_OK;
 }
 
-// The table of entry j: first[t] <= j < first[t + 1] in the scan first[0, ntables] (of equal
-// entries the last one, so tables without entries are passed over).  j < first[ntables].
-SMC_HD inline uint32_t entry_table(const uint32_t* first, uint32_t ntables, uint32_t j) {
-  uint32_t lo = 0, hi = ntables;
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (first[mid] <= j) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // ---- the encoder rule ---------------------------------------------------------------------------
 // LevelDB's 12.5 % rule
 SMC_HD inline bool keep_compressed(int32_t comp_status, uint32_t clen, uint32_t len) {
@@ -189,7 +178,7 @@ SMC_HD inline uint64_t max_block_length(uint64_t len) { return len + kTrailer; }
 SMC_HD inline uint64_t stage_length(uint64_t len) { return (smc::max_compressed_length(len) + 15) / 16 * 16; }
 SMC_HD inline uint64_t decode_fragments(uint64_t ulen) { return (ulen + 65535) / 65536; }
 SMC_HD inline uint64_t encode_fragments(uint64_t len) { return len > 65536 ? (len + 65535) / 65536 : 0; }
-SMC_HD inline uint64_t round16(uint64_t n) { return (n + 15) / 16 * 16; }
+using smc::round16;
 
 // bytes of v as a varint64, and byte i of them
 SMC_HD inline uint32_t varint64_len(uint64_t v) {
@@ -208,10 +197,7 @@ SMC_HD inline uint8_t varint64_byte(uint64_t v, uint32_t i, uint32_t nb) {
 const char* host_message(sm_status st);  // smt_host.cpp: the SMT_ERR_* texts, else NULL
 
 // ---- scratch (smc::Carve: a null base measures) ------------------------------------------------
-struct Header {
-  uint32_t total;  // entries (blocks) in use; 0 over a bound
-  uint32_t over;   // the batch needs more than one of the caller's bounds
-};
+using Header = smc::PlanHeader;  // total: entries (blocks) in use; over: more than one of the caller's bounds
 
 struct Decode {
   Header* hdr;

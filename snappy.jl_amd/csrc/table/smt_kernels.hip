@@ -17,59 +17,13 @@ namespace smt {
 
 namespace {
 
-constexpr uint32_t kWalkWaves = 4;  // tables a workgroup of the walkers takes: one per wave
-constexpr uint32_t kWindow = 64;    // bytes of an index block a wave holds: one per lane
 constexpr uint32_t kCopyRows = 4;   // workgroups that share one block's copy
-
-// The index walker's fetch (walk_index), by one wave.  An entry's three varints and its handle have
-// no fixed place, so the wave keeps a window of kWindow bytes of the decoded index, a byte a lane,
-// read by one load; fetch(pos) reads the byte out of its lane into a scalar register, so the parse
-// is the wave's, not a lane's.  When the cursor leaves the window the window is read again from the
-// cursor on: a key longer than the window costs nothing, the cursor steps over it and the next
-// window starts at the value behind it.  Bytes at or behind the contents' end are not read.
-struct WaveFetch {
-  const uint8_t* in;
-  uint64_t n;
-  uint32_t lane;
-  uint64_t base = 0;
-  uint32_t mine = 0;
-  bool valid = false;
-  __device__ uint32_t operator()(uint64_t pos) {
-    if (!valid || pos < base || pos - base >= kWindow) {
-      base = pos;
-      mine = base + lane < n ? in[base + lane] : 0u;
-      valid = true;
-    }
-    const uint32_t at = __builtin_amdgcn_readfirstlane((uint32_t)(pos - base));
-    return (uint32_t)__builtin_amdgcn_readlane((int)mine, (int)at) & 0xffu;
-  }
-};
 
 // a thread's own bytes of global memory, one load each, at any alignment
 struct DeviceFetch {
   const uint8_t* p;
   __device__ uint32_t operator()(uint64_t pos) const { return p[pos]; }
 };
-
-__device__ inline uint32_t walker_table() {
-  return __builtin_amdgcn_readfirstlane(blockIdx.x * kWalkWaves + (threadIdx.x >> 6));
-}
-
-// The exclusive scan of value(i), i < n, by one workgroup (block_scan's contract: 256 threads, sh
-// its 4 u64 of LDS), tile by tile: each(i, value(i), the sum before i).  Returns the total to every thread.
-template <typename Value, typename Each>
-__device__ inline uint64_t tile_scan(uint32_t n, uint64_t* sh, Value value, Each each) {
-  uint64_t carry = 0;
-  for (uint32_t b0 = 0; b0 < n; b0 += 256) {  // (uniform: every thread takes every tile)
-    const uint32_t i = b0 + threadIdx.x;
-    const uint64_t v = i < n ? value(i) : 0u;
-    uint64_t total;
-    const uint64_t ex = smc::block_scan(v, sh, total);
-    if (i < n) each(i, v, carry + ex);
-    carry += total;
-  }
-  return carry;
-}
 
 // Block j's arguments for the multi library's two calls, the copy and the checksum call.  A block
 // that is not decoded is an empty stream with no room, which those calls return from at once.
@@ -120,7 +74,7 @@ __global__ __launch_bounds__(256) void k_tab_footer(DecodeArgs a) {
 // max_index_bytes, then per table the arguments of the decode, the copy and the checksum call.
 __global__ __launch_bounds__(256) void k_tab_place(DecodeArgs a) {
   __shared__ uint64_t sh[4];
-  const uint64_t sum = tile_scan(
+  const uint64_t sum = smc::tile_scan(
       a.nt, sh, [&](uint32_t t) { return round16(a.s.ix_len[t]); }, [&](uint32_t t, uint64_t, uint64_t at) { a.s.ix_out_off[t] = at; });
   const bool over = sum > a.index_bytes;
   if (threadIdx.x == 0) {
@@ -167,9 +121,9 @@ __global__ __launch_bounds__(256) void k_tab_verdict(DecodeArgs a) {
 // The counting walk, one wave per table, over the table's decoded index block in the scratch.  The
 // walks of a workgroup's waves are independent: no barrier in here.
 __global__ __launch_bounds__(256) void k_tab_count(DecodeArgs a) {
-  const uint32_t t = walker_table();
+  const uint32_t t = smc::walker_index();
   if (t >= a.nt || a.s.hdr->over || a.s.ix_status[t] != SM_OK) return;
-  WaveFetch fetch{a.s.index + a.s.ix_out_off[t], a.s.ix_len[t], threadIdx.x & 63};
+  smc::WindowFetch fetch{a.s.index + a.s.ix_out_off[t], a.s.ix_len[t], threadIdx.x & 63};
   const IndexWalk w = walk_index(fetch, a.s.ix_len[t], a.s.t_len[t], [](uint32_t, const Handle&) {});
   if (fetch.lane == 0) {
     a.s.count[t] = w.status == SM_OK ? w.nblocks : 0u;
@@ -180,7 +134,7 @@ __global__ __launch_bounds__(256) void k_tab_count(DecodeArgs a) {
 // The exclusive scan of the tables' entries against the bound m, by one workgroup.
 __global__ __launch_bounds__(256) void k_tab_scan(DecodeArgs a) {
   __shared__ uint64_t sh[4];
-  const uint64_t sum = tile_scan(
+  const uint64_t sum = smc::tile_scan(
       a.nt, sh, [&](uint32_t t) { return a.s.count[t]; }, [&](uint32_t t, uint64_t, uint64_t at) { a.s.first[t] = smc::sat32(at); });
   if (threadIdx.x == 0) {
     const bool over = a.s.hdr->over != 0 || sum > a.m;
@@ -198,11 +152,11 @@ __global__ __launch_bounds__(256) void k_tab_fill(DecodeArgs a) {
     a.s.h_size[j] = 0;
     a.s.b_table[j] = kNone;
   }
-  const uint32_t t = walker_table();
+  const uint32_t t = smc::walker_index();
   if (t >= a.nt || a.s.hdr->over) return;
   const uint32_t cnt = a.s.count[t], base = a.s.first[t];
   if (cnt == 0) return;
-  WaveFetch fetch{a.s.index + a.s.ix_out_off[t], a.s.ix_len[t], threadIdx.x & 63};
+  smc::WindowFetch fetch{a.s.index + a.s.ix_out_off[t], a.s.ix_len[t], threadIdx.x & 63};
   const uint32_t lane = fetch.lane;
   walk_index(fetch, a.s.ix_len[t], a.s.t_len[t], [&](uint32_t k, const Handle& h) {
     if (lane != 0 || k >= cnt) return;
@@ -227,7 +181,7 @@ __global__ __launch_bounds__(256) void k_tab_index_result(DecodeArgs a) {
 }
 
 hipError_t launch_index_walk(const DecodeArgs& a, hipStream_t s) {
-  const uint32_t walkers = (a.nt + kWalkWaves - 1) / kWalkWaves;
+  const uint32_t walkers = (a.nt + smc::kWalkWaves - 1) / smc::kWalkWaves;
   hipLaunchKernelGGL(k_tab_copy, dim3(a.nt, kCopyRows), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_tab_verdict, dim3((a.nt + 255) / 256), dim3(256), 0, s, a);
   hipLaunchKernelGGL(k_tab_count, dim3(walkers), dim3(256), 0, s, a);
@@ -266,7 +220,7 @@ __global__ __launch_bounds__(256) void k_blk_head(DecodeArgs a) {
 __global__ __launch_bounds__(256) void k_blk_scan(DecodeArgs a) {
   __shared__ uint64_t sh[4];
   const uint32_t used = a.s.hdr->total;
-  const uint64_t sum = tile_scan(
+  const uint64_t sum = smc::tile_scan(
       used, sh, [&](uint32_t j) { return a.s.b_decl[j]; }, [&](uint32_t j, uint64_t, uint64_t at) { a.s.prefix[j] = at; });
   if (threadIdx.x == 0) a.s.prefix[used] = sum;
 }
@@ -400,7 +354,7 @@ __global__ __launch_bounds__(256) void k_ctab_plan(CompressArgs a) {
   const uint32_t total = a.block_first[a.nt];
   const uint32_t used = total > a.m ? 0u : total;
   uint64_t mine = 0;  // the fragments of this thread's blocks: a sum, not a scan
-  const uint64_t stage = tile_scan(
+  const uint64_t stage = smc::tile_scan(
       used, sh,
       [&](uint32_t j) {
         const uint32_t len = a.block_len[j];
@@ -425,7 +379,7 @@ __global__ __launch_bounds__(256) void k_ctab_slots(CompressArgs a) {
   if (j >= a.m) return;
   const bool used = j < a.s.hdr->total;
   const uint32_t len = used ? a.block_len[j] : 0u;
-  const uint32_t t = used ? entry_table(a.block_first, a.nt, j) : kNone;
+  const uint32_t t = used ? smc::slot_owner(a.block_first, a.nt, j) : kNone;
   const bool fits = len <= kMaxSize;
   a.s.in_off[j] = used ? a.block_off[j] : 0u;
   a.s.in_len[j] = fits ? len : 0u;
@@ -447,7 +401,7 @@ hipError_t launch_compress_plan(const CompressArgs& a, hipStream_t s) {
 __global__ __launch_bounds__(256) void k_ctab_sizes(CompressArgs a) {
   __shared__ uint64_t sh[4];
   const uint32_t used = a.s.hdr->total;
-  const uint64_t sum = tile_scan(
+  const uint64_t sum = smc::tile_scan(
       used, sh,
       [&](uint32_t j) -> uint64_t {
         const uint32_t len = a.s.in_len[j];

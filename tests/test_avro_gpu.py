@@ -277,6 +277,17 @@ def test_flipped_payload_bytes(av):
     assert R.CRC in seen and seen & {19, 20, 21} and len(seen) >= 3, seen
 
 
+def test_streams_past_one_scan_tile(av):
+    """301 streams in one batch, every third cut short (a walk error: no slots): the scan of the
+    streams' slot counts runs over two tiles of 256 with zeros among the counts, and block_first is
+    the model's on both sides of the edge."""
+    meta = fixture("meta_forms.avro")  # (four blocks)
+    streams = [meta[:-5] if i % 3 == 1 else meta for i in range(301)]
+    res, models = decode_case(av, streams, table=False)
+    assert [m.slots for m in models[255:258]] == [4, 0, 4]
+    assert res["status"][256] != 0 and res["status"][255] == 0 and res["status"][300] == 0
+
+
 def test_block_runs_behind_every_marker(av):
     small = fixture("small_blocks.avro")
     w = R.walk(small)

@@ -109,6 +109,10 @@ def test_framing_rules_have_one_definition():
         found = sorted(f for f, text in framing.items()
                        for _ in re.finditer(r"\b[\w:<>]+[\s\*&]+%s\s*\([^;{}]*\)\s*\{" % name, text))
         assert found == [where], (name, found)
+    # ... and scan_counts is a forwarder: the scan itself is defined once in all of csrc/, in common/
+    found = _definitions(r"\b[\w:<>]+[\s\*&]+count_scan\s*\([^;{}]*\)\s*\{")
+    assert found == ["common/smc_device.h"], found
+    assert len(re.findall(r"\btile_scan\b", framing["framing/smf_device.h"])) == 0
     fetch = sorted(f for f, text in framing.items() for _ in re.finditer(r"\bstruct\s+WaveFetch\b\s*\{", text))
     assert fetch == ["framing/smf_device.h"], fetch
     for f in ("framing/smf_slots.h", "framing/smf_format.h"):  # the sanitizer driver compiles them for the host
@@ -193,3 +197,66 @@ def test_emit_rules_have_one_definition():
     for name in ("block_literal_bytes", "put_literal_head"):  # ... and its literal comes from the shared rules
         assert len(re.findall(r"\b%s\s*\(" % name, src["sm_gather.hip"])) >= 2, name
     assert re.search(r"\bk_gather_parts\s*\(", src["sm_gather.hip"]) and re.search(r"\bk_gather_parts_batch\s*\(", src["sm_gather.hip"])
+
+
+def test_container_helpers_have_one_definition():
+    """What the container libraries (framing, blocks, orc, parquet, avro, table) share exists once,
+    under csrc/common/: the tiled scan and the count scan over it, the tiled copy, the slot rules
+    (owner search, group rule, copy rows, round16), the host-buffer calls' staging and the two
+    one-wave fetches that read lanes into scalar registers.  The framing library's __shfl fetch stays
+    its own."""
+    src = _sources()
+    for name in ("tile_scan", "count_scan", "copy_tiled", "copy_grid", "copy_rows", "slot_owner", "plan_verdict", "round16",
+                 "walker_index", "carve_stream_call", "upload_stream_call", "download_results", "download_output"):
+        found = _definitions(r"\b[\w:<>]+[\s\*&]+%s\s*\([^;{}]*\)\s*\{" % name)
+        assert len(found) == 1 and found[0].startswith("common/"), (name, found)
+    for name in ("StreamStaging", "StreamCallArrays", "ArgUpload", "PlanHeader"):
+        found = _definitions(r"\bstruct\s+%s\b\s*\{" % name)
+        assert found == ["common/smc_staging.h"] or (name == "PlanHeader" and found == ["common/smc_slots.h"]), (name, found)
+    for name in ("kNoSlot", "kCopyTile", "kCopyGroups", "kWalkWaves", "kWindow"):
+        found = _definitions(r"\bconstexpr\s+uint32_t\s+%s\s*=" % name)
+        # (the framing streams' walkers keep their own count of waves beside their own fetch; the multi
+        # library's ranged decode has a mark of its own under that name)
+        assert [f for f in found if f not in ("framing/smf_streams.hip", "multi/smm_range.h")] == ["common/smc_device.h" if name in ("kWalkWaves", "kWindow")
+                                                                        else "common/smc_slots.h"], (name, found)
+    # by their bodies, whatever a copy would be called: the binary search of a scan, the group rule,
+    # the rounding, the tile loop, the staging's upload of a byte at the least
+    forms = {
+        "owner search": r"first\s*\[\s*mid\s*\]\s*<=\s*j",
+        "group rule": r"fail\s*!=\s*\w+\s*\?\s*fail_status",
+        "tile loop": r"blockIdx\.y\s*\*\s*kCopyTile",
+        "count scan": r"total\s*=\s*over\s*\?\s*0u\s*:\s*\(uint32_t\)\s*sum",
+        "staging ensure": r"io_out\s*\.\s*ensure\s*\(",
+        "window fetch": r"pos\s*-\s*base\s*>=\s*kWindow",
+    }
+    where = {"owner search": "common/smc_slots.h", "group rule": "common/smc_slots.h", "tile loop": "common/smc_device.h",
+             "count scan": "common/smc_device.h", "staging ensure": "common/smc_staging.h", "window fetch": "common/smc_device.h"}
+    for what, pattern in forms.items():
+        # (the multi library, which the containers sit on, keeps its own plan rules: smm_plan.h)
+        found = sorted(f for f, text in src.items()
+                       if re.search(pattern, text) and not f.endswith("_check.cpp") and not f.startswith("multi/"))
+        # (the framing library's single-stream calls size their staging themselves: no batch, no arrays)
+        found = [f for f in found if not (what == "staging ensure" and f == "framing/smf_api.hip")]
+        # (the table library's k_tab_scan carries the index stage's `over` into its own: another rule)
+        found = [f for f in found if not (what == "count scan" and f == "table/smt_kernels.hip")]
+        assert found == [where[what]], (what, found)
+    # a fetch is a struct with a lane in it: one holds the window, one the readlane head fetch, and the
+    # __shfl one is the framing library's
+    structs = {f: re.findall(r"\bstruct\s+(\w+)\s*\{[^}]*\blane\b[^}]*\}[^}]*\}", text) for f, text in src.items()}
+    fetches = sorted((f, s) for f, names in structs.items() for s in names if s.endswith("Fetch"))
+    assert fetches == [("common/smc_device.h", "HeadFetch"), ("common/smc_device.h", "WindowFetch"),
+                       ("framing/smf_device.h", "WaveFetch")], fetches
+    readlane = sorted(f for f, text in src.items() if "/" in f and "__builtin_amdgcn_readlane" in text)  # (the companions)
+    assert readlane == ["common/smc_device.h"], readlane
+    assert len(re.findall(r"__builtin_amdgcn_readlane", src["common/smc_device.h"])) == 2
+    for name in ("scan_owner", "entry_table", "slot_stream", "chunk_verdict", "stream_verdict", "walker_chunk", "walker_table",
+                 "walker_stream", "scan_slots", "ChunkCallArrays"):
+        found = [f for f, text in src.items() if re.search(r"\b%s\b" % name, text)]
+        assert not found, (name, found)
+    # the slot rules and the staging's layout compile without HIP: the host checkers build them alone
+    assert not re.search(r"#\s*include\s*[<\"]hip/", src["common/smc_slots.h"])
+    assert not re.search(r"#\s*include\s*[<\"]hip/", src["common/smc_staging.h"])
+    mk = src["common/companion.mk"].replace("\\\n", " ")
+    hdrs = re.search(r"^HDRS\s*\+=(.*)$", mk, re.M).group(1).split()
+    here = {"../" + f for f in src if f.startswith("common/") and f.endswith(".h")}
+    assert here <= set(hdrs), (here, hdrs)

@@ -3,8 +3,9 @@
 
     tools/isa_compare.py PARENT_TREE CHANGE_TREE [--work DIR]
 
-Every .hip translation unit of the three libraries (snappy.jl_amd/csrc, csrc/framing, csrc/multi)
-is compiled for the device alone to assembly with its Makefile's flags, in both trees.  Per kernel
+Every .hip translation unit of the eight library directories (snappy.jl_amd/csrc and, under it,
+framing, multi, blocks, orc, parquet, avro and table) is compiled for the device alone to assembly
+with its Makefile's flags, in both trees.  Per kernel
 (and per device function that was not inlined) the instruction stream and the .amdhsa_kernel block
 (VGPRs, SGPRs, LDS, scratch, ...) are compared as text; so is everything else in a file that both
 trees have (tables, the metadata note).  Kernels are matched by name within a library, so one that
@@ -23,10 +24,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 BASE = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-strict-aliasing", "-fPIC", "-Wall"]
 SCHED = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 CSRC = os.path.join("snappy.jl_amd", "csrc")
-# (directory, extra flags, the files that take no SCHED) -- as the three Makefiles build them
-LIBS = [(CSRC, ['-DSM_VERSION_STR="isa"'] + SCHED, {"sm_compress_sc.hip"}),
-        (os.path.join(CSRC, "framing"), [], set()),
-        (os.path.join(CSRC, "multi"), [], set())]
+# (directory, extra flags, the files that take no SCHED) -- as the Makefiles build them: the main
+# library's own, and common/companion.mk's BASE alone for every companion
+LIBS = [(CSRC, ['-DSM_VERSION_STR="isa"'] + SCHED, {"sm_compress_sc.hip"})] + [
+    (os.path.join(CSRC, d), [], set()) for d in ("framing", "multi", "blocks", "orc", "parquet", "avro", "table")]
 
 
 def command(src, extra, out):
@@ -41,7 +42,7 @@ def assemble(tree, work, tag):
             if not f.endswith(".hip"):
                 continue
             flags = [x for x in extra if f not in plain or x not in SCHED]
-            s = os.path.join(work, "%s_%s.s" % (tag, f))
+            s = os.path.join(work, "%s_%s_%s.s" % (tag, os.path.basename(d), f))
             subprocess.run(command(f, flags, s), cwd=os.path.join(tree, d), check=True)
             out[(d, f)] = open(s).read()
     return out
