@@ -27,8 +27,8 @@ import threading
 
 import numpy as np
 
-from ._binding import (RAW, check, collect, context_cache, device_caller, exclusive_scan, load, pack_blocks,
-                       slot_offsets)
+from ._binding import (RAW, check, collect, context_cache, device_caller, exclusive_scan, load, numel,
+                       pack_blocks, slot_offsets)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # SNAPPY_MI355X_LIB: alternate build of the same library (diagnostic/ablation builds only)
@@ -299,15 +299,17 @@ _device = device_caller(lib, context, SnappyError)
 def compress_batch_device(d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_len, mode="fast", stream=None,
                           device=None):
     """All arguments are torch CUDA tensors (uint8 / int64 / int32).  Asynchronous on `stream`
-    (a torch.cuda.Stream or raw hipStream_t int; default: torch's current stream)."""
-    _device("sm_compress_batch_device", d_in, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), d_out,
+    (a torch.cuda.Stream or raw hipStream_t int; default: torch's current stream).
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    _device("sm_compress_batch_device", d_in, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len), d_out,
             d_out_off, d_out_len, _mode(mode))
 
 
 def compress_fragments_device(d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_len, total_len, mode="fast",
                               stream=None, device=None):
-    """Fragments of ONE stream of total_len bytes (no per-fragment header; Q2 table size)."""
-    _device("sm_compress_fragments_device", d_in, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), d_out,
+    """Fragments of ONE stream of total_len bytes (no per-fragment header; Q2 table size).
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    _device("sm_compress_fragments_device", d_in, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len), d_out,
             d_out_off, d_out_len, int(total_len), _mode(mode))
 
 
@@ -327,7 +329,10 @@ def last_batch_parts(device=0):
 
 def uncompress_batch_device(d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status,
                             stream=None, device=None):
-    _device("sm_uncompress_batch_device", d_in, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), d_out,
+    """Block b = d_in[d_in_off[b] : d_in_off[b] + d_in_len[b]] decodes into d_out[d_out_off[b] : d_out_off[b] +
+    d_out_cap[b]]; per block d_out_len (int32) and d_status (int32).  Asynchronous on `stream`.
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    _device("sm_uncompress_batch_device", d_in, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len), d_out,
             d_out_off, d_out_cap, d_out_len, d_status)
 
 
@@ -340,31 +345,35 @@ def place_fragments_device(d_src, d_src_off, d_len, d_dst_off, d_dst, total_len,
     fragments' offsets in d_dst; d_status (int32[1], optional, zeroed by the caller) turns
     SM_ERR_DEVICE on an error-mark length, a fragment past d_dst's end or, with write_header, a
     fragment that would start inside the header (d_dst_off[b] < len(varint(total_len))); such a
-    fragment is not copied, the others and the header are."""
-    nfrag = d_len.numel()
-    if not nfrag:  # (tensors of no fragments go as null pointers)
+    fragment is not copied, the others and the header are.
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    nfrag = numel(d_len)
+    if not nfrag and hasattr(d_len, "numel"):  # (tensors of no fragments go as null pointers; what is no tensor is refused)
         d_src = d_src_off = d_len = d_dst_off = None
     _device("sm_place_fragments_device", d_dst, device, stream, d_src, d_src_off, d_len, nfrag, d_dst_off,
-            int(total_len), 1 if write_header else 0, d_dst, d_dst.numel(), d_local_off, d_status)
+            int(total_len), 1 if write_header else 0, d_dst, numel(d_dst), d_local_off, d_status)
 
 
 def uncompress_fragments_device(d_in, d_in_off, d_in_len, d_out, d_out_off, d_frag_len, d_out_len, d_status,
                                 stream=None, device=None):
     """Fragments of ONE stream (no varint headers; sm_compress_fragments_device's output):
-    fragment b must decode to exactly d_frag_len[b] bytes at d_out + d_out_off[b]."""
-    _device("sm_uncompress_fragments_device", d_in, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), d_out,
+    fragment b must decode to exactly d_frag_len[b] bytes at d_out + d_out_off[b].
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    _device("sm_uncompress_fragments_device", d_in, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len), d_out,
             d_out_off, d_frag_len, d_out_len, d_status)
 
 
 def validate_batch_device(d_in, d_in_off, d_in_len, d_status, stream=None, device=None):
     """d_status[b] = the status uncompress(block b) would return (no output written):
-    batched snappy_validate_compressed_buffer."""
-    _device("sm_validate_batch_device", d_in, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), d_status)
+    batched snappy_validate_compressed_buffer.
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    _device("sm_validate_batch_device", d_in, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len), d_status)
 
 
 def uncompressed_length_batch_device(d_in, d_in_off, d_in_len, d_len, d_status, stream=None, device=None):
-    """Batched length_uncompressed (Snappy.jl:90-92): the varint header of every block."""
-    _device("sm_uncompressed_length_batch_device", d_in, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(),
+    """Batched length_uncompressed (Snappy.jl:90-92): the varint header of every block.
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    _device("sm_uncompressed_length_batch_device", d_in, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len),
             d_len, d_status)
 
 

@@ -25,7 +25,7 @@ import numpy as np
 
 from . import HERE, MODES, SnappyError, _in_arg, _mode
 from ._binding import (AVRO, AVRO_BLOCK_KEYS, AvroBlocks, AvroSummary, check, collect, context_cache, device_caller,
-                       exclusive_scan, lay_out, load)
+                       exclusive_scan, field_dtypes, lay_out, load, numel)
 
 LIB_PATH = os.path.join(HERE, "libsnappy_mi355x_avro.so")
 
@@ -42,8 +42,7 @@ SMA_ERR_CRC = 88
 MAGIC = b"Obj\x01"
 SYNC_LENGTH = 16
 INDEX_KEYS = AVRO_BLOCK_KEYS  # sma_blocks' arrays, in its order
-BLOCK_DTYPES = {"pay_off": np.uint64, "pay_len": np.uint32, "ulen": np.uint32, "count": np.uint64, "crc": np.uint32,
-                "out_off": np.uint64}
+BLOCK_DTYPES = field_dtypes(AvroBlocks)  # the arrays' element types as the C ABI declares them (AvroBlocks.elements)
 
 AVRO_ABI_SYMBOLS = tuple(AVRO)  # exported symbols of include/snappy_mi355x_avro.h (tests/test_avro_host.py)
 
@@ -309,10 +308,6 @@ def find_sync(streams, syncs, queries, device=0):
 _device = device_caller(lib, context, AvroError)
 
 
-def _table(d_blocks):
-    return None if d_blocks is None else ctypes.byref(AvroBlocks(*(d_blocks[k].data_ptr() for k in INDEX_KEYS)))
-
-
 def uncompress_avro_streams_device(d_in, d_in_off, d_in_len, max_blocks, max_fragments, d_out, d_out_off, d_out_cap, d_out_len,
                                    d_status, kind="file", d_sync=None, verify_crc=True, d_objects=None, d_block_first=None,
                                    d_block_status=None, d_blocks=None, stream=None, device=None):
@@ -323,18 +318,21 @@ def uncompress_avro_streams_device(d_in, d_in_off, d_in_len, max_blocks, max_fra
     second total, or 0) lets blocks of more than 64 KiB decode by fragments.  Optional, both or
     neither: d_block_first int32[nstreams + 1], d_block_status int32[max_blocks].  Optional: d_blocks,
     a dict of tensors of max_blocks entries keyed as INDEX_KEYS (int64 for pay_off, count and out_off,
-    int32 for the others), the block table.  Nothing is synchronised."""
+    int32 for the others), the block table.  Nothing is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API).
+    Length not checked: d_sync, d_blocks, d_block_status."""
     _device("sma_uncompress_streams_device", d_out, device, stream, _kind(kind), d_in, d_in_off, d_in_len, d_sync,
-            d_in_len.numel(), int(max_blocks), int(max_fragments), 1 if verify_crc else 0, d_out, d_out_off, d_out_cap, d_out_len,
-            d_status, d_objects, d_block_first, _table(d_blocks), d_block_status)
+            numel(d_in_len), int(max_blocks), int(max_fragments), 1 if verify_crc else 0, d_out, d_out_off, d_out_cap, d_out_len,
+            d_status, d_objects, d_block_first, d_blocks, d_block_status)
 
 
 def find_sync_device(d_in, d_in_off, d_in_len, d_sync, d_q_stream, d_q_from, d_pos, stream=None, device=None):
     """sma_find_sync_device: d_pos[i] (int64) = the first position at or after d_q_from[i] (int64) of
     stream d_q_stream[i] (int32) that holds the stream's marker d_sync[16 s : 16 s + 16], else the
-    stream's length.  Nothing is synchronised."""
-    _device("sma_find_sync_device", d_pos, device, stream, d_in, d_in_off, d_in_len, d_sync, d_in_len.numel(), d_q_stream,
-            d_q_from, d_q_stream.numel(), d_pos)
+    stream's length.  Nothing is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API).  Length not checked: d_sync."""
+    _device("sma_find_sync_device", d_pos, device, stream, d_in, d_in_off, d_in_len, d_sync, numel(d_in_len), d_q_stream,
+            d_q_from, numel(d_q_stream), d_pos)
 
 
 def compress_avro_streams_device(d_in, d_block_first, d_block_off, d_block_len, d_block_count, d_sync, max_blocks, stage_bytes,
@@ -345,9 +343,11 @@ def compress_avro_streams_device(d_in, d_block_first, d_block_off, d_block_len, 
     header d_in[d_head_off[s] : + d_head_len[s]] (int64, both or neither) copied in front, written to
     d_out[d_out_off[s]:], where the header's length plus the sum of max_block_length(len) is left for
     it.  max_blocks, stage_bytes (the sum of sma_stage_length) and max_fragments bound the batch.
-    Nothing is synchronised."""
+    Nothing is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API).
+    Length not checked: d_block_off, d_block_len, d_block_count, d_sync."""
     _device("sma_compress_streams_device", d_out, device, stream, d_in, d_block_first, d_block_off, d_block_len, d_block_count,
-            d_sync, d_head_off, d_head_len, d_out_off.numel(), int(max_blocks), int(stage_bytes), int(max_fragments), d_out,
+            d_sync, d_head_off, d_head_len, numel(d_out_off), int(max_blocks), int(stage_bytes), int(max_fragments), d_out,
             d_out_off, d_out_len, d_status, _mode(mode))
 
 

@@ -25,7 +25,7 @@ import os
 import numpy as np
 
 from . import HERE, MODES, SnappyError, _in_arg, _mode
-from ._binding import BLOCKS, BlockChunks, Summary, check, collect, context_cache, device_caller, exclusive_scan, lay_out, load
+from ._binding import BLOCKS, BlockChunks, Summary, check, collect, context_cache, device_caller, exclusive_scan, lay_out, load, numel
 
 LIB_PATH = os.path.join(HERE, "libsnappy_mi355x_blocks.so")
 
@@ -224,9 +224,10 @@ def compress_block_streams_device(format, d_in, d_in_off, d_in_len, max_blocks, 
     """smb_compress_streams_device: input s = d_in[d_in_off[s] : d_in_off[s] + d_in_len[s]] becomes one
     stream at d_out[d_out_off[s]:], where max_length(d_in_len[s], format) bytes are left for it.  d_in /
     d_out uint8, d_in_off / d_in_len / d_out_off / d_out_len int64[nstreams], d_status int32[nstreams];
-    max_blocks bounds the sum of ceil(d_in_len[s] / 65536).  Nothing is synchronised."""
+    max_blocks bounds the sum of ceil(d_in_len[s] / 65536).  Nothing is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
     _device("smb_compress_streams_device", d_out, device, stream, _format(format), d_in, d_in_off, d_in_len,
-            d_in_len.numel(), int(max_blocks), d_out, d_out_off, d_out_len, d_status, _mode(mode))
+            numel(d_in_len), int(max_blocks), d_out, d_out_off, d_out_len, d_status, _mode(mode))
 
 
 def uncompress_block_streams_device(format, d_in, d_in_off, d_in_len, max_chunks, max_fragments, d_out, d_out_off,
@@ -237,9 +238,10 @@ def uncompress_block_streams_device(format, d_in, d_in_off, d_in_len, max_chunks
     (int32).  max_chunks bounds the chunks summed over the streams that are decoded; max_fragments
     (streams_plan's second total, or 0) lets chunks of more than 64 KiB decode by fragments.
     Optional, both or neither: d_chunk_first int32[nstreams + 1], d_chunk_status int32[max_chunks].
-    Nothing is synchronised."""
+    Nothing is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API).  Length not checked: d_chunk_status."""
     _device("smb_uncompress_streams_device", d_out, device, stream, _format(format), d_in, d_in_off, d_in_len,
-            d_in_len.numel(), int(max_chunks), int(max_fragments), d_out, d_out_off, d_out_cap, d_out_len, d_status,
+            numel(d_in_len), int(max_chunks), int(max_fragments), d_out, d_out_off, d_out_cap, d_out_len, d_status,
             d_chunk_first, d_chunk_status)
 
 

@@ -30,7 +30,7 @@ import numpy as np
 
 from . import HERE, MODES, SnappyError, _in_arg, _mode, _out_buffer
 from ._binding import (FRAMING, FRAMING_RANGE, FRAMING_STREAMS, INDEX_KEYS, Chunks, Summary, check, collect,
-                       context_cache, device_caller, exclusive_scan, load)
+                       context_cache, device_caller, exclusive_scan, field_dtypes, load, numel)
 from ._binding import lay_out as _lay_out
 
 LIB_PATH = os.path.join(HERE, "libsnappy_mi355x_framing.so")
@@ -50,9 +50,10 @@ FRAMING_ABI_SYMBOLS = tuple(FRAMING)
 RANGE_ABI_SYMBOLS = tuple(FRAMING_RANGE)
 STREAMS_ABI_SYMBOLS = tuple(FRAMING_STREAMS)
 
-# the index arrays' element types: as the C ABI declares them, and as torch tensors hold the same bits
-_UNSIGNED = dict(zip(INDEX_KEYS, (np.uint8, np.uint64, np.uint32, np.uint32, np.uint32)))
-_SIGNED = dict(zip(INDEX_KEYS, (np.uint8, np.int64, np.int32, np.int32, np.int32)))
+# the index arrays' element types (Chunks.elements): as the C ABI declares them, and as torch tensors
+# hold the same bits
+_UNSIGNED = field_dtypes(Chunks)
+_SIGNED = field_dtypes(Chunks, signed=True)
 
 _lib = None
 
@@ -383,6 +384,12 @@ _device = device_caller(lib, context, FramingError)
 _device_status = device_caller(lib, context, None)
 
 
+def _or_null(d_in, n):
+    """The input argument of a call over d_in[:n]: a tensor of no bytes goes as a null pointer (what is
+    no tensor goes on to the argument checks)."""
+    return None if not n and hasattr(d_in, "numel") else d_in
+
+
 def device_chunks(max_chunks, device=0):
     """Index arrays for up to max_chunks data chunks on the device: a dict of torch tensors (type
     uint8, pay_off int64, pay_len / crc / ulen int32: the C ABI's unsigned values, bit for bit)."""
@@ -392,32 +399,31 @@ def device_chunks(max_chunks, device=0):
             for k in INDEX_KEYS}
 
 
-def _chunks_ref(arrays):
-    return ctypes.byref(Chunks(*(arrays[k].data_ptr() for k in INDEX_KEYS)))
-
-
 def crc32c_batch_device(d_in, d_off, d_len, d_crc, masked=False, stream=None, device=None):
     """d_crc[b] = CRC-32C of d_in[d_off[b] : d_off[b] + d_len[b]] (masked: the framing format's
-    stored form).  d_in uint8, d_off int64, d_len / d_crc int32 CUDA tensors."""
-    _device("smf_crc32c_batch_device", d_in, device, stream, d_in, d_off, d_len, d_len.numel(), d_crc,
+    stored form).  d_in uint8, d_off int64, d_len / d_crc int32 CUDA tensors.
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    _device("smf_crc32c_batch_device", d_in, device, stream, d_in, d_off, d_len, numel(d_len), d_crc,
             1 if masked else 0)
 
 
 def compress_framed_device(d_in, d_out, d_out_len, d_status, mode="fast", stream=None, device=None):
-    """Frame the uint8 tensor d_in into d_out (at least max_framed_length(d_in.numel()) bytes);
-    d_out_len (int64[1]) and d_status (int32[1]) receive the stream's length and status."""
-    n = d_in.numel()
-    _device("smf_compress_device", d_out, device, stream, d_in if n else None, n, d_out, d_out.numel(), d_out_len,
+    """Frame the uint8 tensor d_in into d_out (at least max_framed_length(numel(d_in)) bytes);
+    d_out_len (int64[1]) and d_status (int32[1]) receive the stream's length and status.
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    n = numel(d_in)
+    _device("smf_compress_device", d_out, device, stream, _or_null(d_in, n), n, d_out, numel(d_out), d_out_len,
             d_status, _mode(mode))
 
 
 def index_framed_device(d_in, arrays, d_summary, n=None, stream=None, device=None):
     """Walk the framed stream d_in[:n] on the device with one wave.  arrays: device_chunks(...) or
     None (count only); d_summary: 16 bytes (a uint8[16] or int64[2] tensor) receiving smf_summary
-    -- read it with read_summary() after synchronising."""
-    n = d_in.numel() if n is None else int(n)
-    _device("smf_index_device", d_summary, device, stream, d_in if n else None, n,
-            _chunks_ref(arrays) if arrays is not None else None, arrays["type"].numel() if arrays is not None else 0,
+    -- read it with read_summary() after synchronising.
+    Arguments are checked first (_binding.device_caller; README, Device API).  Length not checked: arrays."""
+    n = numel(d_in) if n is None else int(n)
+    _device("smf_index_device", d_summary, device, stream, _or_null(d_in, n), n,
+            arrays, numel(arrays["type"]) if isinstance(arrays, dict) and "type" in arrays else 0,
             d_summary)
 
 
@@ -429,27 +435,30 @@ def read_summary(d_summary):
 
 def uncompressed_length_framed_device(d_in, d_len, d_status, n=None, stream=None, device=None):
     """d_len (int64[1]) = the total uncompressed length of the framed stream d_in[:n], d_status
-    (int32[1]) = the walk's status."""
-    n = d_in.numel() if n is None else int(n)
-    _device("smf_uncompressed_length_device", d_len, device, stream, d_in if n else None, n, d_len, d_status)
+    (int32[1]) = the walk's status.
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    n = numel(d_in) if n is None else int(n)
+    _device("smf_uncompressed_length_device", d_len, device, stream, _or_null(d_in, n), n, d_len, d_status)
 
 
 def uncompress_chunks_device(d_in, arrays, nchunks, d_out, d_chunk_status, d_out_len, d_status, stream=None,
                              device=None):
     """Decode the first nchunks indexed data chunks of d_in into d_out and check their CRCs
     (smf_uncompress_chunks_device): d_chunk_status int32[nchunks], d_out_len int64[1], d_status
-    int32[1]."""
-    _device("smf_uncompress_chunks_device", d_out, device, stream, d_in, _chunks_ref(arrays), int(nchunks), d_out,
-            d_out.numel(), d_chunk_status, d_out_len, d_status)
+    int32[1].
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    _device("smf_uncompress_chunks_device", d_out, device, stream, d_in, arrays, int(nchunks), d_out,
+            numel(d_out), d_chunk_status, d_out_len, d_status)
 
 
 def uncompress_framed_device(d_in, d_out, d_out_len, d_status, n=None, stream=None, device=None):
     """Index plus decode of the framed stream d_in[:n] into d_out, with one host synchronisation
     of `stream` between them.  Returns the host-known status (0, a structural error, or
     SM_BUFFER_TOO_SMALL with the needed size in d_out_len) instead of raising; the decode's own
-    status (CRC, payload errors) arrives in d_status on the stream."""
-    n = d_in.numel() if n is None else int(n)
-    return _device_status("smf_uncompress_device", d_out, device, stream, d_in if n else None, n, d_out, d_out.numel(),
+    status (CRC, payload errors) arrives in d_status on the stream.
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    n = numel(d_in) if n is None else int(n)
+    return _device_status("smf_uncompress_device", d_out, device, stream, _or_null(d_in, n), n, d_out, numel(d_out),
                           d_out_len, d_status)
 
 
@@ -457,15 +466,17 @@ def compress_framed_indexed_device(d_in, d_out, d_out_len, d_status, arrays, d_c
                                    stream=None, device=None):
     """compress_framed_device that also writes the stream's seek index (smf_compress_indexed_device):
     arrays = device_chunks(max_chunks), d_chunk_off int64[max_chunks + 1], d_nchunks int32[1];
-    max_chunks is taken from d_chunk_off and must be at least ceil(d_in.numel() / 65536)."""
-    n = d_in.numel()
-    _device("smf_compress_indexed_device", d_out, device, stream, d_in if n else None, n, d_out, d_out.numel(),
-            d_out_len, d_status, _mode(mode), _chunks_ref(arrays), d_chunk_off, d_chunk_off.numel() - 1, d_nchunks)
+    max_chunks is taken from d_chunk_off and must be at least ceil(numel(d_in) / 65536).
+    Arguments are checked first (_binding.device_caller; README, Device API).  Length not checked: arrays."""
+    n = numel(d_in)
+    _device("smf_compress_indexed_device", d_out, device, stream, _or_null(d_in, n), n, d_out, numel(d_out),
+            d_out_len, d_status, _mode(mode), arrays, d_chunk_off, max(numel(d_chunk_off) - 1, 0), d_nchunks)
 
 
 def chunk_offsets_device(d_ulen, nchunks, d_chunk_off, stream=None, device=None):
     """d_chunk_off (int64[nchunks + 1]) = the exclusive scan of d_ulen[:nchunks] (int32, as
-    device_chunks()["ulen"]): completes an index_framed_device index."""
+    device_chunks()["ulen"]): completes an index_framed_device index.
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
     _device("smf_chunk_offsets_device", d_chunk_off, device, stream, d_ulen, int(nchunks), d_chunk_off)
 
 
@@ -473,10 +484,11 @@ def uncompress_ranges_device(d_in, arrays, d_chunk_off, nchunks, d_lo, d_len, ma
                              d_out_len, d_range_status, n=None, stream=None, device=None):
     """Batched ranged decode (smf_uncompress_ranges_device) of the indexed framed stream d_in[:n]:
     range r = bytes [d_lo[r], d_lo[r] + d_len[r]) of the content, written to d_out[d_out_off[r]:];
-    d_lo / d_len / d_out_off / d_out_len int64[nranges], d_range_status int32[nranges]."""
-    n = d_in.numel() if n is None else int(n)
-    _device("smf_uncompress_ranges_device", d_out, device, stream, d_in if n else None, n, _chunks_ref(arrays),
-            d_chunk_off, int(nchunks), d_lo, d_len, d_lo.numel(), int(max_range_chunks), d_out, d_out_off, d_out_len,
+    d_lo / d_len / d_out_off / d_out_len int64[nranges], d_range_status int32[nranges].
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    n = numel(d_in) if n is None else int(n)
+    _device("smf_uncompress_ranges_device", d_out, device, stream, _or_null(d_in, n), n, arrays,
+            d_chunk_off, int(nchunks), d_lo, d_len, numel(d_lo), int(max_range_chunks), d_out, d_out_off, d_out_len,
             d_range_status)
 
 
@@ -485,8 +497,9 @@ def compress_framed_streams_device(d_in, d_in_off, d_in_len, max_blocks, d_out, 
     """Batched framing (smf_compress_streams_device): input s = d_in[d_in_off[s] : d_in_off[s] +
     d_in_len[s]] becomes one framed stream at d_out[d_out_off[s]:], where max_framed_length(d_in_len[s])
     bytes are left for it.  d_in / d_out uint8, d_in_off / d_in_len / d_out_off / d_out_len
-    int64[nstreams], d_status int32[nstreams]; max_blocks bounds the sum of ceil(d_in_len[s] / 65536)."""
-    _device("smf_compress_streams_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(),
+    int64[nstreams], d_status int32[nstreams]; max_blocks bounds the sum of ceil(d_in_len[s] / 65536).
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    _device("smf_compress_streams_device", d_out, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len),
             int(max_blocks), d_out, d_out_off, d_out_len, d_status, _mode(mode))
 
 
@@ -496,8 +509,9 @@ def uncompress_framed_streams_device(d_in, d_in_off, d_in_len, max_chunks, d_out
     d_in_off[s] + d_in_len[s]] decodes into d_out[d_out_off[s] : d_out_off[s] + d_out_cap[s]]; per
     stream d_out_len (int64) and d_status (int32) as uncompress_framed_device leaves them for that
     stream alone.  max_chunks bounds the data chunks summed over the streams that are decoded.
-    Optional, both or neither: d_chunk_first int32[nstreams + 1], d_chunk_status int32[max_chunks]."""
-    _device("smf_uncompress_streams_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(),
+    Optional, both or neither: d_chunk_first int32[nstreams + 1], d_chunk_status int32[max_chunks].
+    Arguments are checked first (_binding.device_caller; README, Device API).  Length not checked: d_chunk_status."""
+    _device("smf_uncompress_streams_device", d_out, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len),
             int(max_chunks), d_out, d_out_off, d_out_cap, d_out_len, d_status, d_chunk_first, d_chunk_status)
 
 

@@ -28,7 +28,7 @@ import os
 import numpy as np
 
 from . import HERE, MODES, SnappyError, _capacities, _mode, pack_blocks, slot_offsets
-from ._binding import MULTI, MULTI_RANGE, check, collect, context_cache, device_caller, exclusive_scan, load
+from ._binding import MULTI, MULTI_RANGE, check, collect, context_cache, device_caller, exclusive_scan, load, numel
 
 LIB_PATH = os.path.join(HERE, "libsnappy_mi355x_multi.so")
 BLOCK = 65536
@@ -336,24 +336,27 @@ def compress_streams_device(d_in, d_in_off, d_in_len, max_fragments, d_out, d_ou
                             d_frag_first=None, d_frag_pos=None, mode="fast", stream=None, device=None):
     """smm_compress_device: d_in / d_out uint8, d_in_off / d_out_off int64, d_in_len / d_out_len /
     d_status int32 CUDA tensors (the C ABI's unsigned values, bit for bit); the index tensors
-    (int32, nstreams + 1 and max_fragments entries) both or neither.  Nothing is synchronised."""
-    _device("smm_compress_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), int(max_fragments),
+    (int32, nstreams + 1 and max_fragments entries) both or neither.  Nothing is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API).  Length not checked: d_frag_pos."""
+    _device("smm_compress_device", d_out, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len), int(max_fragments),
             d_out, d_out_off, d_out_len, d_status, d_frag_first, d_frag_pos, _mode(mode))
 
 
 def uncompress_streams_device(d_in, d_in_off, d_in_len, max_fragments, d_out, d_out_off, d_out_cap, d_out_len, d_status,
                               d_frag_first=None, d_frag_pos=None, stream=None, device=None):
     """smm_uncompress_device (tensor types as in compress_streams_device).  max_fragments: the
-    entries of d_frag_pos.  Nothing is synchronised."""
-    _device("smm_uncompress_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(),
+    entries of d_frag_pos.  Nothing is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API).  Length not checked: d_frag_pos."""
+    _device("smm_uncompress_device", d_out, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len),
             int(max_fragments), d_out, d_out_off, d_out_cap, d_out_len, d_status, d_frag_first, d_frag_pos)
 
 
 def index_streams_device(d_in, d_in_off, d_in_len, max_fragments, d_frag_first, d_frag_pos, d_built, d_status,
                          d_out_cap=None, stream=None, device=None):
     """smm_index_device (tensor types as in compress_streams_device; d_built uint8, nstreams
-    entries; d_frag_pos max_fragments entries; d_out_cap None: no cap).  Nothing is synchronised."""
-    _device("smm_index_device", d_in, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), int(max_fragments),
+    entries; d_frag_pos max_fragments entries; d_out_cap None: no cap).  Nothing is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API).  Length not checked: d_frag_pos."""
+    _device("smm_index_device", d_in, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len), int(max_fragments),
             d_out_cap, d_frag_first, d_frag_pos, d_built, d_status)
 
 
@@ -363,10 +366,11 @@ def uncompress_stream_ranges_device(d_in, d_in_off, d_in_len, d_frag_first, d_fr
     """smm_uncompress_ranges_device (tensor types as in compress_streams_device; d_range_stream, d_lo,
     d_len, d_out_len and d_status int32 with an entry per range, d_out_off int64).  nentries: the
     entries of d_frag_pos (default: all of the tensor).  max_range_fragments: at least the sum of
-    range_fragment_count over the ranges.  Nothing is synchronised."""
-    _device("smm_uncompress_ranges_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), d_frag_first,
-            d_frag_pos, d_frag_pos.numel() if nentries is None else int(nentries), d_range_stream, d_lo, d_len,
-            d_lo.numel(), int(max_range_fragments), d_out, d_out_off, d_out_len, d_status)
+    range_fragment_count over the ranges.  Nothing is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    _device("smm_uncompress_ranges_device", d_out, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len), d_frag_first,
+            d_frag_pos, numel(d_frag_pos) if nentries is None else int(nentries), d_range_stream, d_lo, d_len,
+            numel(d_lo), int(max_range_fragments), d_out, d_out_off, d_out_len, d_status)
 
 
 def last_indexed(device=0):

@@ -39,7 +39,7 @@ import numpy as np
 
 from . import HERE, SnappyError, _in_arg, _mode
 from ._binding import (PAGE_KEYS, PARQUET, PARQUET_WRITE, Pages, Summary, check, collect, context_cache, device_caller,
-                       exclusive_scan, lay_out, load)
+                       exclusive_scan, field_dtypes, lay_out, load, numel)
 
 LIB_PATH = os.path.join(HERE, "libsnappy_mi355x_parquet.so")
 
@@ -50,9 +50,7 @@ SMQ_ERR_CRC = 75
 PAGE_DATA, PAGE_INDEX, PAGE_DICTIONARY, PAGE_DATA_V2 = 0, 1, 2, 3
 PAGE_HAS_CRC, PAGE_COMPRESSED = 1, 2
 INDEX_KEYS = PAGE_KEYS  # smq_pages' arrays, in its order
-PAGE_DTYPES = {"hdr_off": np.uint64, "hdr_len": np.uint32, "body_len": np.uint32, "usize": np.uint32, "levels": np.uint32,
-               "out_off": np.uint64, "num_values": np.int32, "type": np.int32, "encoding": np.int32, "flags": np.uint32,
-               "crc": np.uint32}
+PAGE_DTYPES = field_dtypes(Pages)  # the arrays' element types as the C ABI declares them (Pages.elements)
 
 PARQUET_ABI_SYMBOLS = tuple(PARQUET)  # exported symbols of include/snappy_mi355x_parquet.h (tests/test_parquet_host.py)
 PARQUET_WRITE_ABI_SYMBOLS = tuple(PARQUET_WRITE)  # and of include/snappy_mi355x_parquet_write.h (tests/test_parquet_write_host.py)
@@ -277,12 +275,11 @@ def uncompress_column_chunks_device(d_in, d_in_off, d_in_len, max_pages, max_fra
     (chunks_plan's second total, or 0) lets compressed sections of more than 64 KiB decode by
     fragments.  Optional, both or neither: d_page_first int32[nchunks + 1], d_page_status
     int32[max_pages].  Optional: d_pages, a dict of tensors of max_pages entries keyed as INDEX_KEYS
-    (int64 for hdr_off and out_off, int32 for the others), the page table.  Nothing is synchronised."""
-    pages = None
-    if d_pages is not None:
-        pages = ctypes.byref(Pages(*(d_pages[k].data_ptr() for k in INDEX_KEYS)))
-    _device("smq_uncompress_chunks_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), int(max_pages),
-            int(max_fragments), 1 if verify_crc else 0, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_page_first, pages,
+    (int64 for hdr_off and out_off, int32 for the others), the page table.  Nothing is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API).
+    Length not checked: d_pages, d_page_status."""
+    _device("smq_uncompress_chunks_device", d_out, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len), int(max_pages),
+            int(max_fragments), 1 if verify_crc else 0, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_page_first, d_pages,
             d_page_status)
 
 
@@ -294,19 +291,19 @@ def compress_column_chunks_device(d_in, d_in_off, d_in_len, max_pages, stage_byt
     d_out_len (int64) and d_status (int32).  max_pages, stage_bytes and max_fragments are
     compress_chunks_plan's three totals (or bounds on them).  Optional, both or neither: d_page_first
     int32[nchunks + 1], d_page_status int32[max_pages].  Optional: d_pages, a dict of tensors of
-    max_pages entries keyed as INDEX_KEYS, the OUTPUT chunks' page table.  Nothing is synchronised."""
-    pages = None
-    if d_pages is not None:
-        pages = ctypes.byref(Pages(*(d_pages[k].data_ptr() for k in INDEX_KEYS)))
-    _device("smqe_compress_chunks_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), int(max_pages),
-            int(stage_bytes), int(max_fragments), d_out, d_out_off, d_out_cap, d_out_len, d_status, d_page_first, pages,
+    max_pages entries keyed as INDEX_KEYS, the OUTPUT chunks' page table.  Nothing is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API).
+    Length not checked: d_pages, d_page_status."""
+    _device("smqe_compress_chunks_device", d_out, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len), int(max_pages),
+            int(stage_bytes), int(max_fragments), d_out, d_out_off, d_out_cap, d_out_len, d_status, d_page_first, d_pages,
             d_page_status, _mode(mode))
 
 
 def crc32_device(d_in, d_off, d_len, d_crc, stream=None, device=None):
     """smq_crc32_device: d_crc[i] (int32, the CRC's 32 bits) = the CRC-32 (zlib.crc32) of
-    d_in[d_off[i] : d_off[i] + d_len[i]]; d_off and d_len int64.  Nothing is synchronised."""
-    _device("smq_crc32_device", d_crc, device, stream, d_in, d_off, d_len, d_len.numel(), d_crc)
+    d_in[d_off[i] : d_off[i] + d_len[i]]; d_off and d_len int64.  Nothing is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    _device("smq_crc32_device", d_crc, device, stream, d_in, d_off, d_len, numel(d_len), d_crc)
 
 
 def last_indexed(device=0):

@@ -25,7 +25,7 @@ import os
 import numpy as np
 
 from . import HERE, MODES, SnappyError, _in_arg, _mode
-from ._binding import TABLE, Summary, check, context_cache, device_caller, exclusive_scan, lay_out, load
+from ._binding import TABLE, Summary, check, context_cache, device_caller, exclusive_scan, lay_out, load, numel
 
 LIB_PATH = os.path.join(HERE, "libsnappy_mi355x_table.so")
 
@@ -309,8 +309,10 @@ def index_tables_device(d_in, d_in_off, d_in_len, max_blocks, max_index_bytes, d
     """smt_index_tables_device: table t = d_in[d_in_off[t] : d_in_off[t] + d_in_len[t]] (int64 both);
     d_block_first int32[ntables + 1], d_handle_off / d_handle_size int64[max_blocks], d_status
     int32[ntables].  max_index_bytes bounds the decoded index lengths, each rounded up to 16.  Nothing
-    is synchronised."""
-    _device("smt_index_tables_device", d_status, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), int(max_blocks),
+    is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API).
+    Length not checked: d_handle_off, d_handle_size."""
+    _device("smt_index_tables_device", d_status, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len), int(max_blocks),
             int(max_index_bytes), 1 if verify_crc else 0, d_block_first, d_handle_off, d_handle_size, d_status)
 
 
@@ -320,8 +322,10 @@ def uncompress_tables_device(d_in, d_in_off, d_in_len, max_blocks, max_index_byt
     """smt_uncompress_tables_device: every data block of table t decodes into d_out[d_out_off[t] :
     d_out_off[t] + d_out_cap[t]]; per table d_out_len (int64) and d_status (int32).  Optional:
     d_block_first int32[ntables + 1] and, with max_blocks entries each, d_handle_off, d_handle_size,
-    d_block_out_off, d_block_len (int64) and d_block_status (int32).  Nothing is synchronised."""
-    _device("smt_uncompress_tables_device", d_out, device, stream, d_in, d_in_off, d_in_len, d_in_len.numel(), int(max_blocks),
+    d_block_out_off, d_block_len (int64) and d_block_status (int32).  Nothing is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API).
+    Length not checked: d_handle_off, d_handle_size, d_block_out_off, d_block_len, d_block_status."""
+    _device("smt_uncompress_tables_device", d_out, device, stream, d_in, d_in_off, d_in_len, numel(d_in_len), int(max_blocks),
             int(max_index_bytes), int(max_fragments), 1 if verify_crc else 0, d_out, d_out_off, d_out_cap, d_out_len, d_status,
             d_block_first, d_handle_off, d_handle_size, d_block_out_off, d_block_len, d_block_status)
 
@@ -330,8 +334,9 @@ def uncompress_table_blocks_device(d_in, d_blk_off, d_blk_size, max_fragments, d
                                    verify_crc=True, stream=None, device=None):
     """smt_uncompress_blocks_device: block j's contents are d_in[d_blk_off[j] : + d_blk_size[j]]
     (int64, trusted) with its trailer behind; it decodes into d_out[d_out_off[j] : + d_out_cap[j]];
-    per block d_out_len (int64) and d_status (int32).  Nothing is synchronised."""
-    _device("smt_uncompress_blocks_device", d_out, device, stream, d_in, d_blk_off, d_blk_size, d_blk_off.numel(),
+    per block d_out_len (int64) and d_status (int32).  Nothing is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API)."""
+    _device("smt_uncompress_blocks_device", d_out, device, stream, d_in, d_blk_off, d_blk_size, numel(d_blk_off),
             int(max_fragments), 1 if verify_crc else 0, d_out, d_out_off, d_out_cap, d_out_len, d_status)
 
 
@@ -343,9 +348,11 @@ def compress_table_blocks_device(d_in, d_block_first, d_block_off, d_block_len, 
     d_out[d_out_off[t]:], where the sum of max_block_length(len) is left for it; per block
     d_handle_off / d_handle_size (int64), per table d_out_len (int64) and d_status (int32).
     max_blocks, stage_bytes (the sum of smt_stage_length) and max_fragments bound the batch.  Nothing
-    is synchronised."""
+    is synchronised.
+    Arguments are checked first (_binding.device_caller; README, Device API).
+    Length not checked: d_block_off, d_block_len, d_handle_off, d_handle_size."""
     _device("smt_compress_blocks_device", d_out, device, stream, d_in, d_block_first, d_block_off, d_block_len,
-            d_out_off.numel(), int(max_blocks), int(stage_bytes), int(max_fragments), d_out, d_out_off, d_handle_off,
+            numel(d_out_off), int(max_blocks), int(stage_bytes), int(max_fragments), d_out, d_out_off, d_handle_off,
             d_handle_size, d_out_len, d_status, _mode(mode))
 
 

@@ -8,6 +8,8 @@ import re
 import numpy as np
 import pytest
 
+from prototype_types import assert_device_elements
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCALARS = {"size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64, "int": ctypes.c_int,
            "int32_t": ctypes.c_int32, "sm_status": ctypes.c_int32}
@@ -61,9 +63,13 @@ def _c_class(decl):
     return _class(SCALARS[words[0]])
 
 
+DEVICE_POINTERS = {"RAW": 58, "FRAMING": 81, "MULTI": 33}  # the pointer parameters of the *_device functions, ctx and stream among them
+
+
 @pytest.mark.parametrize("header, table, count", [("snappy_mi355x.h", "RAW", 36), ("snappy_mi355x_framing.h", "FRAMING", 33),
                                                   ("snappy_mi355x_multi.h", "MULTI", 15)])
 def test_tables_match_the_headers(binding, header, table, count):
+    device_pointers = DEVICE_POINTERS[table]
     declared, table = _declarations(header), getattr(binding, table)
     assert len(declared) == count and set(declared) == set(table)
     for name, (ret, params) in declared.items():
@@ -72,6 +78,7 @@ def test_tables_match_the_headers(binding, header, table, count):
         assert _class(restype) == _c_class(ret), name
         for k, (t, p) in enumerate(zip(argtypes, params)):
             assert t is not None and _class(t) == _c_class(p), "%s: argument %d (%s)" % (name, k, p.strip())
+    assert assert_device_elements(binding, declared, table) == device_pointers
 
 
 def test_every_function_is_in_one_table(binding, sm, fr, mu):

@@ -13,6 +13,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from prototype_types import assert_device_elements
+
 import multi_range_ref as M
 import multi_ref as R
 from conftest import ROOT
@@ -78,6 +80,7 @@ def test_table_matches_the_header(mu, binding):
         assert _class(restype) == _c_class(ret), name
         for k, (t, p) in enumerate(zip(argtypes, params)):
             assert t is not None and _class(t) == _c_class(p), "%s: argument %d (%s)" % (name, k, p.strip())
+    assert assert_device_elements(binding, declared, table) == 14  # the pointer parameters of the *_device functions, ctx and stream among them
 
 
 def test_symbols_export_from_the_multi_library(mu):

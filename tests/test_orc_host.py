@@ -14,6 +14,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from prototype_types import assert_device_elements
+
 import orc_ref as R
 from conftest import ROOT
 
@@ -248,6 +250,7 @@ def test_table_matches_the_header(sm, orc):
         assert _class(restype) == _c_class(ret), name
         for k, (t, p) in enumerate(zip(argtypes, params)):
             assert t is not None and _class(t) == _c_class(p), "%s: argument %d (%s)" % (name, k, p.strip())
+    assert assert_device_elements(binding, declared, table) == 21  # the pointer parameters of the *_device functions, ctx and stream among them
     assert orc.ORC_ABI_SYMBOLS == tuple(table)
     others = [binding.RAW, binding.FRAMING, binding.MULTI, binding.MULTI_RANGE, binding.BLOCKS]
     assert not set(table) & set().union(*others)  # a group of its own

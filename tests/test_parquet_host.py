@@ -16,6 +16,8 @@ import zlib
 import numpy as np
 import pytest
 
+from prototype_types import assert_device_elements
+
 import parquet_ref as R
 from conftest import ROOT
 
@@ -297,6 +299,7 @@ def test_table_matches_the_header(sm, pq):
         assert _class(restype) == _c_class(ret), name
         for k, (t, p) in enumerate(zip(argtypes, params)):
             assert t is not None and _class(t) == _c_class(p), "%s: argument %d (%s)" % (name, k, p.strip())
+    assert assert_device_elements(binding, declared, table) == 19  # the pointer parameters of the *_device functions, ctx and stream among them
     assert pq.PARQUET_ABI_SYMBOLS == tuple(table)
     others = [binding.RAW, binding.FRAMING, binding.MULTI, binding.MULTI_RANGE, binding.BLOCKS, binding.ORC]
     assert not set(table) & set().union(*others)  # a group of its own

@@ -15,6 +15,8 @@ import subprocess
 
 import pytest
 
+from prototype_types import assert_device_elements
+
 import avro_ref
 import table_ref as R
 from conftest import ROOT
@@ -320,6 +322,7 @@ def test_table_matches_the_header(sm, tb):
         assert _class(restype) == _c_class(ret), name
         for k, (t, p) in enumerate(zip(argtypes, params)):
             assert t is not None and _class(t) == _c_class(p), "%s: argument %d (%s)" % (name, k, p.strip())
+    assert assert_device_elements(binding, declared, table) == 47  # the pointer parameters of the *_device functions, ctx and stream among them
     assert tb.TABLE_ABI_SYMBOLS == tuple(table)
     others = [binding.RAW, binding.FRAMING, binding.MULTI, binding.BLOCKS, binding.ORC, binding.PARQUET, binding.PARQUET_WRITE,
               binding.AVRO]
