@@ -1,5 +1,5 @@
-"""What the eight ctypes bindings of this package share (__init__.py, framing.py, multi.py, blocks.py, orc.py,
-parquet.py, avro.py, table.py): the
+"""What the nine ctypes bindings of this package share (__init__.py, framing.py, multi.py, blocks.py, orc.py,
+parquet.py, avro.py, table.py, kafka.py): the
 prototype table of each library, the loader and the per-device context cache, the status, stream
 and device rules of the device wrappers, and the layout of a batch in one host buffer.
 
@@ -30,7 +30,7 @@ tests/test_bindings.py holds every entry against the declaration in include/*.h
 (tests/test_blocks_host.py: the BLOCKS table; tests/test_orc_host.py: ORC;
 tests/test_multi_range_host.py: MULTI_RANGE; tests/test_parquet_host.py: PARQUET;
 tests/test_parquet_write_host.py: PARQUET_WRITE; tests/test_avro_host.py: AVRO;
-tests/test_table_host.py: TABLE).
+tests/test_table_host.py: TABLE; tests/test_kafka_host.py: KAFKA).
 """
 import ctypes
 import os
@@ -335,6 +335,25 @@ TABLE = {  # include/snappy_mi355x_table.h (smt_summary has Summary's layout)
     "smt_compress_blocks": "s pppppuppppppi",
 }
 
+KAFKA = {  # include/snappy_mi355x_kafka.h (smk_summary is kafka.py's own structure, passed by reference)
+    "smk_status_message": "c s",
+    "smk_version": "c",
+    "smk_index": "s pzpppppup",
+    "smk_segments_plan": "s pppupuupppQQQ",
+    "smk_compress_plan": "s pppuupppQQQ",
+    "smk_max_segment_length": "q qq",
+    "smk_stage_length": "q q",
+    "smk_segments_scratch_bytes": "z uuuq",
+    "smk_write_batch": "s quuppzpzZ",
+    "smk_ctx_create": "p i",
+    "smk_ctx_destroy": "v p",
+    "smk_ctx_last_indexed": "i p",
+    "smk_uncompress_segments_device": "s pbd[4]d[4]uuuuibd[4]d[4]d[4]t[4]w[4+]d[5]d[5]d[5]w[5]t[5]p",
+    "smk_compress_segments_device": "s pbd[4]d[4]uuuqbd[4]d[4]t[4]ip",
+    "smk_uncompress_segments": "s ppppuippppppuppppp",
+    "smk_compress_segments": "s ppppupppppi",
+}
+
 
 _ARGUMENT = re.compile(r"([A-Za-z])(?:\[(=?)(\d+)(\+?)\])?")
 
@@ -424,6 +443,7 @@ def numel(tensor):
 
 
 TABLES = (RAW, FRAMING, MULTI, MULTI_RANGE, BLOCKS, ORC, PARQUET, PARQUET_WRITE, AVRO, TABLE)
+MORE_TABLES = (KAFKA,)  # the libraries behind those: searched after TABLES, judged alike
 _BYREF = type(ctypes.byref(ctypes.c_int()))
 _plans, _dtypes = {}, {}
 
@@ -433,7 +453,7 @@ def tensor_plan(name):
     from its table entry; position counts as the header does (ctx is 0)."""
     plan = _plans.get(name)
     if plan is None:
-        sig = next(t[name] for t in TABLES if name in t)
+        sig = next(t[name] for t in TABLES + MORE_TABLES if name in t)
         plan = _plans[name] = [(k, letter, mark) for k, (letter, mark) in enumerate(arguments(sig)[1])
                                if letter in ELEMENTS or letter in ARRAYS or letter == "r"]
     return plan

@@ -2,7 +2,8 @@
 # (gfx950 only) next to the package, linking libsnappy_mi355x.so by name (found beside it through
 # $ORIGIN; ../Makefile builds it first).  The including Makefile sets LIB, PFX (the sources' and
 # the ABI's prefix), VERSION_MACRO, SRCS, HOSTSRCS and its own HDRS; optionally LINK, the further
-# companions it links by name (../blocks: multi), which their own Makefiles build first.
+# companions it links by name (../blocks: multi), which their own Makefiles build first, and
+# CHECK_EXTRA, other libraries' host-only files that its own host-only file calls into (../kafka).
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 MK = ../common/companion.mk
@@ -14,6 +15,7 @@ EXTRA ?=
 BASE = --offload-arch=$(ARCH) -O3 -std=c++17 -fno-strict-aliasing -fPIC -Wall $(EXTRA)
 MAIN = ../../libsnappy_mi355x.so
 LINK ?=
+CHECK_EXTRA ?=
 OUT ?= ../../libsnappy_mi355x_$(LIB).so
 OBJ ?= build
 OBJS = $(patsubst %.hip,$(OBJ)/%.o,$(SRCS)) $(patsubst %.cpp,$(OBJ)/%.o,$(HOSTSRCS))
@@ -47,9 +49,9 @@ $(OUT): $(OBJS) $(MAIN) $(LINK:%=../../libsnappy_mi355x_%.so)
 host_check: $(OBJ)/$(CHECK)
 	$(OBJ)/$(CHECK)
 
-$(OBJ)/$(CHECK): $(CHECK).cpp $(HOSTSRCS) $(HDRS) Makefile $(MK)
+$(OBJ)/$(CHECK): $(CHECK).cpp $(HOSTSRCS) $(CHECK_EXTRA) $(HDRS) Makefile $(MK)
 	@mkdir -p $(OBJ)
-	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(CHECK).cpp $(HOSTSRCS)
+	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $@ $(CHECK).cpp $(HOSTSRCS) $(CHECK_EXTRA)
 
 clean:
 	rm -rf $(OUT) $(OBJ)
